@@ -6,7 +6,7 @@ forward -> forward_loss -> zero_grad -> backward (-> gradient all-reduce) -> opt
 on synthetic 256x256x3 crops already resident in HBM, 16 joints, 64x64 heat-maps.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hg2_js|hg1|hg8_js|resnet34] [--batch B]
-                  [--global-batch G]
+                  [--global-batch G] [--dump-outputs DIR]
 
 For N > 1 either `python bench.py --gpus N` (it starts its own N ranks as a child `python -m torch.distributed.run`, forwards
 rank 0's line and exit code) or `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` directly (one rank
@@ -27,6 +27,10 @@ Besides the whole-job throughput the line carries
   parity       — max |dcoord| and PCKh@0.5 of the HIP path vs the CPU oracle on a small fixed batch with
                  the weights the timed steps ended on (outside the timed region);
   head_roofline — the DSNT head kernels alone on a B = 1024 batch: achieved HBM GB/s.
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (rank 0):
+the coordinates of every stack, the loss, the last stack's heat-maps, and a fixed seeded sample of the updated parameters
+and of the gradients (inference: the coordinates of both forms).  Inputs and weights are seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -519,6 +523,31 @@ def head_roofline(batch=1024, iters=10):
             'ms_fwd_loss_bwd': round(ms, 4)}
 
 
+DUMP_SAMPLE = 1 << 20      # entries of a flat parameter / gradient vector that --dump-outputs keeps (fixed, seeded, sorted)
+
+
+def _sample_flat(tensors, name):
+    """A fixed seeded sample of the concatenation of `tensors` (None counts as zeros), as a float32 array."""
+    import numpy as np
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    r = np.random.Generator(np.random.PCG64([1234, len(name), flat.numel() % 65521]))
+    idx = np.sort(r.choice(flat.numel(), size=min(DUMP_SAMPLE, flat.numel()), replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/<name>.npy each (float32 / float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        np.save(os.path.join(path, name + '.npy'), a)
+    assert total <= 64 << 20, 'dump of %d bytes exceeds 64 MB' % total
+
+
 def infer_bench(model, x, batch, world, rank, args):
     """Eval-mode forward throughput (replicas only across GPUs: no collective), with and without the reference's
     horizontal-flip test-time augmentation (inference.py:33-48: both orientations through the backbone, the flipped
@@ -536,7 +565,7 @@ def infer_bench(model, x, batch, world, rank, args):
             hm = model.forward_part1(torch.cat([x, x.flip(-1)], 0))[-1]
             hm2 = hm[batch:].flip(-1).index_select(-3, idx)
             return model.forward_part2([(hm[:batch] + hm2) / 2])[-1]
-    res = {}
+    res, last = {}, {}
     for name, fn in (('plain', plain), ('flip_tta', flipped)):
         for _ in range(max(args.warmup, 1)):
             fn()
@@ -545,11 +574,13 @@ def infer_bench(model, x, batch, world, rank, args):
             dist.barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            fn()
+            last[name] = fn()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         res[name] = (time.perf_counter() - t0) / args.steps
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'coords_plain': last['plain'], 'coords_flip_tta': last['flip_tta']})
     if rank == 0:
         out = {'metric': 'images/sec (inference, eval-mode forward, 256x256, 16 joints)', 'value': round(world * batch / res['plain'], 1),
                'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -629,6 +660,9 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extras', action='store_true', help='skip the parity / head / dominant-kernel legs (profiling)')
     ap.add_argument('--force-dp', action='store_true', help='wire the data-parallel hooks even at world size 1 (testing)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (coords, loss, heat-maps, a fixed sample '
+                         'of the updated parameters and of the gradients) as DIR/<name>.npy (rank 0)')
     ap.add_argument('--baseline-ips', type=float, default=None,
                     help='images/sec of the 1-GPU run of the same scaling mode: the line then carries `efficiency` = '
                          'value / (N x this)')
@@ -703,7 +737,7 @@ def main():
         loss.backward()
         opt.step()
         guard.poll()
-        return loss
+        return out, loss
 
     for _ in range(args.warmup):
         step()
@@ -713,7 +747,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        last_out, loss = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -725,6 +759,13 @@ def main():
         elapsed = t.item()
     final_loss = float(loss.item())
     guard.sync()
+    if rank == 0 and args.dump_outputs:
+        params = list(model.parameters())
+        arrays = {'coords%d' % i: c for i, c in enumerate(last_out)}
+        arrays.update(loss=loss.detach().double().reshape(1), heatmaps=model.heatmaps,
+                      params_sample=_sample_flat(params, 'params'),
+                      grads_sample=_sample_flat([p.grad if p.grad is not None else torch.zeros_like(p) for p in params], 'grads'))
+        dump_outputs(args.dump_outputs, arrays)
     exposed = dp.reducer.exposed_comm_ms() if dp is not None else None
 
     out = None

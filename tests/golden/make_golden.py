@@ -12,6 +12,9 @@ Families:
   hg1_128 / hg2_128 / hg2_256 / hg8_128   end-to-end model: coords of EVERY stack, loss, per-parameter grad norms
                 (hg8 = experiments/hourglass.json: eight stacks, seven inter-stack remaps, hourglass.py:166-175)
   pckh          PCKh on synthetic predictions (reference evaluator restated: torchnet absent)
+  oracle_vs_reference   the reference's answers behind tests/test_oracle_vs_reference.py: each model is built
+                the way the test builds the oracle's, its weights loaded into the reference, and what the reference
+                returns stored (small outputs whole; gradients / buffers / large maps as per-tensor segment summaries)
 """
 import os
 import sys
@@ -173,11 +176,185 @@ def pckh():
     np.savez_compressed(os.path.join(HERE, 'pckh.npz'), **out)
 
 
+SEG_SAMPLES = 512
+
+
+def segments(prefix, named, out, samples=SEG_SAMPLES):
+    """Summary of a list of (name, tensor): per tensor numel / max|.| / L2 / sum, plus seeded samples of the
+    concatenation (tests/golden_util.check_segments)."""
+    names = [n for n, _ in named]
+    flat = [t.detach().double().reshape(-1).numpy() for _, t in named]
+    a = np.concatenate(flat)
+    out[prefix + '.names'] = np.array(names)
+    out[prefix + '.numel'] = np.array([f.size for f in flat], dtype=np.int64)
+    out[prefix + '.max'] = np.array([np.abs(f).max() if f.size else 0.0 for f in flat])
+    out[prefix + '.l2'] = np.array([np.sqrt((f * f).sum()) for f in flat])
+    out[prefix + '.sum'] = np.array([f.sum() for f in flat])
+    r = np.random.Generator(np.random.PCG64([11, len(prefix), a.size % 65521]))
+    idx = np.sort(r.choice(a.size, size=min(samples, a.size), replace=False))
+    out[prefix + '.idx'] = idx.astype(np.int32)
+    out[prefix + '.val'] = a[idx]
+
+
+def oracle_vs_reference(ref_nn, ref_hg, ref_model):
+    """The reference's side of every test in tests/test_oracle_vs_reference.py, on the inputs that test makes."""
+    import copy
+    from dsnt_oracle import model as omodel, resnet as oresnet, util as outil
+    ref_util = refimport.load_reference_module('dsnt.util')
+    out = {}
+    # test_hourglass_model_forward_loss_grads
+    for base, reg, dtype in [('hg1', 'none', torch.float64), ('hg2', 'js', torch.float64), ('hg2', 'js', torch.float32),
+                             ('hg2', 'var', torch.float64), ('hg2', 'kl', torch.float64), ('hg2', 'mse', torch.float64)]:
+        k = 'model.%s_%s_%s.' % (base, reg, str(dtype).split('.')[-1])
+        mine = omodel.build_mpii_pose_model(base=base, output_strat='dsnt', reg=reg, reg_coeff=1.0)
+        synthetic.fill_state_dict(mine, seed=0)
+        mine.to(dtype)
+        ref = ref_model.build_mpii_pose_model(base=base, output_strat='dsnt', reg=reg, reg_coeff=1.0).to(dtype)
+        out[k + 'keys'] = np.array(list(ref.state_dict().keys()))
+        ref.load_state_dict(mine.state_dict())
+        x, target, mask = synthetic.batch(2, size=128, seed=1, mask_p=0.8, dtype=dtype)
+        ref.train()
+        outs = ref(x)
+        for i, o in enumerate(outs):
+            out[k + 'out%d' % i] = o.detach().numpy()
+        for i, h in enumerate(ref.heatmaps_array):
+            segments(k + 'hm%d' % i, [('hm', h)], out)
+        loss = ref.forward_loss(outs, target, mask)
+        out[k + 'loss'] = np.float64(loss.item())
+        loss.backward()
+        segments(k + 'grad', [(n, p.grad) for n, p in ref.named_parameters()], out, samples=1024)
+        segments(k + 'buf', list(ref.named_buffers()), out)
+        out[k + 'coords'] = ref.compute_coords(outs).numpy()
+        segments(k + 'heatmaps', [('hm', ref.heatmaps)], out)
+    # test_mask_none_and_tensor_part2
+    mine = omodel.build_mpii_pose_model(base='hg1', output_strat='dsnt', reg='js')
+    synthetic.fill_state_dict(mine, seed=0)
+    mine.to(torch.float64)
+    ref = ref_model.build_mpii_pose_model(base='hg1', output_strat='dsnt', reg='js').to(torch.float64)
+    ref.load_state_dict(mine.state_dict())
+    x, t, _ = synthetic.batch(2, size=128, seed=2, dtype=torch.float64)
+    hm = synthetic.tensor('part2.hm', (1, 16, 8, 8), seed=2, dtype=torch.float64)
+    out['part2.loss'] = np.float64(ref.forward_loss(ref(x), t, None).item())
+    a = ref.forward_part2(hm)
+    out['part2.len'] = np.int64(len(a))
+    out['part2.out0'] = a[0].detach().numpy()
+    # test_builder_quirks
+    r = ref_model.build_mpii_pose_model(base='hg', dilate=2, truncate=1)
+    out['quirks.output_strat'] = np.array(r.output_strat)
+    out['quirks.num_stacks'] = np.int64(r.hg.num_stacks)
+    out['quirks.image_size'] = np.int64(r.image_specs.size)
+    out['quirks.heatmap_size'] = np.int64(r.heatmap_size)
+    for bad in ('vgg', 'hgx'):
+        try:
+            ref_model.build_mpii_pose_model(base=bad)
+            msg = ''
+        except Exception as e:  # noqa: BLE001  (the reference raises a bare Exception)
+            msg = str(e)
+        out['quirks.error_' + bad] = np.array(msg)
+    # test_resnet_wrapper_matches_reference_wrapper
+    for dilate, truncate in [(0, 1), (2, 0), (0, 0), (1, 1)]:
+        k = 'resnet.d%d_t%d.' % (dilate, truncate)
+        torch.manual_seed(0)
+        base = oresnet.resnet18().double()
+        mine = omodel.ResNetHumanPoseModel(copy.deepcopy(base), n_chans=16, dilate=dilate, truncate=truncate, reg='js')
+        synthetic.fill_state_dict(mine, seed=0)
+        mine.double()
+        ref = ref_model.ResNetHumanPoseModel(copy.deepcopy(base), n_chans=16, dilate=dilate, truncate=truncate, reg='js')
+        ref.load_state_dict(mine.state_dict())
+        ref.double()
+        x = synthetic.tensor('resnet.x', (2, 3, 224, 224), seed=4, dtype=torch.float64)
+        t = synthetic.tensor('resnet.t', (2, 16, 2), seed=4, dtype=torch.float64, kind='uniform')
+        a = ref(x)
+        out[k + 'out'] = a.detach().numpy()
+        out[k + 'hm_shape'] = np.array(ref.heatmaps.shape, dtype=np.int64)
+        la = ref.forward_loss(a, t, None)
+        out[k + 'loss'] = np.float64(la.item())
+        la.backward()
+        segments(k + 'grad', [(n, p.grad) for n, p in ref.named_parameters()], out, samples=1024)
+    # test_preact_variants
+    x = synthetic.tensor('preact.x', (3, 16, 8, 8), seed=6, dtype=torch.float64)
+    for preact in ('softmax', 'thresholded_softmax', 'abs', 'relu', 'sigmoid'):
+        out['preact.' + preact] = ref_model.HumanPoseModel()._hm_preact(x, preact).numpy()
+    # test_nn_functions_random
+    for dtype in (torch.float64, torch.float32):
+        k = 'nnf.%s.' % str(dtype).split('.')[-1]
+        hm = torch.softmax(synthetic.tensor(k + 'hm', (4, 16, 64 * 64), seed=3).to(dtype) * 3, -1)
+        hm = hm.view(4, 16, 64, 64).requires_grad_()
+        mu = synthetic.tensor(k + 'mu', (4, 16, 2), seed=3, kind='uniform').to(dtype)
+        mask = (synthetic.tensor(k + 'mask', (4, 16), seed=3, kind='uniform') < 0.4).to(dtype)
+        for name in ('kl_reg_loss', 'js_reg_loss', 'mse_reg_loss', 'variance_reg_loss'):
+            a = getattr(ref_nn, name)(hm, mu, 1 / 32, mask)
+            out[k + name] = np.float64(a.item())
+            ga, = torch.autograd.grad(a, hm)
+            segments(k + name + '.grad', [('grad', ga)], out)
+        out[k + 'dsnt'] = ref_nn.dsnt(hm).detach().numpy()
+        segments(k + 'make_gauss', [('g', ref_nn.make_gauss(mu, 64, 64, 1 / 32))], out)
+        segments(k + 'softmax_2d', [('s', ref_nn.softmax_2d(hm))], out)
+        segments(k + 'thresholded_softmax', [('s', ref_nn.thresholded_softmax(hm.flatten(-2), -0.5))], out)
+    # test_inference_flip_restatement_matches_reference_pieces
+    from dsnt_oracle import inference as oinf
+    out['flip.reverse'] = ref_util.reverse_tensor(torch.arange(24.).view(2, 3, 4), -1).numpy()
+    om = omodel.build_mpii_pose_model(base='hg1', output_strat='dsnt', reg='js')
+    synthetic.fill_state_dict(om, seed=0)
+    om.double()
+    rm = ref_model.build_mpii_pose_model(base='hg1', output_strat='dsnt', reg='js').double()
+    rm.load_state_dict(om.state_dict())
+    rm.eval()
+    x, _, _ = synthetic.batch(1, size=64, seed=3, mask_p=1.0, dtype=torch.float64)
+    tm, tb = torch.eye(2, dtype=torch.float64) * 50, torch.ones(1, 2, dtype=torch.float64)
+    with torch.no_grad():
+        both = torch.cat([x, ref_util.reverse_tensor(x, -1)], 0)
+        hm = rm.forward_part1(both)[-1]
+        hm1, hm2 = hm.split(1)
+        hm2 = ref_util.reverse_tensor(hm2, -1).index_select(-3, oinf.HFLIP_INDICES)
+        coords = rm.compute_coords(rm.forward_part2((hm1 + hm2) / 2))
+        out['flip.want'] = torch.baddbmm(tb[None], coords.double(), tm[None]).numpy()
+    # test_heatmap_util_matches_reference
+    hm = synthetic.tensor('hmu.hm', (3, 5, 16, 16), seed=3)
+    hm[0, 0].zero_()
+    hm[0, 1, 0, 7] = 9.0
+    hm[0, 2, 5, 5] = 9.0; hm[0, 2, 5, 4] = hm[0, 2, 5, 6] = 1.0
+    for nb in (True, False):
+        out['hmu.decode_nb%d' % nb] = ref_util.decode_heatmaps(hm.clone(), use_neighbours=nb).numpy()
+    out['hmu.get_preds'] = ref_util.get_preds(hm.clone()).numpy()
+    draws = []
+    for (x, y, sigma, norm, clip) in HMU_DRAWS:
+        a = torch.zeros(16, 16)
+        ref_util.draw_gaussian(a, x, y, sigma, normalize=norm, clip_size=clip)
+        draws.append(a.numpy())
+    out['hmu.draws'] = np.stack(draws)
+    coords = synthetic.tensor('hmu.coords', (4, 6, 2), seed=3, scale=1.2, kind='uniform')
+    px = coords.clone().add_(1); px[:, :, 0].mul_(16 / 2); px[:, :, 1].mul_(16 / 2); px.add_(-0.5)
+    want = torch.zeros(4, 6, 16, 16)
+    for i in range(4):
+        for j in range(6):
+            ref_util.draw_gaussian(want[i, j], round(px[i, j, 0].item()), round(px[i, j, 1].item()), 1.25,
+                                   normalize=False, clip_size=7)
+    out['hmu.encode'] = want.numpy()
+    # test_gauss_strategy_model_matches_reference_pieces
+    m = omodel.build_mpii_pose_model(base='hg2')
+    synthetic.fill_state_dict(m, seed=0)
+    m.train()
+    x, _, _ = synthetic.batch(2, size=64, seed=5)
+    outs = m(x)
+    out['gauss.decode'] = ref_util.decode_heatmaps(outs[-1].detach().clone()).numpy()
+    np.savez_compressed(os.path.join(HERE, 'oracle_vs_reference.npz'), **out)
+
+
+# (x, y, sigma, normalize, clip_size) of the draw_gaussian cases in test_heatmap_util_matches_reference
+HMU_DRAWS = [(4, 4, 1, False, None), (0, 4, 1, False, 7), (-3, 2, 1.5, False, 7), (-4, 2, 1, False, 7),
+             (18, 3, 1, False, 7), (19, 3, 1, False, 7), (7, 15, 2, True, 7), (3.7, 2.2, 1, True, None)]
+
+
 def main():
     ref = refimport.load_reference()
     assert ref is not None, 'run in the build container: /root/reference is required'
     ref_nn, ref_hg, ref_model = ref
     torch.set_num_threads(8)
+    if sys.argv[1:] == ['oracle_vs_reference']:
+        oracle_vs_reference(ref_nn, ref_hg, ref_model)
+        print('oracle_vs_reference.npz', os.path.getsize(os.path.join(HERE, 'oracle_vs_reference.npz')))
+        return
     if len(sys.argv) > 1:                   # one end-to-end family only, e.g. `make_golden.py hg8_128 hg8 128 js`
         tag, base, size, reg = sys.argv[1:5]
         end_to_end(ref_model, base, int(size), reg, tag)
@@ -192,6 +369,7 @@ def main():
     end_to_end(ref_model, 'hg2', 256, 'js', 'hg2_256')
     end_to_end(ref_model, 'hg8', 128, 'js', 'hg8_128')
     pckh()
+    oracle_vs_reference(ref_nn, ref_hg, ref_model)
     for f in sorted(os.listdir(HERE)):
         if f.endswith('.npz'):
             print(f, os.path.getsize(os.path.join(HERE, f)))
