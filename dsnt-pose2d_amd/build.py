@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libdsnt_hip.so')
-SOURCES = ['api.cpp', 'conv.hip', 'wgrad3.hip', 'wgrad1.hip', 'gemm1.hip', 'bwd1.hip', 'fwd1.hip', 'stem4.hip', 'conv3s.hip', 'dgrad_up.hip', 'elementwise.hip', 'head.hip', 'heatmap.hip', 'debug.hip']
+SOURCES = ['api.cpp', 'conv.hip', 'wgrad3.hip', 'wgrad1.hip', 'gemm1.hip', 'bwd1.hip', 'fwd1.hip', 'stem4.hip', 'conv3s.hip', 'dgrad_up.hip', 'elementwise.hip', 'head.hip', 'heatmap.hip', 'augment.hip', 'debug.hip']
 FLAGS = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wno-unused-value',
          '-Wno-unused-result']
 if os.environ.get('DSNT_TIMELINE'):      # wave timeline stamps in the conv kernels (diagnostic scripts of rounds 1-3, removed in round 6: git history)
@@ -48,7 +48,7 @@ def build(force=False, verbose=True):
             # CUs; the same source built without the vectoriser was bit-reproducible in 80 of 80 passes
             # (tools/determinism_fwd.py, DESIGN.md "round 2").
             extra = ['-fno-slp-vectorize'] if (src == 'conv.hip' or not os.environ.get('DSNT_SLP')) else []   # DSNT_SLP=1: A/B only
-            if src == 'heatmap.hip':      # the reference's separately rounded fp32 coordinate steps: no FMA contraction
+            if src in ('heatmap.hip', 'augment.hip'):   # separately rounded steps (the reference's fp32 coordinates; Pillow's and ATen's sampling and pooling): no FMA contraction
                 extra = extra + ['-ffp-contract=off']
             cmd = [hipcc] + FLAGS + extra + (['-x', 'hip'] if src.endswith('.cpp') else []) + ['-c', s, '-o', o]
             jobs.append(cmd)

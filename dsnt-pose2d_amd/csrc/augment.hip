@@ -1,0 +1,286 @@
+// The MPII training-sample transform on the device (reference src/dsnt/data.py:118-226), one launch per batch.
+//
+// dsnt_augment_fwd: src uint8 [B][R][R][3] (the crops MpiiData.load_cropped_image(id, size=R, margin=R/4) returns) ->
+// input f32 [B][3][S][S], composed in the reference's order:
+//   1. hflip: Image.transpose(FLIP_LEFT_RIGHT), i.e. flipped[y][x] = src[y][R-1-x].
+//   2. rot != 0: Image.rotate(rot, BILINEAR), expand=False.  Pillow takes rot % 360 (Python's modulo), builds the
+//      inverse map [a b c; d e f] from cos/sin of -radians(rot % 360) rounded to 15 decimals, centred on (R/2, R/2)
+//      (c = a*(-R/2) + b*(-R/2) + R/2, f likewise), and for output pixel (x, y) samples xin = a*(x+.5) + b*(y+.5) + c,
+//      yin = d*(x+.5) + e*(y+.5) + f in fp64.  Outside [0, R) x [0, R): black.  Inside: taps at floor(xin - .5),
+//      floor(yin - .5) and +1, clamped to the image, lerped in fp64 along x then y (a + (b - a) * t), and the value
+//      TRUNCATED to uint8 (the rotated image is a PIL uint8 image).  Verified bit-exact against Pillow 12.2.
+//   3. torchvision 0.2.0 CenterCrop(R * scale): the size is int()-truncated, c = int(R * scale); center_crop takes
+//      i = j = int(round((R - c) / 2.)) (Python 3 round: half to even) and Image.crop((j, i, j + c, i + c)), which
+//      zero-fills where the box leaves the image (scale > 1).  So crop pixel (u, v) is rotated pixel (u + off, v + off).
+//   4. ToTensor (q / 255 in fp32), x * gain[ch] (fp32), clamp(0, 1).
+//   5. adaptive_avg_pool2d c x c -> S x S: window [floor(i*c/S), ceil((i+1)*c/S)), summed row-major in fp32, then
+//      / kh / kw (ATen's CPU order).
+//   6. Normalize: (x - mean[ch]) / std[ch] in fp32.
+// One thread per output pixel: it walks its pool window in crop coordinates and maps each crop pixel back through the
+// offset, the inverse rotation and the flip to one (bilinear) sample of src, which is read directly (a 442 KB source is
+// L2-resident).  The three channel planes are written as coalesced stores.  No atomics, no inter-workgroup traffic:
+// the output is bit-reproducible.  Built with -ffp-contract=off (build.py) so the fp64 sampling and the fp32 pooling
+// round like Pillow's and ATen's separately rounded operations.
+//
+// draw != 0: the parameters are drawn on the device first, Philox4x32-10 keyed by (seed) with counter (sample, step, k),
+// so no generator state is carried between calls, and written to scale/rot/hflip/gain (workgroup 0 of each sample
+// writes; every workgroup computes the same draw).  Distributions (data.py:134-140): scale = 2^clip(N(0, .25), -.5, .5);
+// rot = clip(N(0, 30), -60, 60) with probability 0.4, else 0; hflip ~ Bernoulli(.5); gain[ch] ~ U(.6, 1.4).
+//
+// dsnt_augment_keypoints (data.py:150-196, fp64): part_coords = t . matrix . [x, y, 1] with t = R(rot)/scale . F(hflip),
+// joints permuted by the flip table under hflip (out[flip[j]] = in[j], as scatter_ does), part_mask permuted the same way
+// and, in train mode, multiplied by |coord| < 1; trans_m / trans_b = the 2x2 / translation part of inv(matrix) . inv(t).
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int AUG_NT = 256;
+
+struct Philox {
+    __device__ static void round(uint32_t ctr[4], const uint32_t key[2]) {
+        const uint32_t lo0 = 0xD2511F53u * ctr[0], hi0 = __umulhi(0xD2511F53u, ctr[0]);
+        const uint32_t lo1 = 0xCD9E8D57u * ctr[2], hi1 = __umulhi(0xCD9E8D57u, ctr[2]);
+        const uint32_t c0 = hi1 ^ ctr[1] ^ key[0], c2 = hi0 ^ ctr[3] ^ key[1];
+        ctr[0] = c0; ctr[1] = lo1; ctr[2] = c2; ctr[3] = lo0;
+    }
+    // Philox4x32-10
+    __device__ static void gen(uint32_t out[4], uint64_t seed, uint64_t step, uint32_t sample, uint32_t k) {
+        uint32_t ctr[4] = {sample, (uint32_t)step, (uint32_t)(step >> 32), k};
+        uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+        for (int r = 0; r < 10; ++r) {
+            round(ctr, key);
+            key[0] += 0x9E3779B9u;
+            key[1] += 0xBB67AE85u;
+        }
+        for (int i = 0; i < 4; ++i) out[i] = ctr[i];
+    }
+};
+
+// (0, 1]: 24 random bits
+__device__ inline double unit(uint32_t x) { return (double)((x >> 8) + 1u) * (1.0 / 16777216.0); }
+__device__ inline double normal(uint32_t a, uint32_t b) {      // Box-Muller
+    return sqrt(-2.0 * log(unit(a))) * cos(6.283185307179586 * unit(b));
+}
+__device__ inline double clip(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
+
+__device__ void draw_params(uint64_t seed, uint64_t step, int b, float& scale, float& rot, uint8_t& hflip, float gain[3]) {
+    uint32_t r0[4], r1[4], r2[4];
+    Philox::gen(r0, seed, step, (uint32_t)b, 0);
+    Philox::gen(r1, seed, step, (uint32_t)b, 1);
+    Philox::gen(r2, seed, step, (uint32_t)b, 2);
+    scale = (float)exp2(clip(0.25 * normal(r0[0], r0[1]), -0.5, 0.5));
+    rot = unit(r0[2]) <= 0.4 ? (float)clip(30.0 * normal(r1[0], r1[1]), -60.0, 60.0) : 0.f;
+    hflip = unit(r0[3]) <= 0.5 ? 1 : 0;
+    for (int ch = 0; ch < 3; ++ch) gain[ch] = (float)(0.6 + 0.8 * unit(r2[ch]));
+}
+
+// Pillow's rounding of the rotation coefficients: round(x, 15)
+__device__ inline double round15(double x) { return rint(x * 1e15) / 1e15; }
+
+struct SampleCoef {
+    double a, b, c, d, e, f;   // inverse rotation (Pillow's affine data)
+    float gain[3], mean[3], std[3];
+    int c_side, off, rotate, hflip;
+};
+
+__global__ void __launch_bounds__(AUG_NT) augment_kernel(const uint8_t* __restrict__ src, int R, int S,
+                                                         float* __restrict__ scale_p, float* __restrict__ rot_p,
+                                                         uint8_t* __restrict__ hflip_p, float* __restrict__ gain_p,
+                                                         int draw, uint64_t seed, uint64_t step,
+                                                         const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                         float* __restrict__ out) {
+    __shared__ SampleCoef sc;
+    const int b = blockIdx.y;
+    if (threadIdx.x == 0) {
+        float scale, rot, gain[3];
+        uint8_t hflip;
+        if (draw) {
+            draw_params(seed, step, b, scale, rot, hflip, gain);
+            if (blockIdx.x == 0) {
+                scale_p[b] = scale; rot_p[b] = rot; hflip_p[b] = hflip;
+                for (int ch = 0; ch < 3; ++ch) gain_p[3 * b + ch] = gain[ch];
+            }
+        } else {
+            scale = scale_p[b]; rot = rot_p[b]; hflip = hflip_p[b];
+            for (int ch = 0; ch < 3; ++ch) gain[ch] = gain_p[3 * b + ch];
+        }
+        const double cd = (double)R * (double)scale;
+        const int c = cd >= 1.0 && cd <= 8.0 * R ? (int)cd : (cd > 1.0 ? 8 * R : 1);    // (the binding refuses these)
+        sc.c_side = c;
+        sc.off = (int)rint((double)(R - c) / 2.0);
+        sc.hflip = hflip != 0;
+        double deg = fmod((double)rot, 360.0);
+        if (deg < 0) deg += 360.0;                    // Python's float modulo
+        sc.rotate = deg != 0.0;
+        const double ang = -(deg * (M_PI / 180.0));
+        const double ca = round15(cos(ang)), sa = round15(sin(ang));
+        const double cx = R / 2.0, cy = R / 2.0;
+        sc.a = ca; sc.b = sa; sc.d = -sa; sc.e = ca;
+        sc.c = ca * -cx + sa * -cy + 0.0 + cx;
+        sc.f = -sa * -cx + ca * -cy + 0.0 + cy;
+        for (int ch = 0; ch < 3; ++ch) {
+            sc.gain[ch] = gain[ch];
+            sc.mean[ch] = mean[ch];
+            sc.std[ch] = stdv[ch];
+        }
+    }
+    __syncthreads();
+    const int p = blockIdx.x * AUG_NT + threadIdx.x;
+    if (p >= S * S) return;
+    const int oy = p / S, ox = p - oy * S;
+    const int c = sc.c_side, off = sc.off, flip = sc.hflip, rotate = sc.rotate;
+    const int y0 = (int)(((long)oy * c) / S), y1 = (int)(((long)(oy + 1) * c + S - 1) / S);
+    const int x0 = (int)(((long)ox * c) / S), x1 = (int)(((long)(ox + 1) * c + S - 1) / S);
+    const uint8_t* img = src + (size_t)b * R * R * 3;
+    const float g0 = sc.gain[0], g1 = sc.gain[1], g2 = sc.gain[2];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int v = y0; v < y1; ++v) {
+        const int Y = v + off;
+        for (int u = x0; u < x1; ++u) {
+            const int X = u + off;
+            int q0 = 0, q1 = 0, q2 = 0;
+            if (X >= 0 && X < R && Y >= 0 && Y < R) {
+                if (!rotate) {
+                    const uint8_t* px = img + ((size_t)Y * R + (flip ? R - 1 - X : X)) * 3;
+                    q0 = px[0]; q1 = px[1]; q2 = px[2];
+                } else {
+                    const double xo = X + 0.5, yo = Y + 0.5;
+                    double xin = sc.a * xo + sc.b * yo + sc.c;
+                    double yin = sc.d * xo + sc.e * yo + sc.f;
+                    if (xin >= 0.0 && xin < R && yin >= 0.0 && yin < R) {
+                        xin -= 0.5;
+                        yin -= 0.5;
+                        const double fx = floor(xin), fy = floor(yin);
+                        const double dx = xin - fx, dy = yin - fy;
+                        const int xi = (int)fx, yi = (int)fy;
+                        int xa = min(max(xi, 0), R - 1), xb = min(max(xi + 1, 0), R - 1);
+                        if (flip) { xa = R - 1 - xa; xb = R - 1 - xb; }        // taps of the flipped image
+                        const int ya = min(max(yi, 0), R - 1);
+                        const bool has2 = yi + 1 >= 0 && yi + 1 < R;           // Pillow: else v2 = v1
+                        const uint8_t* ra = img + (size_t)ya * R * 3;
+                        const uint8_t* rb = has2 ? img + (size_t)(yi + 1) * R * 3 : ra;
+                        int q[3];
+                        for (int ch = 0; ch < 3; ++ch) {
+                            const double a0 = ra[xa * 3 + ch], a1 = ra[xb * 3 + ch];
+                            const double v1 = a0 + (a1 - a0) * dx;
+                            const double b0 = rb[xa * 3 + ch], b1 = rb[xb * 3 + ch];
+                            const double v2 = has2 ? b0 + (b1 - b0) * dx : v1;
+                            q[ch] = (int)(v1 + (v2 - v1) * dy);
+                        }
+                        q0 = q[0]; q1 = q[1]; q2 = q[2];
+                    }
+                }
+            }
+            s0 += fminf(fmaxf(((float)q0 / 255.f) * g0, 0.f), 1.f);
+            s1 += fminf(fmaxf(((float)q1 / 255.f) * g1, 0.f), 1.f);
+            s2 += fminf(fmaxf(((float)q2 / 255.f) * g2, 0.f), 1.f);
+        }
+    }
+    const float kh = (float)(y1 - y0), kw = (float)(x1 - x0);
+    float* o = out + (size_t)b * 3 * S * S + p;
+    o[0] = (s0 / kh / kw - sc.mean[0]) / sc.std[0];
+    o[(size_t)S * S] = (s1 / kh / kw - sc.mean[1]) / sc.std[1];
+    o[(size_t)2 * S * S] = (s2 / kh / kw - sc.mean[2]) / sc.std[2];
+}
+
+__global__ void augment_keypoints_kernel(const double* __restrict__ matrix, const double* __restrict__ kp,
+                                         const float* __restrict__ kmask, const float* __restrict__ scale_p,
+                                         const float* __restrict__ rot_p, const uint8_t* __restrict__ hflip_p,
+                                         const int64_t* __restrict__ flip_idx, int train, int B, int J,
+                                         float* __restrict__ part_coords, float* __restrict__ part_mask,
+                                         double* __restrict__ trans_m, double* __restrict__ trans_b) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * J) return;
+    const int b = i / J, j = i - b * J;
+    const double* m = matrix + 9 * b;
+    const double s = scale_p[b], rad = (double)rot_p[b] * (M_PI / 180.0);
+    const double cs = cos(rad), sn = sin(rad);
+    const bool flip = hflip_p[b] != 0;
+    // t = [[cos/s, sin/s, 0], [-sin/s, cos/s, 0], [0, 0, 1]] . diag(flip ? -1 : 1, 1, 1)
+    const double fx = flip ? -1.0 : 1.0;
+    const double t00 = cs / s * fx, t01 = sn / s, t10 = -sn / s * fx, t11 = cs / s;
+    const double x = kp[2 * i], y = kp[2 * i + 1];
+    const double px = m[0] * x + m[1] * y + m[2], py = m[3] * x + m[4] * y + m[5];
+    const double qx = t00 * px + t01 * py, qy = t10 * px + t11 * py;
+    int jo = flip ? (int)flip_idx[j] : j;
+    if (jo < 0 || jo >= J) jo = j;                   // (the binding passes a permutation of 0..J-1; never write outside the row)
+    part_coords[2 * (b * J + jo)] = (float)qx;
+    part_coords[2 * (b * J + jo) + 1] = (float)qy;
+    float mk = kmask[i];
+    if (train && !(fabs(qx) < 1.0 && fabs(qy) < 1.0)) mk *= 0.f;
+    part_mask[b * J + jo] = mk;
+    if (j == 0) {
+        // inv(matrix) by the adjugate
+        const double a00 = m[4] * m[8] - m[5] * m[7], a01 = m[2] * m[7] - m[1] * m[8], a02 = m[1] * m[5] - m[2] * m[4];
+        const double a10 = m[5] * m[6] - m[3] * m[8], a11 = m[0] * m[8] - m[2] * m[6], a12 = m[2] * m[3] - m[0] * m[5];
+        const double a20 = m[3] * m[7] - m[4] * m[6], a21 = m[1] * m[6] - m[0] * m[7], a22 = m[0] * m[4] - m[1] * m[3];
+        const double det = m[0] * a00 + m[1] * a10 + m[2] * a20;
+        const double inv[9] = {a00 / det, a01 / det, a02 / det, a10 / det, a11 / det, a12 / det,
+                               a20 / det, a21 / det, a22 / det};
+        // inv(t) = diag(fx, 1, 1) . s * R^T = [[fx s cos, -fx s sin, 0], [s sin, s cos, 0], [0, 0, 1]]
+        const double u00 = fx * s * cs, u01 = -fx * s * sn, u10 = s * sn, u11 = s * cs;
+        trans_m[4 * b + 0] = inv[0] * u00 + inv[1] * u10;
+        trans_m[4 * b + 1] = inv[0] * u01 + inv[1] * u11;
+        trans_m[4 * b + 2] = inv[3] * u00 + inv[4] * u10;
+        trans_m[4 * b + 3] = inv[3] * u01 + inv[4] * u11;
+        trans_b[2 * b + 0] = inv[2];
+        trans_b[2 * b + 1] = inv[5];
+    }
+}
+
+// ImageSpecs.convert (data.py:38-56) on a float image: adaptive_avg_pool2d to S x S (ATen's windows and summation order, as
+// in augment_kernel) then (x - mean[ch]) / std[ch].  One thread per output element of [N][C][S][S].
+__global__ void __launch_bounds__(AUG_NT) pool_normalize_kernel(const float* __restrict__ x, int N, int C, int H, int W, int S,
+                                                                const float* __restrict__ mean,
+                                                                const float* __restrict__ stdv, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * AUG_NT + threadIdx.x;
+    if (i >= (long)N * C * S * S) return;
+    const int ox = (int)(i % S), oy = (int)((i / S) % S), ch = (int)((i / ((long)S * S)) % C);
+    const long plane = i / ((long)S * S);
+    const int y0 = (int)(((long)oy * H) / S), y1 = (int)(((long)(oy + 1) * H + S - 1) / S);
+    const int x0 = (int)(((long)ox * W) / S), x1 = (int)(((long)(ox + 1) * W + S - 1) / S);
+    const float* xp = x + plane * H * W;
+    float s = 0.f;
+    for (int v = y0; v < y1; ++v)
+        for (int u = x0; u < x1; ++u) s += xp[(long)v * W + u];
+    out[i] = (s / (float)(y1 - y0) / (float)(x1 - x0) - mean[ch]) / stdv[ch];
+}
+
+}  // namespace
+
+extern "C" int dsnt_augment_fwd(const uint8_t* src, int B, int R, int S, float* scale, float* rot_deg, uint8_t* hflip,
+                                float* gain, int draw, uint64_t seed, uint64_t step, const float* mean, const float* stdv,
+                                float* out, void* stream) {
+    DSNT_REQUIRE(src && scale && rot_deg && hflip && gain && mean && stdv && out, DSNT_ERR_ARG,
+                 "dsnt_augment_fwd: null pointer");
+    DSNT_REQUIRE(B > 0 && B <= 65535 && R > 0 && R <= 8192 && S > 0 && S <= 4096, DSNT_ERR_SHAPE,
+                 "dsnt_augment_fwd: bad shape B=%d R=%d S=%d", B, R, S);
+    DSNT_LAUNCH(augment_kernel, dim3((S * S + AUG_NT - 1) / AUG_NT, B), dim3(AUG_NT), 0, (hipStream_t)stream, src, R, S,
+                scale, rot_deg, hflip, gain, draw, seed, step, mean, stdv, out);
+    DSNT_CHECK_LAUNCH("dsnt_augment_fwd");
+}
+
+extern "C" int dsnt_augment_keypoints(const double* matrix, const double* keypoints, const float* keypoint_mask, int B,
+                                      int J, const float* scale, const float* rot_deg, const uint8_t* hflip,
+                                      const int64_t* flip_idx, int train, float* part_coords, float* part_mask,
+                                      double* trans_m, double* trans_b, void* stream) {
+    DSNT_REQUIRE(matrix && keypoints && keypoint_mask && scale && rot_deg && hflip && flip_idx && part_coords &&
+                 part_mask && trans_m && trans_b, DSNT_ERR_ARG, "dsnt_augment_keypoints: null pointer");
+    DSNT_REQUIRE(B > 0 && J > 0 && (long)B * J <= (1L << 30), DSNT_ERR_SHAPE, "dsnt_augment_keypoints: bad shape B=%d J=%d",
+                 B, J);
+    DSNT_LAUNCH(augment_keypoints_kernel, dim3((B * J + 255) / 256), dim3(256), 0, (hipStream_t)stream, matrix, keypoints,
+                keypoint_mask, scale, rot_deg, hflip, flip_idx, train, B, J, part_coords, part_mask, trans_m, trans_b);
+    DSNT_CHECK_LAUNCH("dsnt_augment_keypoints");
+}
+
+extern "C" int dsnt_pool_normalize(const float* x, int N, int C, int H, int W, int S, const float* mean, const float* stdv,
+                                   float* out, void* stream) {
+    DSNT_REQUIRE(x && mean && stdv && out, DSNT_ERR_ARG, "dsnt_pool_normalize: null pointer");
+    DSNT_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && S > 0 && S <= 4096 && (long)N * C * S * S <= (1L << 31) - AUG_NT &&
+                 (long)N * C * H * W <= (1L << 40), DSNT_ERR_SHAPE, "dsnt_pool_normalize: bad shape");
+    const long total = (long)N * C * S * S;
+    DSNT_LAUNCH(pool_normalize_kernel, dim3((unsigned)((total + AUG_NT - 1) / AUG_NT)), dim3(AUG_NT), 0, (hipStream_t)stream,
+                x, N, C, H, W, S, mean, stdv, out);
+    DSNT_CHECK_LAUNCH("dsnt_pool_normalize");
+}

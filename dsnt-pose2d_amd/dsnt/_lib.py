@@ -158,6 +158,9 @@ SIGNATURES = {
     'dsnt_sgd_step_guarded': [P, P, P, L, F, F, F, F, I, P, P],
     'dsnt_nonfinite_flag': [P, L, P, I, P],
     'dsnt_pckh': [P, P, P, P, P, P, F, P, P, I, I, P],
+    'dsnt_augment_fwd': [P, I, I, I, P, P, P, P, I, C.c_uint64, C.c_uint64, P, P, P, P],
+    'dsnt_augment_keypoints': [P, P, P, I, I, P, P, P, P, I, P, P, P, P, P],
+    'dsnt_pool_normalize': [P, I, I, I, I, I, P, P, P, P],
     'dsnt_debug_mfma_peak': [P, I, I, I, I, P],
     'dsnt_debug_coexec': [P, I, I, I, P],
     'dsnt_debug_bf16_peak': [P, I, I, I, I, P],

@@ -699,6 +699,28 @@ int dsnt_pckh(const float* pred, const float* target, const double* m, const dou
               const float* mask, const double* head, float threshold, float* hits,
               float* valid, int B, int J, void* stream);
 
+/* ------------------------------------------------------------------ training augmentation
+ * data.py:118-226 (MPIIDataset.__getitem__, use_aug) batched on the device; semantics in csrc/augment.hip.
+ * dsnt_augment_fwd: src uint8 [B][R][R][3] (HWC crops) -> out f32 [B][3][S][S] = normalize(adaptive_avg_pool(clamp(gain *
+ * center_crop(rotate(flip(src)), int(R*scale)) / 255))).  Per-sample parameters scale [B], rot_deg [B], hflip [B] (0/1),
+ * gain [B][3]; mean, stdv [3] (device).  draw != 0: the parameters are first drawn on the device from Philox(seed; sample,
+ * step) with the reference's distributions (data.py:134-140, 205-210) and written to those four buffers; draw == 0: they are
+ * read.  R <= 8192, S <= 4096, B <= 65535.  Bit-reproducible (no atomics).  dsnt_version() >= 115 (all three entry points). */
+int dsnt_augment_fwd(const uint8_t* src, int B, int R, int S, float* scale, float* rot_deg, uint8_t* hflip,
+                     float* gain, int draw, uint64_t seed, uint64_t step, const float* mean, const float* stdv,
+                     float* out, void* stream);
+/* data.py:150-196 in fp64: matrix [B][3][3] (bb transform), keypoints [B][J][2] (original-image pixels), keypoint_mask
+ * [B][J]; the parameters of dsnt_augment_fwd; flip_idx [J] (a permutation: inference.HFLIP_INDICES); train != 0: mask joints
+ * with |coord| >= 1.  Out: part_coords f32 [B][J][2], part_mask f32 [B][J], trans_m f64 [B][2][2], trans_b f64 [B][1][2]. */
+int dsnt_augment_keypoints(const double* matrix, const double* keypoints, const float* keypoint_mask, int B, int J,
+                           const float* scale, const float* rot_deg, const uint8_t* hflip, const int64_t* flip_idx,
+                           int train, float* part_coords, float* part_mask, double* trans_m, double* trans_b,
+                           void* stream);
+/* data.py:38-56 (ImageSpecs.convert) on a float image: x f32 [N][C][H][W] -> out f32 [N][C][S][S] =
+ * (adaptive_avg_pool2d(x, S) - mean[c]) / stdv[c]; mean, stdv [C] (device). */
+int dsnt_pool_normalize(const float* x, int N, int C, int H, int W, int S, const float* mean, const float* stdv,
+                        float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
