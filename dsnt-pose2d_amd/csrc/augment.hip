@@ -84,6 +84,9 @@ struct SampleCoef {
     int c_side, off, rotate, hflip;
 };
 
+// PAIR (dsnt_augment_fwd_pair): `out` is [2B][3][S][S] and every finished pixel is also stored at column S-1-x of sample
+// B + b: the second half is exactly the first one mirrored (inference.py's reverse_tensor(input, -1)).
+template <bool PAIR>
 __global__ void __launch_bounds__(AUG_NT) augment_kernel(const uint8_t* __restrict__ src, int R, int S,
                                                          float* __restrict__ scale_p, float* __restrict__ rot_p,
                                                          uint8_t* __restrict__ hflip_p, float* __restrict__ gain_p,
@@ -182,6 +185,12 @@ __global__ void __launch_bounds__(AUG_NT) augment_kernel(const uint8_t* __restri
     o[0] = (s0 / kh / kw - sc.mean[0]) / sc.std[0];
     o[(size_t)S * S] = (s1 / kh / kw - sc.mean[1]) / sc.std[1];
     o[(size_t)2 * S * S] = (s2 / kh / kw - sc.mean[2]) / sc.std[2];
+    if (PAIR) {
+        float* om = out + ((size_t)gridDim.y + b) * 3 * S * S + (size_t)oy * S + (S - 1 - ox);
+        om[0] = o[0];
+        om[(size_t)S * S] = o[(size_t)S * S];
+        om[(size_t)2 * S * S] = o[(size_t)2 * S * S];
+    }
 }
 
 __global__ void augment_keypoints_kernel(const double* __restrict__ matrix, const double* __restrict__ kp,
@@ -256,9 +265,21 @@ extern "C" int dsnt_augment_fwd(const uint8_t* src, int B, int R, int S, float* 
                  "dsnt_augment_fwd: null pointer");
     DSNT_REQUIRE(B > 0 && B <= 65535 && R > 0 && R <= 8192 && S > 0 && S <= 4096, DSNT_ERR_SHAPE,
                  "dsnt_augment_fwd: bad shape B=%d R=%d S=%d", B, R, S);
-    DSNT_LAUNCH(augment_kernel, dim3((S * S + AUG_NT - 1) / AUG_NT, B), dim3(AUG_NT), 0, (hipStream_t)stream, src, R, S,
-                scale, rot_deg, hflip, gain, draw, seed, step, mean, stdv, out);
+    DSNT_LAUNCH(augment_kernel<false>, dim3((S * S + AUG_NT - 1) / AUG_NT, B), dim3(AUG_NT), 0, (hipStream_t)stream, src,
+                R, S, scale, rot_deg, hflip, gain, draw, seed, step, mean, stdv, out);
     DSNT_CHECK_LAUNCH("dsnt_augment_fwd");
+}
+
+extern "C" int dsnt_augment_fwd_pair(const uint8_t* src, int B, int R, int S, float* scale, float* rot_deg,
+                                     uint8_t* hflip, float* gain, int draw, uint64_t seed, uint64_t step,
+                                     const float* mean, const float* stdv, float* out, void* stream) {
+    DSNT_REQUIRE(src && scale && rot_deg && hflip && gain && mean && stdv && out, DSNT_ERR_ARG,
+                 "dsnt_augment_fwd_pair: null pointer");
+    DSNT_REQUIRE(B > 0 && B <= 65535 && R > 0 && R <= 8192 && S > 0 && S <= 4096, DSNT_ERR_SHAPE,
+                 "dsnt_augment_fwd_pair: bad shape B=%d R=%d S=%d", B, R, S);
+    DSNT_LAUNCH(augment_kernel<true>, dim3((S * S + AUG_NT - 1) / AUG_NT, B), dim3(AUG_NT), 0, (hipStream_t)stream, src,
+                R, S, scale, rot_deg, hflip, gain, draw, seed, step, mean, stdv, out);
+    DSNT_CHECK_LAUNCH("dsnt_augment_fwd_pair");
 }
 
 extern "C" int dsnt_augment_keypoints(const double* matrix, const double* keypoints, const float* keypoint_mask, int B,

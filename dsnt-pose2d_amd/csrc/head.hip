@@ -7,16 +7,19 @@
 // coordinate moments and the divergence sums.  Longer rows fall back to re-reading the row
 // (served by L2).  Meshgrids are never materialised: x_w = (2w - (W-1))/W, y_h = (2h - (H-1))/H.
 #include "common.h"
+#include "flipmerge.h"
 #include <math.h>
 
 #define HB 256   // threads per row
 
-template <int VEC, bool CACHED>
+// A row of H*W values read from `SRC`: a plain `const float*` (every kernel but one), or the flip-merged logits of
+// dsnt_flip_merge_head (FlipSrc, flipmerge.h), which are formed as they are read.
+template <int VEC, bool CACHED, typename SRC = const float*>
 struct Row {
     float v[16];
-    const float* src;
+    SRC src;
     int hw;
-    __device__ __forceinline__ void load(const float* row, int n) {
+    __device__ __forceinline__ void load(SRC row, int n) {
         src = row; hw = n;
         if (CACHED) {
             const int tid = threadIdx.x;
@@ -25,7 +28,7 @@ struct Row {
                 for (int k = 0; k < 4; ++k) {
                     const int i = (k * HB + tid) * 4;
                     float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (i < hw) t = *reinterpret_cast<const float4*>(row + i);
+                    if (i < hw) t = row_load4(row, i);
                     v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w;
                 }
             } else {
@@ -109,14 +112,9 @@ struct Grid2 {
 };
 
 // ------------------------------------------------------------------ preact (model.py:24-45)
-template <int VEC, bool CACHED>
-__global__ __launch_bounds__(HB) void preact_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                         int hw, int mode, float thr, float eps) {
-    __shared__ float red[16];
-    const size_t off = (size_t)blockIdx.x * hw;
-    Row<VEC, CACHED> row;
-    row.load(x + off, hw);
-    float* out = y + off;
+// the normalised row: sink(i, y_i) for every element this thread owns, in Row::each order
+template <typename ROW, typename SINK>
+__device__ __forceinline__ void preact_row(const ROW& row, int mode, float thr, float eps, float* red, SINK sink) {
     if (mode <= 1) {
         float m = -INFINITY;
         row.each([&](int, float v) { m = fmaxf(m, v); });
@@ -130,7 +128,7 @@ __global__ __launch_bounds__(HB) void preact_fwd_kernel(const float* __restrict_
         const float denom = mode == 1 ? s[0] + eps : s[0];
         row.each([&](int i, float v) {
             const float e = (mode == 1 && !(v >= thr)) ? 0.f : expf(v - m);
-            out[i] = e / denom;
+            sink(i, e / denom);
         });
     } else {
         auto f = [&](float v) {
@@ -140,8 +138,19 @@ __global__ __launch_bounds__(HB) void preact_fwd_kernel(const float* __restrict_
         row.each([&](int, float v) { s[0] += f(v); });
         block_sum<1>(s, red);
         const float denom = s[0] + eps;
-        row.each([&](int i, float v) { out[i] = f(v) / denom; });
+        row.each([&](int i, float v) { sink(i, f(v) / denom); });
     }
+}
+
+template <int VEC, bool CACHED>
+__global__ __launch_bounds__(HB) void preact_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                         int hw, int mode, float thr, float eps) {
+    __shared__ float red[16];
+    const size_t off = (size_t)blockIdx.x * hw;
+    Row<VEC, CACHED> row;
+    row.load(x + off, hw);
+    float* out = y + off;
+    preact_row(row, mode, thr, eps, red, [&](int i, float p) { out[i] = p; });
 }
 
 template <int VEC, bool CACHED>
@@ -466,14 +475,11 @@ __global__ void masked_avg_bwd_kernel(const float* __restrict__ g, const float* 
 
 // ------------------------------------------------------------------ fused head
 // forward: softmax over the row + coordinate moments, one HBM read of the logits.
-template <int VEC, bool CACHED>
-__global__ __launch_bounds__(HB) void head_fwd_kernel(const float* __restrict__ logits, float* __restrict__ hm,
-                                                       float* __restrict__ coords, int h, int w) {
-    __shared__ float red[16];
+// the row's softmax, stored to `out` when STORE, and its coordinate moments c (block-reduced: every thread has them)
+template <int VEC, bool CACHED, bool STORE, typename SRC>
+__device__ __forceinline__ void head_fwd_row(Row<VEC, CACHED, SRC>& row, float* __restrict__ out, int h, int w,
+                                             float* red, float (&c)[2]) {
     const int hw = h * w;
-    const size_t off = (size_t)blockIdx.x * hw;
-    Row<VEC, CACHED> row;
-    row.load(logits + off, hw);
     float m = -INFINITY;
     row.each([&](int, float v) { m = fmaxf(m, v); });
     m = block_max(m, red);
@@ -489,8 +495,7 @@ __global__ __launch_bounds__(HB) void head_fwd_kernel(const float* __restrict__ 
     block_sum<1>(s, red);
     const float denom = s[0];
     const Grid2 g(h, w);
-    float* out = hm + off;
-    float c[2] = {0.f, 0.f};
+    c[0] = 0.f; c[1] = 0.f;
     if (CACHED && VEC == 4 && (w & 3) == 0) {
         // four consecutive pixels of one heat-map row per 16-byte store: one division for the position, the
         // normalisation as a multiplication by 1 / sum (one more rounding than e / sum: <= 1 ulp)
@@ -510,7 +515,7 @@ __global__ __launch_bounds__(HB) void head_fwd_kernel(const float* __restrict__ 
                     ps += p[e];
                 }
                 c[0] += px; c[1] = fmaf(y, ps, c[1]);
-                *reinterpret_cast<float4*>(out + i) = make_float4(p[0], p[1], p[2], p[3]);
+                if (STORE) *reinterpret_cast<float4*>(out + i) = make_float4(p[0], p[1], p[2], p[3]);
             }
         }
     } else if (CACHED && VEC == 4) {
@@ -525,18 +530,29 @@ __global__ __launch_bounds__(HB) void head_fwd_kernel(const float* __restrict__ 
                     float x, y; g.xy(i + e, x, y);
                     c[0] = fmaf(x, p[e], c[0]); c[1] = fmaf(y, p[e], c[1]);
                 }
-                *reinterpret_cast<float4*>(out + i) = make_float4(p[0], p[1], p[2], p[3]);
+                if (STORE) *reinterpret_cast<float4*>(out + i) = make_float4(p[0], p[1], p[2], p[3]);
             }
         }
     } else {
         row.each([&](int i, float v) {
             const float p = (CACHED ? v : expf(v - m)) / denom;
-            out[i] = p;
+            if (STORE) out[i] = p;
             float x, y; g.xy(i, x, y);
             c[0] = fmaf(x, p, c[0]); c[1] = fmaf(y, p, c[1]);
         });
     }
     block_sum<2>(c, red);
+}
+
+template <int VEC, bool CACHED>
+__global__ __launch_bounds__(HB) void head_fwd_kernel(const float* __restrict__ logits, float* __restrict__ hm,
+                                                       float* __restrict__ coords, int h, int w) {
+    __shared__ float red[16];
+    const size_t off = (size_t)blockIdx.x * h * w;
+    Row<VEC, CACHED> row;
+    row.load(logits + off, h * w);
+    float c[2];
+    head_fwd_row<VEC, CACHED, true>(row, hm + off, h, w, red, c);
     if (threadIdx.x == 0) { coords[2 * (size_t)blockIdx.x] = c[0]; coords[2 * (size_t)blockIdx.x + 1] = c[1]; }
 }
 
@@ -961,6 +977,88 @@ extern "C" int dsnt_head_fwd(const float* logits, float* hm, float* coords, int6
     ROW_DISPATCH(head_fwd_kernel, (int)rows, h * w, dsnt_aligned16(logits) && dsnt_aligned16(hm), logits, hm,
                  coords, h, w);
     DSNT_CHECK_LAUNCH("dsnt_head_fwd");
+}
+
+// ------------------------------------------------------------------ flip-merged head (inference.py:38-57)
+// One workgroup per (sample b, joint j) row of the merged logits (flipmerge.h), read through a FlipSrc: softmax through
+// head_fwd_row (dsnt_head_fwd's arithmetic), the other preactivations through preact_row (dsnt_preact_fwd's) with
+// dsnt_expect_fwd's expectation in the sink; the same VEC / CACHED variant those launches take on the merged tensor, so
+// the coordinates are theirs bit for bit.  Thread 0 back-projects them in fp64.
+template <int VEC, bool CACHED, bool STORE>
+__global__ __launch_bounds__(HB) void flip_merge_dsnt_kernel(const float* __restrict__ logits, int B, int J, int h,
+                                                              int w, FlipPerm perm, int mode, float thr, float eps,
+                                                              const double* __restrict__ tm,
+                                                              const double* __restrict__ tb, float* __restrict__ hm,
+                                                              float* __restrict__ coords, double* __restrict__ img) {
+    __shared__ float red[16];
+    const int row = blockIdx.x, hw = h * w;
+    Row<VEC, CACHED, FlipSrc> r;
+    r.load(flip_src(logits, B, J, hw, w, perm, row), hw);
+    float* out = STORE ? hm + (size_t)row * hw : nullptr;
+    float c[2] = {0.f, 0.f};
+    if (mode == 0) {
+        head_fwd_row<VEC, CACHED, STORE>(r, out, h, w, red, c);
+    } else {
+        const Grid2 g(h, w);
+        preact_row(r, mode, thr, eps, red, [&](int i, float p) {
+            if (STORE) out[i] = p;
+            float x, y; g.xy(i, x, y);
+            c[0] = fmaf(x, p, c[0]); c[1] = fmaf(y, p, c[1]);
+        });
+        block_sum<2>(c, red);
+    }
+    if (threadIdx.x == 0) {
+        coords[2 * (size_t)row] = c[0];
+        coords[2 * (size_t)row + 1] = c[1];
+        flip_backproject(c[0], c[1], tm, tb, img, row / J, row);
+    }
+}
+
+extern "C" int dsnt_flip_merge_head(const float* logits, int64_t B, int J, int h, int w, const int* perm, int strategy,
+                                    int preact, float threshold, float eps, const double* transform_m,
+                                    const double* transform_b, float* hm, float* coords, double* img, void* stream) {
+    DSNT_REQUIRE(logits && perm && transform_m && transform_b && coords && img, DSNT_ERR_ARG,
+                 "dsnt_flip_merge_head: null pointer");
+    DSNT_REQUIRE(strategy == DSNT_FLIP_DSNT || strategy == DSNT_FLIP_GAUSS, DSNT_ERR_ARG,
+                 "dsnt_flip_merge_head: unknown strategy %d", strategy);
+    DSNT_REQUIRE(strategy != DSNT_FLIP_DSNT || (preact >= 0 && preact <= 4), DSNT_ERR_ARG,
+                 "dsnt_flip_merge_head: unknown preact mode %d", preact);
+    DSNT_REQUIRE(J > 0 && J <= DSNT_FLIP_MAX_J, DSNT_ERR_SHAPE, "dsnt_flip_merge_head: J=%d outside 1..%d", J,
+                 DSNT_FLIP_MAX_J);
+    DSNT_REQUIRE(B > 0 && 2 * B * J < (1LL << 31), DSNT_ERR_SHAPE, "dsnt_flip_merge_head: B=%lld out of range",
+                 (long long)B);
+    if (int e = check_rows("dsnt_flip_merge_head", 2 * B * J, h, w)) return e;
+    FlipPerm fp = {};
+    unsigned seen = 0;
+    for (int j = 0; j < J; ++j) {
+        DSNT_REQUIRE(perm[j] >= 0 && perm[j] < J && !(seen >> perm[j] & 1u), DSNT_ERR_ARG,
+                     "dsnt_flip_merge_head: perm is not a permutation of 0..%d (perm[%d] = %d)", J - 1, j, perm[j]);
+        seen |= 1u << perm[j];
+        fp.p[j] = perm[j];
+    }
+    if (strategy == DSNT_FLIP_GAUSS) {
+        flip_merge_decode_launch(logits, (int)B, J, h, w, fp, transform_m, transform_b, hm, coords, img, stream);
+        DSNT_CHECK_LAUNCH("dsnt_flip_merge_head");
+    }
+    // the variant dsnt_head_fwd / dsnt_preact_fwd + dsnt_expect_fwd pick for the (16-byte aligned) merged tensor
+    const int hw = h * w;
+    const bool vec = hw % 4 == 0 && dsnt_aligned16(logits) && (!hm || dsnt_aligned16(hm));
+    const bool cached = hw <= 4096;
+    const dim3 grid((unsigned)(B * J));
+    hipStream_t st = (hipStream_t)stream;
+#define FLIP_LAUNCH(V, C, S) DSNT_LAUNCH((flip_merge_dsnt_kernel<V, C, S>), grid, dim3(HB), 0, st, logits, (int)B, J, h, w, \
+                                         fp, preact, threshold, eps, transform_m, transform_b, hm, coords, img)
+    if (hm) {
+        if (vec && cached) FLIP_LAUNCH(4, true, true);
+        else if (cached) FLIP_LAUNCH(1, true, true);
+        else FLIP_LAUNCH(1, false, true);
+    } else {
+        if (vec && cached) FLIP_LAUNCH(4, true, false);
+        else if (cached) FLIP_LAUNCH(1, true, false);
+        else FLIP_LAUNCH(1, false, false);
+    }
+#undef FLIP_LAUNCH
+    DSNT_CHECK_LAUNCH("dsnt_flip_merge_head");
 }
 
 extern "C" int dsnt_head_loss_rows(const float* hm, const float* coords, const float* target, float* dist,

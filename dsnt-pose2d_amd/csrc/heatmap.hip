@@ -6,6 +6,7 @@
 // (image, joint) row of H*W floats; the 7x7 target bump is evaluated in-register, never materialised
 // for the loss.
 #include "common.h"
+#include "flipmerge.h"
 #include <math.h>
 
 // The reference's coordinate arithmetic is a chain of separately rounded fp32 tensor ops (add_, mul_, add_);
@@ -87,12 +88,13 @@ __global__ __launch_bounds__(HB) void heatmap_mse_bwd_kernel(const float* __rest
 
 // util.py:150-198: first arg-max pixel, (0, 0) when the maximum is not positive, +-0.25 px towards the larger
 // neighbour for interior pixels, then pixel -> normalised coordinates ((p + 0.5) * (2/size) - 1, fp32 steps).
-__global__ __launch_bounds__(HB) void decode_heatmaps_kernel(const float* __restrict__ hm, float* __restrict__ coords,
-                                                              int h, int w, int use_neighbours, float sx, float sy) {
+// One row read from `x` (a `const float*`, or the flip-merged logits of dsnt_flip_merge_head: FlipSrc); thread 0 returns
+// true with the coordinates in (cx, cy).
+template <typename SRC>
+__device__ __forceinline__ bool decode_row(const SRC& x, int h, int w, int use_neighbours, float sx, float sy, float& cx,
+                                           float& cy) {
     __shared__ float rv[4];
     __shared__ int ri[4];
-    const long row = blockIdx.x;
-    const float* x = hm + (size_t)row * h * w;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = threadIdx.x; i < h * w; i += HB) {
@@ -124,9 +126,55 @@ __global__ __launch_bounds__(HB) void decode_heatmaps_kernel(const float* __rest
             }
         }
         // sx = float(2 / w), sy = float(2 / h) rounded on the host exactly like the reference's Python scalars
-        coords[2 * row + 0] = __fadd_rn(__fmul_rn(__fadd_rn(px, 0.5f), sx), -1.f);
-        coords[2 * row + 1] = __fadd_rn(__fmul_rn(__fadd_rn(py, 0.5f), sy), -1.f);
+        cx = __fadd_rn(__fmul_rn(__fadd_rn(px, 0.5f), sx), -1.f);
+        cy = __fadd_rn(__fmul_rn(__fadd_rn(py, 0.5f), sy), -1.f);
+        return true;
     }
+    return false;
+}
+
+__global__ __launch_bounds__(HB) void decode_heatmaps_kernel(const float* __restrict__ hm, float* __restrict__ coords,
+                                                              int h, int w, int use_neighbours, float sx, float sy) {
+    const long row = blockIdx.x;
+    float cx, cy;
+    if (decode_row(hm + (size_t)row * h * w, h, w, use_neighbours, sx, sy, cx, cy)) {
+        coords[2 * row + 0] = cx;
+        coords[2 * row + 1] = cy;
+    }
+}
+
+// dsnt_flip_merge_head, gauss strategy (model.py:268-269 on the merged heat-maps of inference.py:38-48): the merged row
+// is stored when hm != NULL, then decoded as dsnt_decode_heatmaps does (use_neighbours = 1) and back-projected.
+template <bool STORE>
+__global__ __launch_bounds__(HB) void flip_merge_decode_kernel(const float* __restrict__ logits, int B, int J, int h,
+                                                                int w, FlipPerm perm, float sx, float sy,
+                                                                const double* __restrict__ tm,
+                                                                const double* __restrict__ tb, float* __restrict__ hm,
+                                                                float* __restrict__ coords, double* __restrict__ img) {
+    const int row = blockIdx.x, hw = h * w;
+    const FlipSrc x = flip_src(logits, B, J, hw, w, perm, row);
+    if (STORE) {
+        float* o = hm + (size_t)row * hw;
+        for (int i = threadIdx.x; i < hw; i += HB) o[i] = x[i];
+    }
+    float cx, cy;
+    if (decode_row(x, h, w, 1, sx, sy, cx, cy)) {
+        coords[2 * (size_t)row] = cx;
+        coords[2 * (size_t)row + 1] = cy;
+        flip_backproject(cx, cy, tm, tb, img, row / J, row);
+    }
+}
+
+int flip_merge_decode_launch(const float* logits, int B, int J, int h, int w, const FlipPerm& perm, const double* tm,
+                             const double* tb, float* hm, float* coords, double* img, void* stream) {
+    const float sx = (float)(2.0 / (double)w), sy = (float)(2.0 / (double)h);
+    if (hm)
+        DSNT_LAUNCH(flip_merge_decode_kernel<true>, dim3((unsigned)(B * J)), dim3(HB), 0, (hipStream_t)stream, logits, B,
+                    J, h, w, perm, sx, sy, tm, tb, hm, coords, img);
+    else
+        DSNT_LAUNCH(flip_merge_decode_kernel<false>, dim3((unsigned)(B * J)), dim3(HB), 0, (hipStream_t)stream, logits,
+                    B, J, h, w, perm, sx, sy, tm, tb, hm, coords, img);
+    return DSNT_OK;
 }
 
 static int check_rows_hm(const char* who, int64_t rows, int h, int w, float sigma) {

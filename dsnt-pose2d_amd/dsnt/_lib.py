@@ -86,6 +86,7 @@ SIGNATURES = {
     'dsnt_masked_avg_fwd': [P, P, P, L, P],
     'dsnt_masked_avg_bwd': [P, P, P, P, L, P],
     'dsnt_head_fwd': [P, P, P, L, I, I, P],
+    'dsnt_flip_merge_head': [P, L, I, I, I, P, I, I, F, F, P, P, P, P, P, P],
     'dsnt_head_loss_rows': [P, P, P, P, P, L, I, I, F, I, P],
     'dsnt_head_bwd': [P, P, P, P, P, P, P, L, I, I, F, I, P],
     'dsnt_head_loss_grad': [P, P, P, P, P, P, P, P, L, I, I, F, I, F, P],
@@ -159,6 +160,7 @@ SIGNATURES = {
     'dsnt_nonfinite_flag': [P, L, P, I, P],
     'dsnt_pckh': [P, P, P, P, P, P, F, P, P, I, I, P],
     'dsnt_augment_fwd': [P, I, I, I, P, P, P, P, I, C.c_uint64, C.c_uint64, P, P, P, P],
+    'dsnt_augment_fwd_pair': [P, I, I, I, P, P, P, P, I, C.c_uint64, C.c_uint64, P, P, P, P],
     'dsnt_augment_keypoints': [P, P, P, I, I, P, P, P, P, I, P, P, P, P, P],
     'dsnt_pool_normalize': [P, I, I, I, I, I, P, P, P, P],
     'dsnt_debug_mfma_peak': [P, I, I, I, I, P],

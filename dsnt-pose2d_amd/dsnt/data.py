@@ -100,6 +100,10 @@ class DeviceAugment:
     gain 1).  `train` masks joints that leave the crop (`|coord| >= 1`), as the reference does for the train subset.
     Values of given `params` are not checked on the host (that would synchronise): scale must lie in (1/R, 8].
     Everything is enqueued on the current stream; nothing synchronises with the host.
+
+    `flip_pair=True` (flip test-time augmentation, `inference.predict(..., paired=True)`): the same launch also
+    writes every pixel mirrored into a second half, and the dict gains `input_pair` f32 `[2B, 3, S, S]` whose rows
+    `B..2B-1` are exactly `input.flip(-1)`; `input` is then a view of its first half, with the same values.
     """
 
     def __init__(self, image_specs, mean, std, use_aug=True, train=True, seed=0):
@@ -120,7 +124,7 @@ class DeviceAugment:
             self._dev[device] = c
         return c
 
-    def __call__(self, src_u8, keypoints, keypoint_mask, matrix, head_lengths, step, params=None):
+    def __call__(self, src_u8, keypoints, keypoint_mask, matrix, head_lengths, step, params=None, flip_pair=False):
         if not isinstance(src_u8, torch.Tensor) or src_u8.dim() != 4 or src_u8.shape[1] != src_u8.shape[2] \
                 or src_u8.shape[3] != 3:
             raise RuntimeError('dsnt: src_u8 must be [B, R, R, 3] (HWC crops), got %s'
@@ -163,10 +167,11 @@ class DeviceAugment:
         if J != flip.numel():
             flip = torch.arange(J, device=dev)       # never applied: no sample is flipped
         S = self.image_specs.size
-        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-        _lib.call('dsnt_augment_fwd', _lib.ptr(src_u8), B, R, S, _lib.ptr(scale), _lib.ptr(rot), _lib.ptr(hflip),
-                  _lib.ptr(gain), draw, self.seed & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _lib.ptr(mean),
-                  _lib.ptr(std), _lib.ptr(out))
+        pair = torch.empty(2 * B if flip_pair else B, 3, S, S, dtype=torch.float32, device=dev)
+        _lib.call('dsnt_augment_fwd_pair' if flip_pair else 'dsnt_augment_fwd', _lib.ptr(src_u8), B, R, S, _lib.ptr(scale),
+                  _lib.ptr(rot), _lib.ptr(hflip), _lib.ptr(gain), draw, self.seed & (2 ** 64 - 1),
+                  int(step) & (2 ** 64 - 1), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(pair))
+        out = pair[:B]
         pc = torch.empty(B, J, 2, dtype=torch.float32, device=dev)
         pm = torch.empty(B, J, dtype=torch.float32, device=dev)
         tm = torch.empty(B, 2, 2, dtype=torch.float64, device=dev)
@@ -174,6 +179,9 @@ class DeviceAugment:
         _lib.call('dsnt_augment_keypoints', _lib.ptr(matrix), _lib.ptr(keypoints), _lib.ptr(kmask), B, J,
                   _lib.ptr(scale), _lib.ptr(rot), _lib.ptr(hflip), _lib.ptr(flip), 1 if self.train else 0,
                   _lib.ptr(pc), _lib.ptr(pm), _lib.ptr(tm), _lib.ptr(tb))
-        return {'normalize': normalize, 'transform_b': tb, 'transform_m': tm, 'input': out, 'part_mask': pm,
-                'part_coords': pc, 'hflip': hflip.bool(),
-                'params': {'scale': scale, 'rot': rot, 'hflip': hflip, 'gain': gain}}
+        sample = {'normalize': normalize, 'transform_b': tb, 'transform_m': tm, 'input': out, 'part_mask': pm,
+                  'part_coords': pc, 'hflip': hflip.bool(),
+                  'params': {'scale': scale, 'rot': rot, 'hflip': hflip, 'gain': gain}}
+        if flip_pair:
+            sample['input_pair'] = pair
+        return sample

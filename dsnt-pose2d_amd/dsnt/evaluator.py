@@ -50,6 +50,7 @@ class PCKhEvaluator:
         self.meters = {n: _Meter() for n in self.JOINT_NAMES + list(self.JOINT_GROUPS)}
         self._members = {g: [self.JOINT_NAMES.index(n) for n in sorted(names)]
                          for g, names in self.JOINT_GROUPS.items()}
+        self._member_idx = {}      # (device, n_joints) -> {group: device index tensor}: no host upload per batch
 
     @staticmethod
     def calculate_pckh_distance(pred, target, ref_dist):
@@ -62,9 +63,14 @@ class PCKhEvaluator:
             name = self.JOINT_NAMES[j] if n_joints == len(self.JOINT_NAMES) else None
             if name is not None:
                 self.meters[name].add_tensors(hj[j], vj[j])
-        for g, idx in self._members.items():
-            idx = [i for i in idx if i < n_joints]
-            self.meters[g].add_tensors(hj[idx].sum(), vj[idx].sum())
+        key = (hj.device, n_joints)
+        groups = self._member_idx.get(key)
+        if groups is None:
+            groups = {g: torch.tensor([i for i in idx if i < n_joints], dtype=torch.long, device=hj.device)
+                      for g, idx in self._members.items()}
+            self._member_idx[key] = groups
+        for g, idx in groups.items():
+            self.meters[g].add_tensors(hj.index_select(0, idx).sum(), vj.index_select(0, idx).sum())
 
     def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m,
                        transform_b):

@@ -8,11 +8,20 @@ left<->right (`:43-45`) before `forward_part2` turns the mean logits into coordi
 coordinates are mapped back with `baddbmm(transform_b, coords, transform_m)` in fp64 (`:54-57`).
 The progress bar and the tele meters are out of scope; `time_meter`, if given, only needs `.add(seconds)`.
 The backbone and the DSNT head run on the HIP path (eval-mode BN from the running statistics).
+
+`predict` and `predict_dataset` are the batched form of the same computation (any batch size, flip augmentation
+included, nothing synchronising with the host): the mirrored twin of every input runs in the same forward, and one
+launch (`flip_merge_head`, `dsnt_flip_merge_head`) merges the last stack's logits, runs the head and back-projects.
 """
+import ctypes
 import time
 
 import torch
 from torch.utils.data import DataLoader
+
+from . import _lib
+from . import nn as dnn
+from . import util as dutil
 
 # MPII_Joint_Horizontal_Flips of `torchdata.mpii` (absent third-party package, reference data.py:15,97):
 # the standard MPII order r-ankle, r-knee, r-hip, l-hip, l-knee, l-ankle, pelvis, thorax, upper neck,
@@ -62,3 +71,131 @@ def generate_predictions(model, dataset, use_flipped=True, batch_size=1, time_me
             preds[pos:pos + n] = orig_preds
             pos += n
     return preds
+
+
+# ------------------------------------------------------------------ batched evaluation
+_STRATEGIES = {'dsnt': 0, 'gauss': 1}     # DSNT_FLIP_DSNT, DSNT_FLIP_GAUSS
+_perm_cache = {}
+
+
+def _host_perm(perm):
+    key = tuple(int(v) for v in perm)
+    arr = _perm_cache.get(key)
+    if arr is None:
+        arr = (ctypes.c_int * len(key))(*key)
+        _perm_cache[key] = arr
+    return arr
+
+
+def flip_merge_head(logits, transform_m, transform_b, strategy='dsnt', preact='softmax', perm=None, heatmaps=True):
+    """The merge and head of flip test-time augmentation for a paired batch, in one launch (`dsnt_flip_merge_head`).
+
+    `logits` f32 `[2B, J, h, w]`: the last stack's heat-map logits, rows `B..2B-1` those of the mirrored inputs.
+    Merges `(L[b] + L[B+b][perm].flip(-1)) / 2` (inference.py:40-46 of the reference), then `strategy` 'dsnt'
+    applies `preact` and the DSNT expectation (the values `forward_part2` + `compute_coords` give on the merged
+    logits) and 'gauss' decodes the arg-max (`util.decode_heatmaps`).  `perm` defaults to `HFLIP_INDICES` (a host
+    sequence; it is checked there, never read from the device).  Returns `(image_coords, coords, heatmaps)`: f64
+    `[B, J, 2]` = `transform_b + coords @ transform_m`, the normalised f32 `[B, J, 2]`, and the merged heat-maps
+    `[B, J, h, w]` (or None when `heatmaps=False`).  `transform_m` f64 `[B, 2, 2]`, `transform_b` f64 `[B, 1, 2]`."""
+    if strategy not in _STRATEGIES:
+        raise RuntimeError('dsnt: flip_merge_head supports the dsnt and gauss strategies, not %r' % (strategy,))
+    if preact not in dnn.PREACT_MODES:
+        raise Exception('unrecognised heatmap preactivation function: {}'.format(preact))
+    x = _lib.f32(logits).contiguous()
+    if x.dim() != 4 or x.size(0) % 2:
+        raise RuntimeError('dsnt: flip_merge_head needs paired logits [2B, J, h, w], got %s' % (tuple(x.shape),))
+    B, J, h, w = x.size(0) // 2, x.size(1), x.size(2), x.size(3)
+    tm = transform_m.to(device=x.device, dtype=torch.float64).reshape(B, 2, 2).contiguous()
+    tb = transform_b.to(device=x.device, dtype=torch.float64).reshape(B, 1, 2).contiguous()
+    perm = HFLIP_INDICES.tolist() if perm is None else [int(v) for v in perm]
+    if len(perm) != J:
+        raise RuntimeError('dsnt: flip_merge_head: %d flip indices for %d joints' % (len(perm), J))
+    mode = dnn.PREACT_MODES[preact]
+    thr = -0.5 if mode == 1 else 0.0           # hm_preact's arguments (model.py:24-45)
+    eps = 0.0 if mode == 0 else 1e-12
+    coords = torch.empty(B, J, 2, device=x.device, dtype=torch.float32)
+    img = torch.empty(B, J, 2, device=x.device, dtype=torch.float64)
+    hm = torch.empty(B, J, h, w, device=x.device, dtype=torch.float32) if heatmaps else None
+    _lib.call('dsnt_flip_merge_head', _lib.ptr(x), B, J, h, w, _host_perm(perm), _STRATEGIES[strategy], mode, thr, eps,
+              _lib.ptr(tm), _lib.ptr(tb), _lib.ptr(hm), _lib.ptr(coords), _lib.ptr(img))
+    return img, coords, hm
+
+
+def _last(out):
+    return out[-1] if isinstance(out, (list, tuple)) else out
+
+
+def _is_hourglass(model):
+    from .model import HourglassHumanPoseModel
+    return isinstance(model, HourglassHumanPoseModel)
+
+
+def _set_heatmaps(model, hm):
+    if _is_hourglass(model):
+        model.heatmaps_array = [hm]           # `model.heatmaps` is heatmaps_array[0]
+    else:
+        model.heatmaps = hm
+
+
+def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=False, return_normalized=False):
+    """Joint positions in original-image pixels for a batch, on the device: f64 `[B, J, 2]`.
+
+    `inputs` f32 `[B, 3, S, S]` on the device, or with `paired=True` the `[2B, 3, S, S]` `input_pair` of
+    `data.DeviceAugment(..., flip_pair=True)` (rows `B..2B-1` the mirrored inputs).  `transform_m` `[B, 2, 2]`,
+    `transform_b` `[B, 1, 2]`.  Per sample this is what `generate_predictions(..., batch_size=1)` computes, at any
+    batch size, for hourglass and ResNet models:
+      * `use_flipped`: the pair (built here with ATen's flip unless `paired`) runs in one forward; for the 'dsnt'
+        and 'gauss' strategies one `dsnt_flip_merge_head` launch merges the last stack's logits, runs the head and
+        back-projects.  The 'fc' strategy falls back to the ATen merge (`flip`, `index_select`, add, divide) and
+        `forward_part2`, then `baddbmm`.
+      * otherwise: `forward`, the device-side `compute_coords` and `baddbmm`.
+    The model is put in eval mode.  Nothing synchronises with the host.  `model.heatmaps` holds the (merged)
+    heat-maps afterwards.  `return_normalized=True` returns `(image_coords, normalised f32 coords)`."""
+    model.eval()
+    S = 2 if (use_flipped and paired) else 1
+    if inputs.size(0) % S:
+        raise RuntimeError('dsnt: predict(paired=True) needs an input_pair [2B, 3, S, S], got %s' % (tuple(inputs.shape),))
+    B = inputs.size(0) // S
+    tm = transform_m.to(device=inputs.device, dtype=torch.float64)
+    tb = transform_b.to(device=inputs.device, dtype=torch.float64).reshape(B, 1, 2)
+    with torch.no_grad():
+        if use_flipped:
+            pair = inputs if paired else torch.cat([inputs, reverse_tensor(inputs, -1)], 0)
+            logits = _last(model.forward_part1(pair))
+            strat = model.output_strat
+            if strat in _STRATEGIES:
+                img, coords, hm = flip_merge_head(logits, tm, tb, strat, model.preact)
+                _set_heatmaps(model, hm)
+            else:
+                hm1, hm2 = logits.split(B)
+                hm2 = reverse_tensor(hm2, -1).index_select(-3, HFLIP_INDICES.to(hm2.device))
+                hm = (hm1 + hm2) / 2
+                # a bare tensor would be iterated per sample by the hourglass head (the reference's batch-1 quirk)
+                coords = _last(model.forward_part2([hm] if _is_hourglass(model) else hm)).detach().float()
+                img = torch.baddbmm(tb, coords.double(), tm)
+        else:
+            out = _last(model(inputs))
+            coords = dutil.decode_heatmaps(out) if model.output_strat == 'gauss' else out.detach().float()
+            img = torch.baddbmm(tb, coords.double(), tm)
+    return (img, coords) if return_normalized else img
+
+
+def predict_dataset(model, dataset, use_flipped=True, batch_size=32, time_meter=None):
+    """`generate_predictions` at any batch size: a CPU DoubleTensor `[len(dataset), J, 2]` of joint positions in
+    original-image pixels, per sample what the batch-1 flip loop gives.  Predictions stay on the device until the
+    one copy at the end; with a `time_meter` each batch is timed, which synchronises once per batch."""
+    model.cuda()
+    model.eval()
+    loader = DataLoader(dataset, batch_size, num_workers=0)
+    preds = []
+    for batch in loader:
+        start = time.perf_counter()
+        img = predict(model, batch['input'].cuda(), batch['transform_m'].cuda(), batch['transform_b'].cuda(),
+                      use_flipped=use_flipped)
+        if time_meter is not None:
+            torch.cuda.synchronize()
+            time_meter.add(time.perf_counter() - start)
+        preds.append(img)
+    if not preds:
+        return torch.zeros(0, 16, 2, dtype=torch.float64)
+    return torch.cat(preds, 0).cpu()

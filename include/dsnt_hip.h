@@ -136,6 +136,23 @@ int dsnt_masked_avg_bwd(const float* g_out, const float* mask, const float* out2
  * Writes normalised heat-maps and coords. */
 int dsnt_head_fwd(const float* logits, float* hm, float* coords, int64_t rows, int h, int w,
                   void* stream);
+/* Flip-merged head of test-time flip augmentation, batched: replaces the merge and head of inference.py:38-57
+ * (cat/flip/index_select/add/divide, forward_part2, compute_coords and baddbmm per batch of ONE sample).
+ * logits f32 [2B][J][h][w], the last stack's heat-map logits of a paired batch (rows B..2B-1: the mirrored inputs).
+ * Per (b, j): m[y][x] = (L[b][j][y][x] + L[B+b][perm[j]][y][w-1-x]) / 2 (fp32), then
+ *   strategy DSNT_FLIP_DSNT:  preact (0..4 = softmax, thresholded_softmax, abs, relu, sigmoid, with threshold and eps as
+ *                             dsnt_preact_fwd takes them) and the DSNT expectation; the coordinates equal dsnt_head_fwd's
+ *                             (softmax) or dsnt_preact_fwd + dsnt_expect_fwd's on the merged tensor, bit for bit;
+ *   strategy DSNT_FLIP_GAUSS: the arg-max decode of dsnt_decode_heatmaps (use_neighbours = 1) of m (preact ignored).
+ * Out: coords f32 [B][J][2] (normalised); img f64 [B][J][2] = transform_b[b] + coords . transform_m[b] computed in fp64
+ * (transform_m f64 [B][2][2], transform_b f64 [B][1][2]); hm f32 [B][J][h][w] = the merged heat-maps (the normalised
+ * ones for dsnt, m itself for gauss), or NULL.  perm: HOST int[J], a permutation of 0..J-1 (inference.HFLIP_INDICES),
+ * J <= 32, passed by value to the kernel.  Maps as dsnt_head_fwd accepts.  dsnt_version() >= 116. */
+#define DSNT_FLIP_DSNT 0
+#define DSNT_FLIP_GAUSS 1
+int dsnt_flip_merge_head(const float* logits, int64_t B, int J, int h, int w, const int* perm, int strategy,
+                         int preact, float threshold, float eps, const double* transform_m, const double* transform_b,
+                         float* hm, float* coords, double* img, void* stream);
 /* Fused head, loss: model.py:233-246 — per-row Euclidean distance and regulariser value
  * (reg_kind -1 = none) from the saved heat-maps; reductions by dsnt_masked_avg_fwd. */
 int dsnt_head_loss_rows(const float* hm, const float* coords, const float* target,
@@ -709,6 +726,12 @@ int dsnt_pckh(const float* pred, const float* target, const double* m, const dou
 int dsnt_augment_fwd(const uint8_t* src, int B, int R, int S, float* scale, float* rot_deg, uint8_t* hflip,
                      float* gain, int draw, uint64_t seed, uint64_t step, const float* mean, const float* stdv,
                      float* out, void* stream);
+/* dsnt_augment_fwd_pair: dsnt_augment_fwd with out f32 [2B][3][S][S]; out[B + b][c][y][x] = out[b][c][y][S-1-x], the
+ * mirrored twin flip test-time augmentation feeds the model (replaces inference.py:37's cat + reverse_tensor).
+ * dsnt_version() >= 116. */
+int dsnt_augment_fwd_pair(const uint8_t* src, int B, int R, int S, float* scale, float* rot_deg, uint8_t* hflip,
+                          float* gain, int draw, uint64_t seed, uint64_t step, const float* mean, const float* stdv,
+                          float* out, void* stream);
 /* data.py:150-196 in fp64: matrix [B][3][3] (bb transform), keypoints [B][J][2] (original-image pixels), keypoint_mask
  * [B][J]; the parameters of dsnt_augment_fwd; flip_idx [J] (a permutation: inference.HFLIP_INDICES); train != 0: mask joints
  * with |coord| >= 1.  Out: part_coords f32 [B][J][2], part_mask f32 [B][J], trans_m f64 [B][2][2], trans_b f64 [B][1][2]. */
