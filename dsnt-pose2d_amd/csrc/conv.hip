@@ -2678,6 +2678,31 @@ extern "C" int64_t dsnt_conv_wgrad_f16x3_ws_floats(const dsnt_conv_geom* g, int 
 }
 extern "C" int dsnt_conv_wgrad_halo_ok(const dsnt_conv_geom* g) { return g ? dsnt_wg3_plan(g, 0).ok : 0; }
 
+// Which kernel an fp16x3 launch of this geometry reaches (both operand bounds given, no second residual, no BatchNorm-backward
+// epilogue).  wgrad = 0, dsnt_conv_fwd_f16x3_ex: 1 the streaming 1x1 kernel (gemm1.hip), 2 the LDS halo-tile kernel, 0 the implicit
+// GEMM.  wgrad = 1, dsnt_conv_wgrad_f16x3: 1 the stem kernel (stem4.hip), 2 the halo kernel (wgrad3.hip), 3 the 1x1 kernel
+// (wgrad1.hip), 0 the generic one.  Negative: the geometry is not supported.
+extern "C" int dsnt_conv_f16x3_route(const dsnt_conv_geom* g, int wgrad) {
+    if (!g || check_geom(g, "dsnt_conv_f16x3_route") != 0) return -1;
+    if (wgrad) {
+        if (!dsnt_conv_wgrad_bf16x6_ok(g)) return -1;
+        if (dsnt_stem4_wgrad_slabs(g)) return 1;
+        if (dsnt_wg3_plan(g, 0).ok) return 2;
+        if (dsnt_wg1_plan(g, false).ok) return 3;
+        return 0;
+    }
+    if (!dsnt_conv_bf16x6_ok(g)) return -1;
+    static const float one = 1.f;
+    ConvP p;
+    memset(&p, 0, sizeof(p));
+    p.a_bound = &one; p.w_bound = &one; p.wq = reinterpret_cast<const unsigned short*>(&one);
+    p.N = g->N; p.H = g->H; p.W = g->W; p.Cin = g->Cin; p.Ho = g->Ho; p.Wo = g->Wo; p.Cout = g->Cout;
+    p.R = g->R; p.S = g->S; p.stride = g->stride; p.pad = g->pad; p.dil = g->dil;
+    p.M = g->N * g->Ho * g->Wo; p.K = g->R * g->S * g->Cin;
+    if (dsnt_gemm1_cfg(p) > 0) return 1;
+    return conv3x3_halo_ok(g) && !g_force_gemm6 ? 2 : 0;
+}
+
 static int conv_wgrad_impl(const float* x, const float* in_scale, const float* in_shift, int in_relu,
                            const float* dy, float* ws, float* dw, float* dbias, int accumulate,
                            const dsnt_conv_geom* g, void* stream, bool bf16x6, const float* a_bound,

@@ -195,6 +195,7 @@ PLAIN = {
     'dsnt_conv_wgrad_bf16x6_ok': (I, [GP]),
     'dsnt_conv_wgrad_splits': (I, [GP]),
     'dsnt_conv_wgrad_halo_ok': (I, [GP]),
+    'dsnt_conv_f16x3_route': (I, [GP, I]),
     'dsnt_conv_fwd_stream_ok': (I, [GP]),
     'dsnt_conv_fwd_stream_form': (I, [GP, I]),
     'dsnt_conv_dgrad_strided_ok': (I, [GP]),

@@ -372,6 +372,10 @@ int dsnt_conv_wgrad_desc_f16x3(const float* x, const float* in_scale, const floa
  * launch runs as four-wave workgroups, one per CU, over half as many slabs; both fall back to the plain plan for every
  * other geometry). */
 int dsnt_conv_wgrad_halo_ok(const dsnt_conv_geom* g);
+/* Which kernel an fp16x3 launch of geometry g reaches (both bounds given, no second residual, no BatchNorm-backward epilogue).
+ * wgrad = 0 (dsnt_conv_fwd_f16x3_ex): 1 streaming 1x1, 2 halo tile, 0 implicit GEMM; wgrad = 1 (dsnt_conv_wgrad_f16x3): 1 stem,
+ * 2 halo, 3 1x1, 0 generic.  < 0: not supported. */
+int dsnt_conv_f16x3_route(const dsnt_conv_geom* g, int wgrad);
 int dsnt_conv_wgrad_f16x3_splits(const dsnt_conv_geom* g, int accumulate);
 int64_t dsnt_conv_wgrad_f16x3_ws_floats(const dsnt_conv_geom* g, int accumulate);
 
