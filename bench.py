@@ -6,14 +6,16 @@ forward -> forward_loss -> zero_grad -> backward (-> gradient all-reduce) -> opt
 on synthetic 256x256x3 crops already resident in HBM, 16 joints, 64x64 heat-maps.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hg2_js|hg1|hg8_js|resnet34] [--batch B]
-                  [--global-batch G] [--dump-outputs DIR]
+                  [--global-batch G] [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline]]
 
 For N > 1 either `python bench.py --gpus N` (it starts its own N ranks as a child `python -m torch.distributed.run`, forwards
 rank 0's line and exit code) or `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` directly (one rank
 per GPU, RCCL).  Rank 0 prints ONE JSON line.  Default scaling is weak: the per-GPU batch is
 fixed (32; hg8: 16) as N grows.  `--global-batch G` fixes the TOTAL batch instead (per-GPU batch G / N,
 "scaling": "strong") — north_star quotes efficiency at global batch 256: `--global-batch 256` at N = 1 and 8.
-Besides the whole-job throughput the line carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the whole-job throughput,
+`step_bounds` (the timed step against its two floors, arithmetic only) and, for N > 1, `dp`.  `--full` adds the legs that
+take runs of their own, after the timed steps (`--no-extras` drops all but cpu_baseline, `--no-cpu-baseline` that one):
   roofline     — the dominant kernel (3x3 128->128 halo convolution at 64x64, the shape that holds ~half of the
                  backbone FLOPs) timed live with HIP events on its stream: algorithmic FLOPs / launch time vs the
                  split-precision MFMA peak; `roofline.by_time`: the step's largest kernel families (weight gradients,
@@ -26,7 +28,9 @@ Besides the whole-job throughput the line carries
                  sweep, then 2 warm-up + 5 timed steps at the best count;
   parity       — max |dcoord| and PCKh@0.5 of the HIP path vs the CPU oracle on a small fixed batch with
                  the weights the timed steps ended on (outside the timed region);
-  head_roofline — the DSNT head kernels alone on a B = 1024 batch: achieved HBM GB/s.
+  head_roofline — the DSNT head kernels alone on a B = 1024 batch: achieved HBM GB/s;
+  flip_tta_images_per_sec — `--workload hg2_infer` only: the flip-augmented forward, timed like the plain one (also run
+                 by --dump-outputs, which writes its result).
 `--dump-outputs DIR` writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (rank 0):
 the coordinates of every stack, the loss, the last stack's heat-maps, and a fixed seeded sample of the updated parameters
 and of the gradients (inference: the coordinates of both forms).  Inputs and weights are seeded, so two builds run with
@@ -549,9 +553,10 @@ def dump_outputs(path, arrays):
 
 
 def infer_bench(model, x, batch, world, rank, args):
-    """Eval-mode forward throughput (replicas only across GPUs: no collective), with and without the reference's
-    horizontal-flip test-time augmentation (inference.py:33-48: both orientations through the backbone, the flipped
-    half mirrored back with left/right joints swapped, mean of the un-normalised heat-maps, then the DSNT head)."""
+    """Eval-mode forward throughput (replicas only across GPUs: no collective) and, with --full or --dump-outputs (which
+    writes its last result), the same with the reference's horizontal-flip test-time augmentation (inference.py:33-48: both
+    orientations through the backbone, the flipped half mirrored back with left/right joints swapped, mean of the
+    un-normalised heat-maps, then the DSNT head)."""
     from dsnt.inference import HFLIP_INDICES
     model.eval()
     idx = HFLIP_INDICES.to(x.device)
@@ -566,7 +571,10 @@ def infer_bench(model, x, batch, world, rank, args):
             hm2 = hm[batch:].flip(-1).index_select(-3, idx)
             return model.forward_part2([(hm[:batch] + hm2) / 2])[-1]
     res, last = {}, {}
-    for name, fn in (('plain', plain), ('flip_tta', flipped)):
+    legs = [('plain', plain)]
+    if args.full or args.dump_outputs:
+        legs.append(('flip_tta', flipped))
+    for name, fn in legs:
         for _ in range(max(args.warmup, 1)):
             fn()
         torch.cuda.synchronize()
@@ -587,9 +595,10 @@ def infer_bench(model, x, batch, world, rank, args):
                'ms_per_step': round(1e3 * res['plain'], 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
                'dtype': 'f32', 'data': 'synthetic',
                'config': {'workload': 'hg2 + DSNT inference, batch %d per GPU, replicas' % batch, 'global_batch': world * batch,
-                          'parallelism': 'replicas%d' % world},
-               'flip_tta_images_per_sec': round(world * batch / res['flip_tta'], 1),
-               'note': 'not the BASELINE metric (that is the train step: default workload)'}
+                          'parallelism': 'replicas%d' % world}}
+        if 'flip_tta' in res:
+            out['flip_tta_images_per_sec'] = round(world * batch / res['flip_tta'], 1)
+        out['note'] = 'not the BASELINE metric (that is the train step: default workload)'
         print(json.dumps(out), file=_JSON_OUT, flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -647,8 +656,7 @@ def launch_ranks(n_gpus, argv):
     return child.returncode
 
 
-def main():
-    _claim_stdout()
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
@@ -657,8 +665,13 @@ def main():
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch (default: the workload\'s)')
     ap.add_argument('--global-batch', type=int, default=None,
                     help='strong scaling: total batch over all GPUs (per-GPU batch = this / N)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the parity / head / dominant-kernel legs (profiling)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the legs the headline figure does not need: dominant-kernel, '
+                         'kernel-family and head rooflines, parity with the CPU oracle, the CPU baseline (hg2_infer: the '
+                         'flip-augmented forward)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true',
+                    help='with --full: skip the parity / head / dominant-kernel legs (profiling)')
     ap.add_argument('--force-dp', action='store_true', help='wire the data-parallel hooks even at world size 1 (testing)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last one computed (coords, loss, heat-maps, a fixed sample '
@@ -666,7 +679,27 @@ def main():
     ap.add_argument('--baseline-ips', type=float, default=None,
                     help='images/sec of the 1-GPU run of the same scaling mode: the line then carries `efficiency` = '
                          'value / (N x this)')
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def full_legs(args, model, base, reg, batch, world, ips):
+    """--full, rank 0, after the timed steps: the fields of the line that take runs of their own, in the line's order."""
+    out = {}
+    if not args.no_extras:
+        out['roofline'] = dominant_kernel_roofline(batch)
+        out['roofline']['by_time'] = family_rooflines(batch)
+        out['head_roofline'] = head_roofline()
+        if hasattr(model, 'hg'):
+            out['parity'] = parity_vs_oracle(model, base, reg)
+    if world == 1 and not args.no_cpu_baseline:
+        out['cpu_baseline'] = cpu_baseline(base, reg)
+        out['speedup_vs_cpu'] = round(ips / out['cpu_baseline']['value'], 1)
+    return out
+
+
+def main():
+    _claim_stdout()
+    args = parse_args()
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` as the driver calls it: this process becomes the launcher of N ranks and nothing else
@@ -846,15 +879,8 @@ def main():
                 # for what it is; the driver computes the real efficiency from its own N = 1 run
                 key = 'efficiency' if base_src == '--baseline-ips' else 'efficiency_vs_committed'
                 out['dp'][key] = round(ips / (base_ips * world), 4)
-        if not args.no_extras:
-            out['roofline'] = dominant_kernel_roofline(batch)
-            out['roofline']['by_time'] = family_rooflines(batch)
-            out['head_roofline'] = head_roofline()
-            if hasattr(model, 'hg'):
-                out['parity'] = parity_vs_oracle(model, base, reg)
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(base, reg)
-            out['speedup_vs_cpu'] = round(out['value'] / out['cpu_baseline']['value'], 1)
+        if args.full:
+            out.update(full_legs(args, model, base, reg, batch, world, out['value']))
     if dist.is_initialized():
         if world > 1:
             dist.barrier()

@@ -234,3 +234,37 @@ def test_bench_starts_its_own_ranks_as_a_child_process(tmp_path, monkeypatch):
     # ... and the source never replaces the process
     src = open(os.path.join(root, 'bench.py')).read()
     assert 'os.exec' not in src and 'execv' not in src.replace('never exec', '')
+
+
+def test_bench_leaves_the_extra_legs_to_full(monkeypatch):
+    """A plain `bench.py` run times the steps and prints the line; the legs that take runs of their own (rooflines, parity,
+    CPU baseline) come only with --full, and --no-extras / --no-cpu-baseline drop their parts of it."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert not bench.parse_args(['--gpus', '1', '--steps', '5', '--warmup', '2']).full
+    assert bench.parse_args(['--full']).full
+
+    ran = []
+    monkeypatch.setattr(bench, 'dominant_kernel_roofline', lambda b: ran.append('roofline') or {'frac': 0.5})
+    monkeypatch.setattr(bench, 'family_rooflines', lambda b: ran.append('by_time') or [])
+    monkeypatch.setattr(bench, 'head_roofline', lambda: ran.append('head') or {})
+    monkeypatch.setattr(bench, 'parity_vs_oracle', lambda m, base, reg: ran.append('parity') or {})
+    monkeypatch.setattr(bench, 'cpu_baseline', lambda base, reg: ran.append('cpu') or {'value': 5.0})
+    hg = build_mpii_pose_model(base='hg1', output_strat='dsnt', reg='js')
+
+    def legs(*argv, world=1, model=hg):
+        del ran[:]
+        out = bench.full_legs(bench.parse_args(['--full'] + list(argv)), model, 'hg1', 'js', 32, world, 1000.0)
+        return list(out), list(ran), out
+    keys, called, out = legs()
+    assert keys == ['roofline', 'head_roofline', 'parity', 'cpu_baseline', 'speedup_vs_cpu']
+    assert called == ['roofline', 'by_time', 'head', 'parity', 'cpu']
+    assert out['roofline']['by_time'] == [] and out['speedup_vs_cpu'] == 200.0
+    assert legs('--no-extras')[1] == ['cpu']
+    assert legs('--no-cpu-baseline')[1] == ['roofline', 'by_time', 'head', 'parity']
+    assert legs(world=2)[1] == ['roofline', 'by_time', 'head', 'parity']             # the CPU baseline is a 1-GPU figure
+    assert 'parity' not in legs(model=build_mpii_pose_model(base='resnet34', output_strat='dsnt'))[0]
