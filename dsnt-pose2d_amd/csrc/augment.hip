@@ -30,6 +30,23 @@
 // dsnt_augment_keypoints (data.py:150-196, fp64): part_coords = t . matrix . [x, y, 1] with t = R(rot)/scale . F(hflip),
 // joints permuted by the flip table under hflip (out[flip[j]] = in[j], as scatter_ does), part_mask permuted the same way
 // and, in train mode, multiplied by |coord| < 1; trans_m / trans_b = the 2x2 / translation part of inv(matrix) . inv(t).
+//
+// Gather variants (dsnt_augment_fwd_gather, dsnt_augment_fwd_pair_gather, dsnt_augment_keypoints_gather): the same
+// kernels instantiated with a Gather / KpGather argument.  Sample b reads row idx[b] of a resident pool of N samples
+// instead of row b of a contiguous batch, and draws with sample word b + draw_offset (offset 0: exactly
+// dsnt_augment_fwd's draw).  An index outside [0, N) reads nothing: that sample's input is NaN, its part_mask 0 and its
+// coordinates, matrices and normalize NaN, so the loss (or NanGuard) reports it.  The instantiations without the
+// argument are the kernels above, unchanged.
+//
+// dsnt_epoch_indices: out[i] = order(first + i), a bijection of [0, n) keyed by (seed, epoch); shuffle == 0 or n == 1:
+// the identity.  Construction (restated in numpy by tests/loader_ref.py):
+//   k = the smallest even number >= 2 with 2^k >= n; h = k / 2; mask = 2^h - 1.
+//   feistel(x): L = x >> h, Rt = x & mask; for r in 0..7: (L, Rt) = (Rt, L ^ (F_r(Rt) & mask)); return (L << h) | Rt,
+//     F_r(v) = word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter (v, epoch lo, epoch hi, 0x4F524400 + r).
+//     The counter's last word is the domain: the augmentation draw uses 0, 1, 2 there, so order and draw are
+//     independent streams of the same seed.
+//   order(p) = y, where y = feistel(p), then y = feistel(y) while y >= n (cycle-walking: the walk stays on p's cycle
+//     of the permutation of [0, 2^k), so it ends in [0, n); 2^k < 4n, about 4 steps or fewer expected).
 #include "common.h"
 #include <math.h>
 
@@ -64,11 +81,11 @@ __device__ inline double normal(uint32_t a, uint32_t b) {      // Box-Muller
 }
 __device__ inline double clip(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
 
-__device__ void draw_params(uint64_t seed, uint64_t step, int b, float& scale, float& rot, uint8_t& hflip, float gain[3]) {
+__device__ void draw_params(uint64_t seed, uint64_t step, uint32_t b, float& scale, float& rot, uint8_t& hflip, float gain[3]) {
     uint32_t r0[4], r1[4], r2[4];
-    Philox::gen(r0, seed, step, (uint32_t)b, 0);
-    Philox::gen(r1, seed, step, (uint32_t)b, 1);
-    Philox::gen(r2, seed, step, (uint32_t)b, 2);
+    Philox::gen(r0, seed, step, b, 0);
+    Philox::gen(r1, seed, step, b, 1);
+    Philox::gen(r2, seed, step, b, 2);
     scale = (float)exp2(clip(0.25 * normal(r0[0], r0[1]), -0.5, 0.5));
     rot = unit(r0[2]) <= 0.4 ? (float)clip(30.0 * normal(r1[0], r1[1]), -60.0, 60.0) : 0.f;
     hflip = unit(r0[3]) <= 0.5 ? 1 : 0;
@@ -84,22 +101,48 @@ struct SampleCoef {
     int c_side, off, rotate, hflip;
 };
 
+// The gather variants' extra kernel argument: sample b is row idx[b] of a pool of n rows and draws with sample word
+// b + draw_offset.  The kernels take it as an optional trailing parameter pack (`G... gather`, empty or one argument),
+// so the instantiations without it have exactly the signature, and the code, of the plain kernels.
+struct Gather {
+    const int64_t* idx;
+    int64_t n;
+    uint32_t draw_offset;
+};
+struct KpGather {
+    const int64_t* idx;
+    int64_t n;
+    const double* head_len;     // [n]
+    double* normalize;          // [B]: head_len[idx[b]]
+};
+template <typename T>
+__device__ inline const T& only(const T& t) { return t; }
+
 // PAIR (dsnt_augment_fwd_pair): `out` is [2B][3][S][S] and every finished pixel is also stored at column S-1-x of sample
 // B + b: the second half is exactly the first one mirrored (inference.py's reverse_tensor(input, -1)).
-template <bool PAIR>
+template <bool PAIR, typename... G>
 __global__ void __launch_bounds__(AUG_NT) augment_kernel(const uint8_t* __restrict__ src, int R, int S,
                                                          float* __restrict__ scale_p, float* __restrict__ rot_p,
                                                          uint8_t* __restrict__ hflip_p, float* __restrict__ gain_p,
                                                          int draw, uint64_t seed, uint64_t step,
                                                          const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                         float* __restrict__ out) {
+                                                         float* __restrict__ out, G... gather) {
+    constexpr bool GATHER = sizeof...(G) > 0;
     __shared__ SampleCoef sc;
     const int b = blockIdx.y;
+    uint32_t sample = (uint32_t)b;                    // the draw's sample word
+    int64_t row = 0;                                  // (gather) the pool row of sample b; -1: outside the pool
+    if constexpr (GATHER) {
+        const Gather g = only(gather...);
+        sample += g.draw_offset;
+        row = g.idx[b];
+        if (row < 0 || row >= g.n) row = -1;          // reads nothing; the sample's input becomes NaN below
+    }
     if (threadIdx.x == 0) {
         float scale, rot, gain[3];
         uint8_t hflip;
         if (draw) {
-            draw_params(seed, step, b, scale, rot, hflip, gain);
+            draw_params(seed, step, sample, scale, rot, hflip, gain);
             if (blockIdx.x == 0) {
                 scale_p[b] = scale; rot_p[b] = rot; hflip_p[b] = hflip;
                 for (int ch = 0; ch < 3; ++ch) gain_p[3 * b + ch] = gain[ch];
@@ -132,10 +175,22 @@ __global__ void __launch_bounds__(AUG_NT) augment_kernel(const uint8_t* __restri
     const int p = blockIdx.x * AUG_NT + threadIdx.x;
     if (p >= S * S) return;
     const int oy = p / S, ox = p - oy * S;
+    if constexpr (GATHER) {
+        if (row < 0) {
+            const float nan = __builtin_nanf("");
+            for (int half = 0; half < (PAIR ? 2 : 1); ++half) {
+                float* o = out + ((size_t)half * gridDim.y + b) * 3 * S * S + p;
+                o[0] = nan;
+                o[(size_t)S * S] = nan;
+                o[(size_t)2 * S * S] = nan;
+            }
+            return;
+        }
+    }
     const int c = sc.c_side, off = sc.off, flip = sc.hflip, rotate = sc.rotate;
     const int y0 = (int)(((long)oy * c) / S), y1 = (int)(((long)(oy + 1) * c + S - 1) / S);
     const int x0 = (int)(((long)ox * c) / S), x1 = (int)(((long)(ox + 1) * c + S - 1) / S);
-    const uint8_t* img = src + (size_t)b * R * R * 3;
+    const uint8_t* img = GATHER ? src + (size_t)row * R * R * 3 : src + (size_t)b * R * R * 3;
     const float g0 = sc.gain[0], g1 = sc.gain[1], g2 = sc.gain[2];
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
     for (int v = y0; v < y1; ++v) {
@@ -193,30 +248,52 @@ __global__ void __launch_bounds__(AUG_NT) augment_kernel(const uint8_t* __restri
     }
 }
 
+// G: empty, or one KpGather (dsnt_augment_keypoints_gather: the inputs are rows idx[b] of the pools).
+template <typename... G>
 __global__ void augment_keypoints_kernel(const double* __restrict__ matrix, const double* __restrict__ kp,
                                          const float* __restrict__ kmask, const float* __restrict__ scale_p,
                                          const float* __restrict__ rot_p, const uint8_t* __restrict__ hflip_p,
                                          const int64_t* __restrict__ flip_idx, int train, int B, int J,
                                          float* __restrict__ part_coords, float* __restrict__ part_mask,
-                                         double* __restrict__ trans_m, double* __restrict__ trans_b) {
+                                         double* __restrict__ trans_m, double* __restrict__ trans_b, G... gather) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * J) return;
     const int b = i / J, j = i - b * J;
+    constexpr bool GATHER = sizeof...(G) > 0;
     const double* m = matrix + 9 * b;
+    int64_t e = 0;                                    // (gather) the element of the pools: row idx[b], joint j
+    if constexpr (GATHER) {
+        const KpGather g = only(gather...);
+        const int64_t row = g.idx[b];
+        if (row < 0 || row >= g.n) {                  // reads nothing
+            const double nan = __builtin_nan("");
+            part_coords[2 * i] = part_coords[2 * i + 1] = (float)nan;
+            part_mask[i] = 0.f;
+            if (j == 0) {
+                for (int e = 0; e < 4; ++e) trans_m[4 * b + e] = nan;
+                trans_b[2 * b] = trans_b[2 * b + 1] = nan;
+                g.normalize[b] = nan;
+            }
+            return;
+        }
+        if (j == 0) g.normalize[b] = g.head_len[row];
+        m = matrix + 9 * row;
+        e = row * J + j;
+    }
     const double s = scale_p[b], rad = (double)rot_p[b] * (M_PI / 180.0);
     const double cs = cos(rad), sn = sin(rad);
     const bool flip = hflip_p[b] != 0;
     // t = [[cos/s, sin/s, 0], [-sin/s, cos/s, 0], [0, 0, 1]] . diag(flip ? -1 : 1, 1, 1)
     const double fx = flip ? -1.0 : 1.0;
     const double t00 = cs / s * fx, t01 = sn / s, t10 = -sn / s * fx, t11 = cs / s;
-    const double x = kp[2 * i], y = kp[2 * i + 1];
+    const double x = GATHER ? kp[2 * e] : kp[2 * i], y = GATHER ? kp[2 * e + 1] : kp[2 * i + 1];
     const double px = m[0] * x + m[1] * y + m[2], py = m[3] * x + m[4] * y + m[5];
     const double qx = t00 * px + t01 * py, qy = t10 * px + t11 * py;
     int jo = flip ? (int)flip_idx[j] : j;
     if (jo < 0 || jo >= J) jo = j;                   // (the binding passes a permutation of 0..J-1; never write outside the row)
     part_coords[2 * (b * J + jo)] = (float)qx;
     part_coords[2 * (b * J + jo) + 1] = (float)qy;
-    float mk = kmask[i];
+    float mk = GATHER ? kmask[e] : kmask[i];
     if (train && !(fabs(qx) < 1.0 && fabs(qy) < 1.0)) mk *= 0.f;
     part_mask[b * J + jo] = mk;
     if (j == 0) {
@@ -256,6 +333,38 @@ __global__ void __launch_bounds__(AUG_NT) pool_normalize_kernel(const float* __r
     out[i] = (s / (float)(y1 - y0) / (float)(x1 - x0) - mean[ch]) / stdv[ch];
 }
 
+// dsnt_epoch_indices (construction in the header comment).  h = half the Feistel width in bits; h == 0: the identity.
+constexpr int ORDER_NT = 256;
+constexpr int ORDER_ROUNDS = 8;
+constexpr uint32_t ORDER_DOMAIN = 0x4F524400u;   // Philox counter word 3; the augmentation draw uses 0, 1, 2
+
+__device__ inline uint64_t feistel(uint64_t x, int h, uint64_t seed, uint64_t epoch) {
+    const uint64_t mask = (1ULL << h) - 1;
+    uint64_t l = x >> h, r = x & mask;
+    for (int i = 0; i < ORDER_ROUNDS; ++i) {
+        uint32_t o[4];
+        Philox::gen(o, seed, epoch, (uint32_t)r, ORDER_DOMAIN + i);
+        const uint64_t t = l ^ (o[0] & mask);
+        l = r;
+        r = t;
+    }
+    return (l << h) | r;
+}
+
+__global__ void __launch_bounds__(ORDER_NT) epoch_indices_kernel(int64_t n, uint64_t seed, uint64_t epoch, int64_t first,
+                                                                 int64_t count, int h, int64_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * ORDER_NT + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t p = (uint64_t)(first + i);
+    if (h == 0) {
+        out[i] = (int64_t)p;
+        return;
+    }
+    uint64_t y = feistel(p, h, seed, epoch);
+    while (y >= (uint64_t)n) y = feistel(y, h, seed, epoch);      // cycle-walking: ends on p's cycle inside [0, n)
+    out[i] = (int64_t)y;
+}
+
 }  // namespace
 
 extern "C" int dsnt_augment_fwd(const uint8_t* src, int B, int R, int S, float* scale, float* rot_deg, uint8_t* hflip,
@@ -290,9 +399,72 @@ extern "C" int dsnt_augment_keypoints(const double* matrix, const double* keypoi
                  part_mask && trans_m && trans_b, DSNT_ERR_ARG, "dsnt_augment_keypoints: null pointer");
     DSNT_REQUIRE(B > 0 && J > 0 && (long)B * J <= (1L << 30), DSNT_ERR_SHAPE, "dsnt_augment_keypoints: bad shape B=%d J=%d",
                  B, J);
-    DSNT_LAUNCH(augment_keypoints_kernel, dim3((B * J + 255) / 256), dim3(256), 0, (hipStream_t)stream, matrix, keypoints,
-                keypoint_mask, scale, rot_deg, hflip, flip_idx, train, B, J, part_coords, part_mask, trans_m, trans_b);
+    DSNT_LAUNCH(augment_keypoints_kernel<>, dim3((B * J + 255) / 256), dim3(256), 0, (hipStream_t)stream, matrix,
+                keypoints, keypoint_mask, scale, rot_deg, hflip, flip_idx, train, B, J, part_coords, part_mask, trans_m,
+                trans_b);
     DSNT_CHECK_LAUNCH("dsnt_augment_keypoints");
+}
+
+template <bool PAIR>
+static int augment_fwd_gather(const char* name, const uint8_t* pool, int64_t N, const int64_t* idx, int B, int R, int S,
+                              float* scale, float* rot_deg, uint8_t* hflip, float* gain, int draw, uint64_t seed,
+                              uint64_t step, uint32_t draw_offset, const float* mean, const float* stdv, float* out,
+                              void* stream) {
+    DSNT_REQUIRE(pool && idx && scale && rot_deg && hflip && gain && mean && stdv && out, DSNT_ERR_ARG, "%s: null pointer",
+                 name);
+    DSNT_REQUIRE(N > 0 && B > 0 && B <= 65535 && R > 0 && R <= 8192 && S > 0 && S <= 4096, DSNT_ERR_SHAPE,
+                 "%s: bad shape N=%lld B=%d R=%d S=%d", name, (long long)N, B, R, S);
+    const Gather g{idx, N, draw_offset};
+    DSNT_LAUNCH(augment_kernel<PAIR>, dim3((S * S + AUG_NT - 1) / AUG_NT, B), dim3(AUG_NT), 0, (hipStream_t)stream, pool,
+                R, S, scale, rot_deg, hflip, gain, draw, seed, step, mean, stdv, out, g);
+    DSNT_CHECK_LAUNCH(name);
+}
+
+extern "C" int dsnt_augment_fwd_gather(const uint8_t* pool, int64_t N, const int64_t* idx, int B, int R, int S,
+                                       float* scale, float* rot_deg, uint8_t* hflip, float* gain, int draw,
+                                       uint64_t seed, uint64_t step, uint32_t draw_offset, const float* mean,
+                                       const float* stdv, float* out, void* stream) {
+    return augment_fwd_gather<false>("dsnt_augment_fwd_gather", pool, N, idx, B, R, S, scale, rot_deg, hflip, gain, draw,
+                                     seed, step, draw_offset, mean, stdv, out, stream);
+}
+
+extern "C" int dsnt_augment_fwd_pair_gather(const uint8_t* pool, int64_t N, const int64_t* idx, int B, int R, int S,
+                                            float* scale, float* rot_deg, uint8_t* hflip, float* gain, int draw,
+                                            uint64_t seed, uint64_t step, uint32_t draw_offset, const float* mean,
+                                            const float* stdv, float* out, void* stream) {
+    return augment_fwd_gather<true>("dsnt_augment_fwd_pair_gather", pool, N, idx, B, R, S, scale, rot_deg, hflip, gain,
+                                    draw, seed, step, draw_offset, mean, stdv, out, stream);
+}
+
+extern "C" int dsnt_augment_keypoints_gather(const double* matrix_pool, const double* kp_pool, const float* mask_pool,
+                                             const double* head_len_pool, int64_t N, const int64_t* idx, int B, int J,
+                                             const float* scale, const float* rot_deg, const uint8_t* hflip,
+                                             const int64_t* flip_idx, int train, float* part_coords, float* part_mask,
+                                             double* trans_m, double* trans_b, double* normalize, void* stream) {
+    DSNT_REQUIRE(matrix_pool && kp_pool && mask_pool && head_len_pool && idx && scale && rot_deg && hflip && flip_idx &&
+                 part_coords && part_mask && trans_m && trans_b && normalize, DSNT_ERR_ARG,
+                 "dsnt_augment_keypoints_gather: null pointer");
+    DSNT_REQUIRE(N > 0 && B > 0 && J > 0 && (long)B * J <= (1L << 30) && N <= (1LL << 40) / J, DSNT_ERR_SHAPE,
+                 "dsnt_augment_keypoints_gather: bad shape N=%lld B=%d J=%d", (long long)N, B, J);
+    const KpGather g{idx, N, head_len_pool, normalize};
+    DSNT_LAUNCH(augment_keypoints_kernel<KpGather>, dim3((B * J + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                matrix_pool, kp_pool, mask_pool, scale, rot_deg, hflip, flip_idx, train, B, J, part_coords, part_mask,
+                trans_m, trans_b, g);
+    DSNT_CHECK_LAUNCH("dsnt_augment_keypoints_gather");
+}
+
+extern "C" int dsnt_epoch_indices(int64_t n, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int shuffle,
+                                  int64_t* out, void* stream) {
+    DSNT_REQUIRE(out, DSNT_ERR_ARG, "dsnt_epoch_indices: null pointer");
+    DSNT_REQUIRE(n > 0 && n <= (1LL << 62) && first >= 0 && count > 0 && count <= n - first &&
+                 count <= (int64_t)INT32_MAX * ORDER_NT, DSNT_ERR_SHAPE,
+                 "dsnt_epoch_indices: bad range n=%lld first=%lld count=%lld", (long long)n, (long long)first,
+                 (long long)count);
+    int k = 2;
+    while ((1ULL << k) < (uint64_t)n) k += 2;
+    DSNT_LAUNCH(epoch_indices_kernel, dim3((unsigned)((count + ORDER_NT - 1) / ORDER_NT)), dim3(ORDER_NT), 0,
+                (hipStream_t)stream, n, seed, epoch, first, count, shuffle != 0 && n > 1 ? k / 2 : 0, out);
+    DSNT_CHECK_LAUNCH("dsnt_epoch_indices");
 }
 
 extern "C" int dsnt_pool_normalize(const float* x, int N, int C, int H, int W, int S, const float* mean, const float* stdv,

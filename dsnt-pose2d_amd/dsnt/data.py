@@ -9,6 +9,10 @@ keypoints, their mask and the back-projection, in two launches on the current st
 Reading the MPII files and parsing its annotations stay out of scope: the boundary is "source crops already
 on the device".  The exact transform (Pillow's rotation, torchvision 0.2.0's centre crop) is documented in
 `csrc/augment.hip`.
+
+`DeviceDataset` keeps a whole training set of crops resident on the device, and `EpochLoader` runs shuffled epochs
+over it: the order (a counter-based permutation), the gather and the transform are all device launches, so an epoch
+needs no host work (the reference's `DataLoader(train_data, batch_size, shuffle=True, num_workers=4)`).
 """
 import numpy as np
 import torch
@@ -143,7 +147,6 @@ class DeviceAugment:
         normalize = _check('head_lengths', head_lengths.to(torch.float64), torch.float64, (B,))
         if src_u8.device != keypoints.device or keypoints.device != matrix.device or matrix.device != kmask.device:
             raise RuntimeError('dsnt: DeviceAugment inputs must be on one device')
-        mean, std, flip = self._consts(dev)
         draw = 0
         if params is not None:
             scale = _check('params.scale', params['scale'], torch.float32, (B,)).clone()
@@ -161,27 +164,312 @@ class DeviceAugment:
             rot = torch.zeros(B, dtype=torch.float32, device=dev)
             hflip = torch.zeros(B, dtype=torch.uint8, device=dev)
             gain = torch.ones(B, 3, dtype=torch.float32, device=dev)
-        if J != flip.numel() and (draw or params is not None):
+        sample = self._launch(src_u8, keypoints, kmask, matrix, B, step, (draw, scale, rot, hflip, gain), flip_pair,
+                              params is not None)
+        sample['normalize'] = normalize
+        sample['hflip'] = hflip.bool()
+        return sample
+
+    def _flip_table(self, J, flips, dev):
+        """The joint permutation of a flip; `flips`: some sample may be flipped (drawn or given parameters)."""
+        flip = self._consts(dev)[2]
+        if J == flip.numel():
+            return flip
+        if flips:
             raise RuntimeError('dsnt: with flips the keypoints need the %d MPII joints (inference.HFLIP_INDICES), got %d'
                                % (flip.numel(), J))
-        if J != flip.numel():
-            flip = torch.arange(J, device=dev)       # never applied: no sample is flipped
-        S = self.image_specs.size
+        key = (dev, J)
+        if key not in self._dev:
+            self._dev[key] = torch.arange(J, device=dev)       # never applied: no sample is flipped
+        return self._dev[key]
+
+    def _launch(self, crops, keypoints, kmask, matrix, B, step, p, flip_pair, given, gather=None):
+        """The image and keypoint launches of one batch, shared by `__call__` and `EpochLoader`.  `p` = (draw, scale, rot,
+        hflip, gain); `given`: the parameters were passed in.  `gather` = (idx, head_lengths, draw_offset): sample b is
+        row idx[b] of the pools `crops`, `keypoints`, `kmask`, `matrix`, `head_lengths`, and `normalize` is written
+        too.  Returns the sample dict; the caller fills in `hflip` (and, batched, `normalize`)."""
+        dev = crops.device
+        R, J, S = crops.shape[1], keypoints.shape[1], self.image_specs.size
+        draw, scale, rot, hflip, gain = p
+        mean, std, _ = self._consts(dev)
+        flip = self._flip_table(J, draw or given, dev)
         pair = torch.empty(2 * B if flip_pair else B, 3, S, S, dtype=torch.float32, device=dev)
-        _lib.call('dsnt_augment_fwd_pair' if flip_pair else 'dsnt_augment_fwd', _lib.ptr(src_u8), B, R, S, _lib.ptr(scale),
-                  _lib.ptr(rot), _lib.ptr(hflip), _lib.ptr(gain), draw, self.seed & (2 ** 64 - 1),
-                  int(step) & (2 ** 64 - 1), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(pair))
-        out = pair[:B]
+        name = 'dsnt_augment_fwd_pair' if flip_pair else 'dsnt_augment_fwd'
+        drawn = (B, R, S, _lib.ptr(scale), _lib.ptr(rot), _lib.ptr(hflip), _lib.ptr(gain), draw,
+                 self.seed & (2 ** 64 - 1), int(step) & (2 ** 64 - 1))
+        if gather is None:
+            _lib.call(name, _lib.ptr(crops), *drawn, _lib.ptr(mean), _lib.ptr(std), _lib.ptr(pair))
+        else:
+            idx, head_lengths, draw_offset = gather
+            N = crops.shape[0]
+            _lib.call(name + '_gather', _lib.ptr(crops), N, _lib.ptr(idx), *drawn, draw_offset, _lib.ptr(mean),
+                      _lib.ptr(std), _lib.ptr(pair))
         pc = torch.empty(B, J, 2, dtype=torch.float32, device=dev)
         pm = torch.empty(B, J, dtype=torch.float32, device=dev)
         tm = torch.empty(B, 2, 2, dtype=torch.float64, device=dev)
         tb = torch.empty(B, 1, 2, dtype=torch.float64, device=dev)
-        _lib.call('dsnt_augment_keypoints', _lib.ptr(matrix), _lib.ptr(keypoints), _lib.ptr(kmask), B, J,
-                  _lib.ptr(scale), _lib.ptr(rot), _lib.ptr(hflip), _lib.ptr(flip), 1 if self.train else 0,
-                  _lib.ptr(pc), _lib.ptr(pm), _lib.ptr(tm), _lib.ptr(tb))
-        sample = {'normalize': normalize, 'transform_b': tb, 'transform_m': tm, 'input': out, 'part_mask': pm,
-                  'part_coords': pc, 'hflip': hflip.bool(),
-                  'params': {'scale': scale, 'rot': rot, 'hflip': hflip, 'gain': gain}}
+        kp_args = (_lib.ptr(scale), _lib.ptr(rot), _lib.ptr(hflip), _lib.ptr(flip), 1 if self.train else 0,
+                   _lib.ptr(pc), _lib.ptr(pm), _lib.ptr(tm), _lib.ptr(tb))
+        normalize = None
+        if gather is None:
+            _lib.call('dsnt_augment_keypoints', _lib.ptr(matrix), _lib.ptr(keypoints), _lib.ptr(kmask), B, J, *kp_args)
+        else:
+            normalize = torch.empty(B, dtype=torch.float64, device=dev)
+            _lib.call('dsnt_augment_keypoints_gather', _lib.ptr(matrix), _lib.ptr(keypoints), _lib.ptr(kmask),
+                      _lib.ptr(head_lengths), N, _lib.ptr(idx), B, J, *kp_args, _lib.ptr(normalize))
+        sample = {'normalize': normalize, 'transform_b': tb, 'transform_m': tm, 'input': pair[:B], 'part_mask': pm,
+                  'part_coords': pc, 'hflip': None, 'params': {'scale': scale, 'rot': rot, 'hflip': hflip, 'gain': gain}}
         if flip_pair:
             sample['input_pair'] = pair
         return sample
+
+
+_FIELDS = ('crops', 'keypoints', 'keypoint_mask', 'matrix', 'head_lengths')
+_DTYPES = (torch.uint8, torch.float64, torch.float32, torch.float64, torch.float64)
+_STAGE_BYTES = 64 << 20
+
+
+def _host_array(name, a):
+    """A numpy array (or memmap) of `a`, or `a` itself if it is already a device tensor.  No copy of a host array."""
+    if isinstance(a, torch.Tensor):
+        return a if a.is_cuda else a.numpy()
+    if isinstance(a, np.ndarray):
+        return a
+    raise RuntimeError('dsnt: %s must be a numpy array or a tensor, got %s' % (name, type(a)))
+
+
+def _dataset_shapes(crops, keypoints, keypoint_mask, matrix, head_lengths):
+    """(N, R, J) of a training set, or an error naming the first field with a wrong shape."""
+    if crops.ndim != 4 or crops.shape[1] != crops.shape[2] or crops.shape[3] != 3 or crops.shape[0] < 1:
+        raise RuntimeError('dsnt: crops must be [N, R, R, 3] (HWC crops, N >= 1), got %s' % (tuple(crops.shape),))
+    N, R = crops.shape[0], crops.shape[1]
+    J = keypoints.shape[1] if keypoints.ndim == 3 else -1
+    for name, t, shape in (('keypoints', keypoints, (N, J, 2)), ('keypoint_mask', keypoint_mask, (N, J)),
+                           ('matrix', matrix, (N, 3, 3)), ('head_lengths', head_lengths, (N,))):
+        if tuple(t.shape) != shape or J < 1:
+            raise RuntimeError('dsnt: %s must have shape %s, got %s' % (name, shape, tuple(t.shape)))
+    return N, R, J
+
+
+class DeviceDataset:
+    """A training set resident on one device: the pool `EpochLoader` gathers batches from.
+
+    Fields (rows = samples): `crops` uint8 `[N, R, R, 3]` (what `DeviceAugment` takes as `src_u8`), `keypoints` float64
+    `[N, J, 2]`, `keypoint_mask` float32 `[N, J]`, `matrix` float64 `[N, 3, 3]`, `head_lengths` float64 `[N]`.  The
+    constructor takes device tensors of exactly these dtypes; `from_arrays` uploads host data in chunks, `save` / `load`
+    keep a packed set as plain `.npy` files.  Only shapes, dtypes and devices are checked.  The full MPII crop set at
+    R = 384 (25k samples) is 11 GB.
+    """
+
+    def __init__(self, crops, keypoints, keypoint_mask, matrix, head_lengths):
+        ts = (crops, keypoints, keypoint_mask, matrix, head_lengths)
+        for name, t in zip(_FIELDS, ts):
+            if not isinstance(t, torch.Tensor):
+                raise RuntimeError('dsnt: DeviceDataset.%s must be a tensor (use DeviceDataset.from_arrays for host data)'
+                                   % name)
+        N, R, J = _dataset_shapes(*ts)
+        for name, t, dtype in zip(_FIELDS, ts, _DTYPES):
+            if t.dtype != dtype:
+                raise RuntimeError('dsnt: %s must be %s, got %s' % (name, dtype, t.dtype))
+        for t in ts:
+            _lib.ptr(t)          # refuses CPU and non-contiguous tensors
+        if any(t.device != crops.device for t in ts):
+            raise RuntimeError('dsnt: DeviceDataset fields must be on one device')
+        self.crops, self.keypoints, self.keypoint_mask, self.matrix, self.head_lengths = ts
+
+    def __len__(self):
+        return self.crops.shape[0]
+
+    @property
+    def device(self):
+        return self.crops.device
+
+    @property
+    def nbytes(self):
+        return sum(getattr(self, f).numel() * getattr(self, f).element_size() for f in _FIELDS)
+
+    @classmethod
+    def from_arrays(cls, crops, keypoints, keypoint_mask, matrix, head_lengths, device='cuda', chunk_bytes=_STAGE_BYTES):
+        """Upload a training set from numpy arrays, `np.load(..., mmap_mode='r')` memmaps or CPU tensors.  `crops` must
+        be uint8; the other fields are converted to their dtype (`keypoint_mask` may be bool or integer).  Every field
+        goes through one pinned staging buffer of at most `chunk_bytes`, a chunk of rows at a time, so the host never
+        holds a second full copy.  Synchronises with the device (it is the one-off packing step)."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('dsnt: DeviceDataset lives on a HIP device, not %s (no CPU fallback)' % device)
+        arrays = [_host_array(n, a) for n, a in zip(_FIELDS, (crops, keypoints, keypoint_mask, matrix, head_lengths))]
+        _dataset_shapes(*arrays)
+        for name, a in zip(_FIELDS, arrays):
+            kind = _kind(a)
+            if name == 'crops' and str(a.dtype).replace('torch.', '') != 'uint8':
+                raise RuntimeError('dsnt: crops must be uint8, got %s' % a.dtype)
+            if name in ('keypoints', 'matrix', 'head_lengths') and kind != 'f':
+                raise RuntimeError('dsnt: %s must be floating point, got %s' % (name, a.dtype))
+            if name == 'keypoint_mask' and kind not in 'biuf':
+                raise RuntimeError('dsnt: keypoint_mask must be real or bool, got %s' % a.dtype)
+        stage = _stage(arrays, chunk_bytes)
+        with torch.cuda.device(device):
+            out = [_upload(a, dtype, device, stage) for a, dtype in zip(arrays, _DTYPES)]
+        return cls(*out)
+
+    def save(self, directory):
+        """Write the fields as `<directory>/<field>.npy` (through one pinned staging buffer; `load` reads them back)."""
+        import os
+        os.makedirs(directory, exist_ok=True)
+        stage = _stage([getattr(self, n) for n in _FIELDS], _STAGE_BYTES)
+        for name in _FIELDS:
+            t = getattr(self, name)
+            mm = np.lib.format.open_memmap(os.path.join(directory, name + '.npy'), mode='w+',
+                                           dtype=str(t.dtype).replace('torch.', ''), shape=tuple(t.shape))
+            rows = _chunk_rows(t, stage)
+            for r0 in range(0, len(t), rows):
+                part = t[r0:r0 + rows]
+                buf = stage[:part.numel() * t.element_size()].view(t.dtype).view(part.shape)
+                buf.copy_(part)                                  # synchronous: the device has written it on return
+                mm[r0:r0 + rows] = buf.numpy()
+            mm.flush()
+            del mm
+
+    @classmethod
+    def load(cls, directory, device='cuda', chunk_bytes=_STAGE_BYTES):
+        """A set written by `save`: the `.npy` files are memory-mapped and uploaded in chunks."""
+        import os
+        arrays = [np.load(os.path.join(directory, n + '.npy'), mmap_mode='r') for n in _FIELDS]
+        return cls.from_arrays(*arrays, device=device, chunk_bytes=chunk_bytes)
+
+
+def _kind(a):
+    """numpy's dtype kind ('b', 'i', 'u', 'f', ...) of an array or a tensor."""
+    if isinstance(a, torch.Tensor):
+        if a.dtype == torch.bool:
+            return 'b'
+        return 'f' if a.dtype.is_floating_point else 'c' if a.dtype.is_complex else 'u' if a.dtype == torch.uint8 else 'i'
+    return a.dtype.kind
+
+
+def _stage(arrays, chunk_bytes):
+    """The one pinned staging buffer of an upload or a save: at most `chunk_bytes`, at least one row (8-byte
+    elements) of every field."""
+    row = max(int(np.prod(a.shape[1:], dtype=np.int64)) * 8 for a in arrays)
+    return torch.empty(max(row, min(int(chunk_bytes), row * len(arrays[0]))), dtype=torch.uint8, pin_memory=True)
+
+
+def _chunk_rows(t, stage):
+    row = max(1, int(np.prod(t.shape[1:], dtype=np.int64))) * t.element_size()
+    return max(1, stage.numel() // row)
+
+
+def _upload(a, dtype, device, stage):
+    if isinstance(a, torch.Tensor):                    # already on a device
+        return a.to(device=device, dtype=dtype).contiguous()
+    dst = torch.empty(a.shape, dtype=dtype, device=device)
+    rows = _chunk_rows(dst, stage)
+    for r0 in range(0, len(a), rows):
+        part = a[r0:r0 + rows]
+        buf = stage[:part.size * dst.element_size()].view(dtype).view(part.shape)
+        np.copyto(buf.numpy(), part, casting='unsafe')
+        dst[r0:r0 + len(part)].copy_(buf, non_blocking=True)
+        torch.cuda.current_stream().synchronize()      # the staging buffer is reused by the next chunk
+    return dst
+
+
+class EpochLoader:
+    """Epochs of `DeviceAugment` samples gathered from a `DeviceDataset`, with no host work per batch.
+
+    `EpochLoader(dataset, batch_size, augment, seed=0, shuffle=True, drop_last=False, rank=0, world_size=1,
+    flip_pair=False)`.  Iterating yields the rest of the current epoch (then moves to the next), as the reference's
+    `DataLoader(..., shuffle=True)` does.  Each sample is `DeviceAugment`'s dict (same keys and dtypes; `input_pair`
+    with `flip_pair`) plus `index`, int64 `[B]`, the dataset rows used.  A batch is three launches on the current
+    stream: the indices (`dsnt_epoch_indices`), the image and the keypoints (the `_gather` kernels, which read the
+    rows directly from the pool).  Nothing synchronises with the host and nothing crop-sized is allocated.
+
+    Order: position p of epoch e is `order(p)`, a bijection of [0, N) keyed by (`seed`, e), computed on the device
+    (`csrc/augment.hip`); `shuffle=False` keeps dataset order.  Augmentation: step `e * len(self) + b` of `augment`
+    (keyed by `augment.seed`), so resuming at (epoch, batch) reproduces the batch.  `drop_last=False` keeps a final
+    partial batch.  With `world_size` W > 1 (`drop_last` required), rank r takes positions
+    `[(s*W + r)*B, (s*W + r + 1)*B)` of the epoch's order at its batch s and draws with sample offset r*B: the ranks
+    shard one epoch without communicating.  With `use_aug=False` the identity parameters are shared read-only
+    tensors.
+    """
+
+    def __init__(self, dataset, batch_size, augment, seed=0, shuffle=True, drop_last=False, rank=0, world_size=1,
+                 flip_pair=False):
+        if not isinstance(dataset, DeviceDataset):
+            raise RuntimeError('dsnt: EpochLoader needs a DeviceDataset, got %s' % type(dataset))
+        if not isinstance(augment, DeviceAugment):
+            raise RuntimeError('dsnt: EpochLoader needs a DeviceAugment, got %s' % type(augment))
+        B, W, r, n = int(batch_size), int(world_size), int(rank), len(dataset)
+        if B < 1 or B > 65535:
+            raise RuntimeError('dsnt: batch_size must be in [1, 65535], got %d' % B)
+        if W < 1 or not 0 <= r < W:
+            raise RuntimeError('dsnt: need 0 <= rank < world_size, got rank %d of %d' % (r, W))
+        if W > 1 and not drop_last:
+            raise RuntimeError('dsnt: world_size > 1 needs drop_last=True (every rank takes whole batches)')
+        if drop_last and B * W > n:
+            raise RuntimeError('dsnt: drop_last with batch_size %d x world_size %d > %d samples leaves no batch'
+                               % (B, W, n))
+        if r * B >= 2 ** 32:
+            raise RuntimeError('dsnt: rank * batch_size must be < 2^32 (the draw offset)')
+        augment._flip_table(dataset.keypoints.shape[1], augment.use_aug, dataset.device)    # refuses J != 16 with flips
+        self.dataset, self.batch_size, self.augment = dataset, B, augment
+        self.seed, self.shuffle, self.drop_last = int(seed), bool(shuffle), bool(drop_last)
+        self.rank, self.world_size, self.flip_pair = r, W, bool(flip_pair)
+        self.epoch, self.batch = 0, 0
+        self._identity = {}
+
+    def __len__(self):
+        """Batches per epoch of this rank."""
+        n, B = len(self.dataset), self.batch_size
+        return n // (B * self.world_size) if self.drop_last else (n + B - 1) // B
+
+    def set_epoch(self, epoch):
+        self.epoch, self.batch = int(epoch), 0
+
+    def state_dict(self):
+        """Where iteration resumes: `batch` is the next batch of `epoch` to yield."""
+        return {'epoch': self.epoch, 'batch': self.batch, 'seed': self.seed}
+
+    def load_state_dict(self, state):
+        self.epoch, self.batch, self.seed = int(state['epoch']), int(state['batch']), int(state['seed'])
+
+    def _order(self, epoch, first, count):
+        idx = torch.empty(count, dtype=torch.int64, device=self.dataset.device)
+        _lib.call('dsnt_epoch_indices', len(self.dataset), self.seed & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), first,
+                  count, 1 if self.shuffle else 0, _lib.ptr(idx))
+        return idx
+
+    def indices(self, epoch=None):
+        """The order of `epoch` (default: the current one) over all ranks, int64 `[N]` on the device."""
+        return self._order(self.epoch if epoch is None else epoch, 0, len(self.dataset))
+
+    def _params(self, B, dev):
+        if self.augment.use_aug:
+            return (1, torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
+                    torch.empty(B, dtype=torch.uint8, device=dev), torch.empty(B, 3, dtype=torch.float32, device=dev))
+        p = self._identity.get(B)
+        if p is None:                                      # read by the kernels, never written (draw == 0)
+            p = self._identity[B] = (0, torch.ones(B, dtype=torch.float32, device=dev),
+                                     torch.zeros(B, dtype=torch.float32, device=dev),
+                                     torch.zeros(B, dtype=torch.uint8, device=dev),
+                                     torch.ones(B, 3, dtype=torch.float32, device=dev))
+        return p
+
+    def _batch(self, epoch, s):
+        d, B, W, r = self.dataset, self.batch_size, self.world_size, self.rank
+        first = (s * W + r) * B
+        count = min(B, len(d) - first)
+        idx = self._order(epoch, first, count)
+        p = self._params(count, d.device)
+        sample = self.augment._launch(d.crops, d.keypoints, d.keypoint_mask, d.matrix, count, epoch * len(self) + s, p,
+                                      self.flip_pair, False, gather=(idx, d.head_lengths, r * B))
+        sample['hflip'] = p[3].view(torch.bool)
+        sample['index'] = idx
+        return sample
+
+    def __iter__(self):
+        while self.batch < len(self):
+            s = self.batch
+            sample = self._batch(self.epoch, s)
+            self.batch = s + 1
+            yield sample
+        self.epoch, self.batch = self.epoch + 1, 0

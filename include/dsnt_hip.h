@@ -743,6 +743,29 @@ int dsnt_augment_keypoints(const double* matrix, const double* keypoints, const 
                            const float* scale, const float* rot_deg, const uint8_t* hflip, const int64_t* flip_idx,
                            int train, float* part_coords, float* part_mask, double* trans_m, double* trans_b,
                            void* stream);
+/* Gather variants for a device-resident training set (dsnt.data.DeviceDataset / EpochLoader).  dsnt_version() >= 118.
+ * dsnt_augment_fwd_gather / _pair_gather: dsnt_augment_fwd / _pair where sample b is row idx[b] (int64 [B]) of pool uint8
+ * [N][R][R][3], drawn (draw != 0) with Philox sample word b + draw_offset (0: exactly dsnt_augment_fwd's draw; rank r of W
+ * passes r * B).  An index outside [0, N) reads nothing and makes that sample's input NaN. */
+int dsnt_augment_fwd_gather(const uint8_t* pool, int64_t N, const int64_t* idx, int B, int R, int S, float* scale,
+                            float* rot_deg, uint8_t* hflip, float* gain, int draw, uint64_t seed, uint64_t step,
+                            uint32_t draw_offset, const float* mean, const float* stdv, float* out, void* stream);
+int dsnt_augment_fwd_pair_gather(const uint8_t* pool, int64_t N, const int64_t* idx, int B, int R, int S, float* scale,
+                                 float* rot_deg, uint8_t* hflip, float* gain, int draw, uint64_t seed, uint64_t step,
+                                 uint32_t draw_offset, const float* mean, const float* stdv, float* out, void* stream);
+/* dsnt_augment_keypoints on rows idx[b] of matrix_pool f64 [N][3][3], kp_pool f64 [N][J][2], mask_pool f32 [N][J]; also
+ * writes normalize f64 [B] = head_len_pool[idx[b]] (f64 [N]).  An index outside [0, N) reads nothing: part_mask 0,
+ * part_coords, trans_m, trans_b and normalize NaN. */
+int dsnt_augment_keypoints_gather(const double* matrix_pool, const double* kp_pool, const float* mask_pool,
+                                  const double* head_len_pool, int64_t N, const int64_t* idx, int B, int J,
+                                  const float* scale, const float* rot_deg, const uint8_t* hflip, const int64_t* flip_idx,
+                                  int train, float* part_coords, float* part_mask, double* trans_m, double* trans_b,
+                                  double* normalize, void* stream);
+/* out int64 [count] = order(first + i): a bijection of [0, n) keyed by (seed, epoch), an 8-round Feistel network of
+ * Philox4x32-10 round functions over 2^k >= n with cycle-walking (construction in csrc/augment.hip); shuffle == 0: the
+ * identity.  Needs 0 <= first, 0 < count <= n - first. */
+int dsnt_epoch_indices(int64_t n, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int shuffle, int64_t* out,
+                       void* stream);
 /* data.py:38-56 (ImageSpecs.convert) on a float image: x f32 [N][C][H][W] -> out f32 [N][C][S][S] =
  * (adaptive_avg_pool2d(x, S) - mean[c]) / stdv[c]; mean, stdv [C] (device). */
 int dsnt_pool_normalize(const float* x, int N, int C, int H, int W, int S, const float* mean, const float* stdv,
