@@ -47,6 +47,18 @@
 //     independent streams of the same seed.
 //   order(p) = y, where y = feistel(p), then y = feistel(y) while y >= n (cycle-walking: the walk stays on p's cycle
 //     of the permutation of [0, 2^k), so it ends in [0, n); 2^k < 4n, about 4 steps or fewer expected).
+//
+// dsnt_crop_affine: R x R crops of full images, bit for bit Pillow's
+//   Image.fromarray(img).transform((R, R), Image.AFFINE, (a, b, c, d, e, f), Image.BILINEAR)
+// with the coefficients of the bounding-box matrix M (image pixels -> normalised crop coordinates in [-1, 1]^2; crop pixel
+// centres at n = 2(x + .5)/R - 1).  inv = inverse3(M), the keypoints kernel's inverse, then in fp64 and in this order:
+//   a = 2*inv[0]/R, b = 2*inv[1]/R, c = inv[2] - inv[0] - inv[1];  d = 2*inv[3]/R, e = 2*inv[4]/R, f = inv[5] - inv[3] - inv[4].
+// Pillow samples crop pixel (x, y) at xin = a*(x+.5) + b*(y+.5) + c, yin = d*(x+.5) + e*(y+.5) + f with the bilinear rule
+// of step 2 above (DSNT_BILINEAR_RGB), black outside the image.  Images come from a ragged pool (one uint8 HWC buffer,
+// byte offset and (h, w) per image).  A sample whose index lies outside [0, N), whose image record does not fit the pool
+// (a side outside [1, 16384], or bytes outside it) or whose det(M) is 0 or not finite reads nothing: its crop is zero and
+// its valid byte 0.  Stores: a thread packs 4 pixels (12 bytes) into three dword stores, so a wave writes 768
+// contiguous bytes; odd R (a crop not dword-aligned) and a crop's last partial group store bytes.
 #include "common.h"
 #include <math.h>
 
@@ -94,6 +106,52 @@ __device__ void draw_params(uint64_t seed, uint64_t step, uint32_t b, float& sca
 
 // Pillow's rounding of the rotation coefficients: round(x, 15)
 __device__ inline double round15(double x) { return rint(x * 1e15) / 1e15; }
+
+// inv = inverse of the row-major 3 x 3 matrix m by the adjugate over the determinant; returns the determinant.  The one
+// inverse of a bounding-box matrix: the keypoints kernel's back-projection and the crop kernel's sampling map both use it.
+__device__ __forceinline__ double inverse3(const double* m, double inv[9]) {
+    const double a00 = m[4] * m[8] - m[5] * m[7], a01 = m[2] * m[7] - m[1] * m[8], a02 = m[1] * m[5] - m[2] * m[4];
+    const double a10 = m[5] * m[6] - m[3] * m[8], a11 = m[0] * m[8] - m[2] * m[6], a12 = m[2] * m[3] - m[0] * m[5];
+    const double a20 = m[3] * m[7] - m[4] * m[6], a21 = m[1] * m[6] - m[0] * m[7], a22 = m[0] * m[4] - m[1] * m[3];
+    const double det = m[0] * a00 + m[1] * a10 + m[2] * a20;
+    inv[0] = a00 / det; inv[1] = a01 / det; inv[2] = a02 / det;
+    inv[3] = a10 / det; inv[4] = a11 / det; inv[5] = a12 / det;
+    inv[6] = a20 / det; inv[7] = a21 / det; inv[8] = a22 / det;
+    return det;
+}
+
+// Pillow's bilinear sampler (bilinear_filter32RGB) at (XIN, YIN) of a W x H HWC uint8 image IMG: outside [0, W) x [0, H)
+// it leaves q0..q2 as they are (the caller's black); inside, taps at floor(xin - .5), floor(yin - .5) and +1, clamped
+// to the image (the second row only where it exists, else v2 = v1), lerped in fp64 along x then y (a + (b - a) * t) and
+// truncated.  FLIP != 0: the taps of the image mirrored left-right.  A statement macro, not a function: as an inlined
+// function the row address of augment_kernel compiled to different instructions, and augment_kernel keeps exactly the
+// code it had before the crop kernel shared the sampler (hipcc -S).
+#define DSNT_BILINEAR_RGB(IMG, W, H, XIN, YIN, FLIP, q0, q1, q2)                                  \
+    do {                                                                                          \
+        double xin = (XIN), yin = (YIN);                                                          \
+        if (xin >= 0.0 && xin < (W) && yin >= 0.0 && yin < (H)) {                                  \
+            xin -= 0.5;                                                                           \
+            yin -= 0.5;                                                                           \
+            const double fx = floor(xin), fy = floor(yin);                                        \
+            const double dx = xin - fx, dy = yin - fy;                                            \
+            const int xi = (int)fx, yi = (int)fy;                                                 \
+            int xa = min(max(xi, 0), (W) - 1), xb = min(max(xi + 1, 0), (W) - 1);                 \
+            if (FLIP) { xa = (W) - 1 - xa; xb = (W) - 1 - xb; }     /* taps of the flipped image */ \
+            const int ya = min(max(yi, 0), (H) - 1);                                              \
+            const bool has2 = yi + 1 >= 0 && yi + 1 < (H);          /* Pillow: else v2 = v1 */    \
+            const uint8_t* ra = (IMG) + (size_t)ya * (W) * 3;                                     \
+            const uint8_t* rb = has2 ? (IMG) + (size_t)(yi + 1) * (W) * 3 : ra;                   \
+            int q[3];                                                                             \
+            for (int ch = 0; ch < 3; ++ch) {                                                      \
+                const double a0 = ra[xa * 3 + ch], a1 = ra[xb * 3 + ch];                          \
+                const double v1 = a0 + (a1 - a0) * dx;                                            \
+                const double b0 = rb[xa * 3 + ch], b1 = rb[xb * 3 + ch];                          \
+                const double v2 = has2 ? b0 + (b1 - b0) * dx : v1;                                \
+                q[ch] = (int)(v1 + (v2 - v1) * dy);                                               \
+            }                                                                                     \
+            q0 = q[0]; q1 = q[1]; q2 = q[2];                                                      \
+        }                                                                                         \
+    } while (0)
 
 struct SampleCoef {
     double a, b, c, d, e, f;   // inverse rotation (Pillow's affine data)
@@ -204,30 +262,8 @@ __global__ void __launch_bounds__(AUG_NT) augment_kernel(const uint8_t* __restri
                     q0 = px[0]; q1 = px[1]; q2 = px[2];
                 } else {
                     const double xo = X + 0.5, yo = Y + 0.5;
-                    double xin = sc.a * xo + sc.b * yo + sc.c;
-                    double yin = sc.d * xo + sc.e * yo + sc.f;
-                    if (xin >= 0.0 && xin < R && yin >= 0.0 && yin < R) {
-                        xin -= 0.5;
-                        yin -= 0.5;
-                        const double fx = floor(xin), fy = floor(yin);
-                        const double dx = xin - fx, dy = yin - fy;
-                        const int xi = (int)fx, yi = (int)fy;
-                        int xa = min(max(xi, 0), R - 1), xb = min(max(xi + 1, 0), R - 1);
-                        if (flip) { xa = R - 1 - xa; xb = R - 1 - xb; }        // taps of the flipped image
-                        const int ya = min(max(yi, 0), R - 1);
-                        const bool has2 = yi + 1 >= 0 && yi + 1 < R;           // Pillow: else v2 = v1
-                        const uint8_t* ra = img + (size_t)ya * R * 3;
-                        const uint8_t* rb = has2 ? img + (size_t)(yi + 1) * R * 3 : ra;
-                        int q[3];
-                        for (int ch = 0; ch < 3; ++ch) {
-                            const double a0 = ra[xa * 3 + ch], a1 = ra[xb * 3 + ch];
-                            const double v1 = a0 + (a1 - a0) * dx;
-                            const double b0 = rb[xa * 3 + ch], b1 = rb[xb * 3 + ch];
-                            const double v2 = has2 ? b0 + (b1 - b0) * dx : v1;
-                            q[ch] = (int)(v1 + (v2 - v1) * dy);
-                        }
-                        q0 = q[0]; q1 = q[1]; q2 = q[2];
-                    }
+                    DSNT_BILINEAR_RGB(img, R, R, sc.a * xo + sc.b * yo + sc.c, sc.d * xo + sc.e * yo + sc.f, flip, q0,
+                                      q1, q2);
                 }
             }
             s0 += fminf(fmaxf(((float)q0 / 255.f) * g0, 0.f), 1.f);
@@ -297,13 +333,8 @@ __global__ void augment_keypoints_kernel(const double* __restrict__ matrix, cons
     if (train && !(fabs(qx) < 1.0 && fabs(qy) < 1.0)) mk *= 0.f;
     part_mask[b * J + jo] = mk;
     if (j == 0) {
-        // inv(matrix) by the adjugate
-        const double a00 = m[4] * m[8] - m[5] * m[7], a01 = m[2] * m[7] - m[1] * m[8], a02 = m[1] * m[5] - m[2] * m[4];
-        const double a10 = m[5] * m[6] - m[3] * m[8], a11 = m[0] * m[8] - m[2] * m[6], a12 = m[2] * m[3] - m[0] * m[5];
-        const double a20 = m[3] * m[7] - m[4] * m[6], a21 = m[1] * m[6] - m[0] * m[7], a22 = m[0] * m[4] - m[1] * m[3];
-        const double det = m[0] * a00 + m[1] * a10 + m[2] * a20;
-        const double inv[9] = {a00 / det, a01 / det, a02 / det, a10 / det, a11 / det, a12 / det,
-                               a20 / det, a21 / det, a22 / det};
+        double inv[9];
+        inverse3(m, inv);
         // inv(t) = diag(fx, 1, 1) . s * R^T = [[fx s cos, -fx s sin, 0], [s sin, s cos, 0], [0, 0, 1]]
         const double u00 = fx * s * cs, u01 = -fx * s * sn, u10 = s * sn, u11 = s * cs;
         trans_m[4 * b + 0] = inv[0] * u00 + inv[1] * u10;
@@ -363,6 +394,88 @@ __global__ void __launch_bounds__(ORDER_NT) epoch_indices_kernel(int64_t n, uint
     uint64_t y = feistel(p, h, seed, epoch);
     while (y >= (uint64_t)n) y = feistel(y, h, seed, epoch);      // cycle-walking: ends on p's cycle inside [0, n)
     out[i] = (int64_t)y;
+}
+
+// dsnt_crop_affine (contract in the header comment).  Workgroup (x, b) makes CROP_NT * CROP_PX pixels of crop b; thread 0
+// derives the sample's Pillow coefficients once, every thread then samples CROP_PX consecutive pixels (row-major over the
+// crop, so a group may wrap a row) and packs their 12 bytes into three dwords.
+constexpr int CROP_NT = 256;
+constexpr int CROP_PX = 4;                 // 4 RGB pixels = 12 bytes = 3 dwords per thread
+constexpr int CROP_MAX_SIDE = 16384;
+
+struct CropCoef {
+    double a, b, c, d, e, f;               // Pillow's affine data: crop pixel centre -> image pixel
+    int64_t off;                           // of the image in the pool (an offset, so the taps stay global loads)
+    int w, h, ok;
+};
+
+__global__ void __launch_bounds__(CROP_NT) crop_affine_kernel(const uint8_t* __restrict__ pool, int64_t pool_bytes,
+                                                              const int64_t* __restrict__ offset,
+                                                              const int32_t* __restrict__ hw, int64_t N,
+                                                              const int64_t* __restrict__ idx,
+                                                              const double* __restrict__ matrix, int R,
+                                                              uint8_t* __restrict__ out, uint8_t* __restrict__ valid) {
+    __shared__ CropCoef sc;
+    const int b = blockIdx.y;
+    if (threadIdx.x == 0) {
+        int ok = 0;
+        const int64_t i = idx[b];
+        if (i >= 0 && i < N) {
+            const int h = hw[2 * i], w = hw[2 * i + 1];
+            const int64_t off = offset[i];
+            if (h >= 1 && h <= CROP_MAX_SIDE && w >= 1 && w <= CROP_MAX_SIDE && off >= 0 &&
+                off <= pool_bytes - (int64_t)h * w * 3) {
+                double inv[9];
+                const double det = inverse3(matrix + 9 * b, inv);
+                if (det != 0.0 && isfinite(det)) {
+                    const double r = (double)R;
+                    sc.a = 2 * inv[0] / r; sc.b = 2 * inv[1] / r; sc.c = inv[2] - inv[0] - inv[1];
+                    sc.d = 2 * inv[3] / r; sc.e = 2 * inv[4] / r; sc.f = inv[5] - inv[3] - inv[4];
+                    sc.off = off;
+                    sc.w = w;
+                    sc.h = h;
+                    ok = 1;
+                }
+            }
+        }
+        sc.ok = ok;
+        if (blockIdx.x == 0) valid[b] = (uint8_t)ok;
+    }
+    __syncthreads();
+    const int64_t npx = (int64_t)R * R;
+    const int64_t p0 = ((int64_t)blockIdx.x * CROP_NT + threadIdx.x) * CROP_PX;
+    if (p0 >= npx) return;
+    uint32_t word[3] = {0u, 0u, 0u};       // byte 3k + ch of the group = channel ch of pixel p0 + k
+    if (sc.ok) {
+        const double ca = sc.a, cb = sc.b, cc = sc.c, cd = sc.d, ce = sc.e, cf = sc.f;
+        const uint8_t* img = pool + sc.off;
+        const int W = sc.w, H = sc.h;
+#pragma unroll
+        for (int k = 0; k < CROP_PX; ++k) {
+            const int64_t p = p0 + k;
+            if (p < npx) {
+                const int y = (int)(p / R), x = (int)(p - (int64_t)y * R);
+                const double xo = x + 0.5, yo = y + 0.5;
+                int q0 = 0, q1 = 0, q2 = 0;
+                DSNT_BILINEAR_RGB(img, W, H, ca * xo + cb * yo + cc, cd * xo + ce * yo + cf, 0, q0, q1, q2);
+                const int q[3] = {q0, q1, q2};
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const int j = 3 * k + ch;
+                    word[j >> 2] |= (uint32_t)q[ch] << (8 * (j & 3));
+                }
+            }
+        }
+    }
+    uint8_t* o = out + ((size_t)b * npx + p0) * 3;
+    if (p0 + CROP_PX <= npx && ((uintptr_t)o & 3) == 0) {
+        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+        o4[0] = word[0];
+        o4[1] = word[1];
+        o4[2] = word[2];
+    } else {                               // odd R (unaligned crops) or the last, partial group of a crop
+        for (int j = 0; j < 3 * CROP_PX && p0 + j / 3 < npx; ++j) o[j] = (uint8_t)(word[j >> 2] >> (8 * (j & 3)));
+    }
 }
 
 }  // namespace
@@ -465,6 +578,19 @@ extern "C" int dsnt_epoch_indices(int64_t n, uint64_t seed, uint64_t epoch, int6
     DSNT_LAUNCH(epoch_indices_kernel, dim3((unsigned)((count + ORDER_NT - 1) / ORDER_NT)), dim3(ORDER_NT), 0,
                 (hipStream_t)stream, n, seed, epoch, first, count, shuffle != 0 && n > 1 ? k / 2 : 0, out);
     DSNT_CHECK_LAUNCH("dsnt_epoch_indices");
+}
+
+extern "C" int dsnt_crop_affine(const uint8_t* pool, int64_t pool_bytes, const int64_t* offset, const int32_t* hw,
+                                int64_t N, const int64_t* idx, const double* matrix, int B, int R, uint8_t* out,
+                                uint8_t* valid, void* stream) {
+    DSNT_REQUIRE(pool && offset && hw && idx && matrix && out && valid, DSNT_ERR_ARG, "dsnt_crop_affine: null pointer");
+    DSNT_REQUIRE(pool_bytes > 0 && N > 0 && B > 0 && B <= 65535 && R > 0 && R <= 8192, DSNT_ERR_SHAPE,
+                 "dsnt_crop_affine: bad shape pool_bytes=%lld N=%lld B=%d R=%d", (long long)pool_bytes, (long long)N, B,
+                 R);
+    constexpr int per_wg = CROP_NT * CROP_PX;
+    DSNT_LAUNCH(crop_affine_kernel, dim3((R * R + per_wg - 1) / per_wg, B), dim3(CROP_NT), 0, (hipStream_t)stream, pool,
+                pool_bytes, offset, hw, N, idx, matrix, R, out, valid);
+    DSNT_CHECK_LAUNCH("dsnt_crop_affine");
 }
 
 extern "C" int dsnt_pool_normalize(const float* x, int N, int C, int H, int W, int S, const float* mean, const float* stdv,

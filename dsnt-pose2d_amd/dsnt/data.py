@@ -13,6 +13,10 @@ on the device".  The exact transform (Pillow's rotation, torchvision 0.2.0's cen
 `DeviceDataset` keeps a whole training set of crops resident on the device, and `EpochLoader` runs shuffled epochs
 over it: the order (a counter-based permutation), the gather and the transform are all device launches, so an epoch
 needs no host work (the reference's `DataLoader(train_data, batch_size, shuffle=True, num_workers=4)`).
+
+`ImagePool` keeps full decoded images on the device and crops person boxes from them (`dsnt_crop_affine`, Pillow's
+affine bilinear sampler bit for bit); `box_matrix` builds the box matrices, and `DeviceDataset.from_pool` builds a
+training set from the crops.
 """
 import numpy as np
 import torch
@@ -337,6 +341,49 @@ class DeviceDataset:
         arrays = [np.load(os.path.join(directory, n + '.npy'), mmap_mode='r') for n in _FIELDS]
         return cls.from_arrays(*arrays, device=device, chunk_bytes=chunk_bytes)
 
+    @classmethod
+    def from_pool(cls, pool, idx, matrix, keypoints, keypoint_mask, head_lengths, size=384, chunk_bytes=_STAGE_BYTES):
+        """A training set cropped on the device from the full images of an `ImagePool`: row i is `pool.crop` of image
+        `idx[i]` through `matrix[i]` at `size` x `size`, written by `dsnt_crop_affine` a chunk of rows at a time straight
+        into the crop tensor.  `idx` [N] (integer), `matrix` [N, 3, 3], `keypoints` [N, J, 2] (original-image pixels),
+        `keypoint_mask` [N, J], `head_lengths` [N]: numpy arrays, CPU tensors or tensors on the pool's device; host data
+        is uploaded as `from_arrays` does.  The crops follow `matrix` and Pillow's affine sampler, not torchdata's
+        `load_cropped_image`.  Raises if a row has no crop (index outside the pool, singular matrix); that check
+        synchronises once, at the end (it is the one-off packing step)."""
+        if not isinstance(pool, ImagePool):
+            raise RuntimeError('dsnt: from_pool needs an ImagePool, got %s' % type(pool))
+        device = pool.device
+        names = ('idx', 'matrix', 'keypoints', 'keypoint_mask', 'head_lengths')
+        arrays = [_host_array(n, a) for n, a in zip(names, (idx, matrix, keypoints, keypoint_mask, head_lengths))]
+        N = arrays[0].shape[0] if arrays[0].ndim == 1 else -1
+        J = arrays[2].shape[1] if arrays[2].ndim == 3 else -1
+        for name, a, shape in zip(names, arrays, ((N,), (N, 3, 3), (N, J, 2), (N, J), (N,))):
+            if tuple(a.shape) != shape or N < 1 or J < 1:
+                raise RuntimeError('dsnt: %s must have shape %s, got %s' % (name, shape, tuple(a.shape)))
+        if _kind(arrays[0]) not in 'iu':
+            raise RuntimeError('dsnt: idx must be integer, got %s' % arrays[0].dtype)
+        for name, a in zip(names[1:], arrays[1:]):
+            if _kind(a) not in ('biuf' if name == 'keypoint_mask' else 'f'):
+                raise RuntimeError('dsnt: %s must be %s, got %s' % (name, 'real or bool' if name == 'keypoint_mask'
+                                                                     else 'floating point', a.dtype))
+        R = int(size)
+        if not 1 <= R <= 8192:
+            raise RuntimeError('dsnt: size must lie in [1, 8192], got %d' % R)
+        stage = _stage(arrays, chunk_bytes)
+        dtypes = (torch.int64, torch.float64, torch.float64, torch.float32, torch.float64)
+        with torch.cuda.device(device):
+            rows, m, kp, km, hl = [_upload(a, dt, device, stage) for a, dt in zip(arrays, dtypes)]
+            crops = torch.empty(N, R, R, 3, dtype=torch.uint8, device=device)
+            valid = torch.empty(N, dtype=torch.uint8, device=device)
+            for r0 in range(0, N, _CROP_ROWS):
+                r1 = min(N, r0 + _CROP_ROWS)
+                pool._crop_into(rows[r0:r1], m[r0:r1], crops[r0:r1], valid[r0:r1])
+            bad = int((valid == 0).sum())
+        if bad:
+            raise RuntimeError('dsnt: from_pool: %d of %d rows have no crop (index outside the pool of %d images, or a '
+                               'singular or non-finite matrix)' % (bad, N, len(pool)))
+        return cls(crops, kp, km, m, hl)
+
 
 def _kind(a):
     """numpy's dtype kind ('b', 'i', 'u', 'f', ...) of an array or a tensor."""
@@ -359,10 +406,15 @@ def _chunk_rows(t, stage):
     return max(1, stage.numel() // row)
 
 
-def _upload(a, dtype, device, stage):
+def _upload(a, dtype, device, stage, dst=None):
+    """`a` on `device` as `dtype`, through the pinned `stage` a chunk of rows at a time; into `dst` (a contiguous device
+    tensor of `a`'s shape) when given."""
     if isinstance(a, torch.Tensor):                    # already on a device
+        if dst is not None:
+            return dst.copy_(a)
         return a.to(device=device, dtype=dtype).contiguous()
-    dst = torch.empty(a.shape, dtype=dtype, device=device)
+    if dst is None:
+        dst = torch.empty(a.shape, dtype=dtype, device=device)
     rows = _chunk_rows(dst, stage)
     for r0 in range(0, len(a), rows):
         part = a[r0:r0 + rows]
@@ -473,3 +525,131 @@ class EpochLoader:
             self.batch = s + 1
             yield sample
         self.epoch, self.batch = self.epoch + 1, 0
+
+
+_MAX_SIDE = 16384          # dsnt_crop_affine's bound on an image side
+_CROP_ROWS = 8192          # samples per dsnt_crop_affine launch in DeviceDataset.from_pool (a launch takes <= 65535)
+
+
+def box_matrix(center, side, device=None):
+    """The bounding-box matrix of square boxes, f64 `[B, 3, 3]`: original-image pixels -> box coordinates in [-1, 1]
+    (`n = (x - cx) * 2 / side`, the convention of `DeviceAugment`'s and `ImagePool.crop`'s `matrix`).  `center` `[B, 2]`
+    (cx, cy) and `side` `[B]`, in pixels, on any device (default: `center`'s).  Entries: `2 / side` on the diagonal,
+    `-2 * cx / side` and `-2 * cy / side` in the last column, 1 in the corner, computed in fp64 where the result lives
+    (on the device for device tensors: no host round trip).  Any detector's box maps onto it, e.g. `center` = the box
+    centre and `side` = 1.25 * max(width, height)."""
+    c = torch.as_tensor(center, dtype=torch.float64, device=device)
+    s = torch.as_tensor(side, dtype=torch.float64, device=c.device)
+    if c.dim() != 2 or c.shape[1] != 2 or tuple(s.shape) != (c.shape[0],):
+        raise RuntimeError('dsnt: box_matrix needs center [B, 2] and side [B], got %s and %s'
+                           % (tuple(c.shape), tuple(s.shape)))
+    m = torch.zeros(c.shape[0], 3, 3, dtype=torch.float64, device=c.device)
+    m[:, 0, 0] = 2 / s
+    m[:, 1, 1] = 2 / s
+    m[:, 0, 2] = -2 * c[:, 0] / s
+    m[:, 1, 2] = -2 * c[:, 1] / s
+    m[:, 2, 2] = 1
+    return m
+
+
+def _image(i, a):
+    """Image `i` of `ImagePool.from_images` as a numpy array or a device tensor, checked to be H x W x 3 uint8."""
+    if not isinstance(a, (np.ndarray, torch.Tensor)):
+        raise RuntimeError('dsnt: image %d must be an H x W x 3 uint8 numpy array or tensor, got %s (decode it and convert '
+                           "a PIL image with np.asarray(img.convert('RGB')))" % (i, type(a)))
+    a = _host_array('image %d' % i, a)
+    dtype = str(a.dtype).replace('torch.', '')
+    if a.ndim != 3 or a.shape[2] != 3 or dtype != 'uint8':
+        raise RuntimeError("dsnt: image %d must be H x W x 3 uint8 (RGB), got shape %s of %s; convert with .convert('RGB') "
+                           'and np.asarray' % (i, tuple(a.shape), dtype))
+    if not (1 <= a.shape[0] <= _MAX_SIDE and 1 <= a.shape[1] <= _MAX_SIDE):
+        raise RuntimeError('dsnt: image %d is %d x %d; sides must lie in [1, %d]' % (i, a.shape[0], a.shape[1], _MAX_SIDE))
+    return a
+
+
+class ImagePool:
+    """Full RGB images resident on one device, to crop person boxes from (`crop`, `DeviceDataset.from_pool`,
+    `inference.predict_boxes`).
+
+    Fields: `data` uint8 `[total]`, the images one after another, each H x W x 3 (HWC, row-major); `offset` int64 `[N]`,
+    the byte where image i starts; `hw` int32 `[N, 2]`, its (H, W).  `from_images` packs a list of decoded images;
+    decoding (JPEG, PNG) stays with the caller.
+    """
+
+    def __init__(self, data, offset, hw):
+        for name, t, dtype in (('data', data, torch.uint8), ('offset', offset, torch.int64), ('hw', hw, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+                raise RuntimeError('dsnt: ImagePool.%s must be a %s tensor' % (name, dtype))
+        for t in (data, offset, hw):
+            _lib.ptr(t)          # refuses CPU and non-contiguous tensors
+        N = offset.shape[0] if offset.dim() == 1 else -1
+        if data.dim() != 1 or data.numel() < 1 or N < 1 or tuple(hw.shape) != (N, 2):
+            raise RuntimeError('dsnt: ImagePool needs data [total], offset [N] and hw [N, 2], got %s, %s and %s'
+                               % (tuple(data.shape), tuple(offset.shape), tuple(hw.shape)))
+        if offset.device != data.device or hw.device != data.device:
+            raise RuntimeError('dsnt: ImagePool fields must be on one device')
+        self.data, self.offset, self.hw = data, offset, hw
+
+    def __len__(self):
+        return self.offset.shape[0]
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @classmethod
+    def from_images(cls, images, device='cuda', chunk_bytes=_STAGE_BYTES):
+        """Pack a list of decoded RGB images: H x W x 3 uint8 numpy arrays, CPU tensors or device tensors, sides up to
+        16384.  Host images go through one pinned staging buffer of at most `chunk_bytes`, a chunk of rows at a time,
+        straight into the pool.  Synchronises with the device (it is a packing step)."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('dsnt: ImagePool lives on a HIP device, not %s (no CPU fallback)' % device)
+        arrays = [_image(i, a) for i, a in enumerate(images)]
+        if not arrays:
+            raise RuntimeError('dsnt: ImagePool.from_images needs at least one image')
+        sizes = np.array([a.shape[0] * a.shape[1] * 3 for a in arrays], np.int64)
+        offset = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        hw = np.array([a.shape[:2] for a in arrays], np.int32)
+        stage = _stage(arrays, chunk_bytes)
+        with torch.cuda.device(device):
+            data = torch.empty(int(sizes.sum()), dtype=torch.uint8, device=device)
+            for a, o, n in zip(arrays, offset, sizes):
+                _upload(a, torch.uint8, device, stage, dst=data[int(o):int(o + n)].view(tuple(a.shape)))
+            offset_t, hw_t = (_upload(a, dt, device, stage) for a, dt in ((offset, torch.int64), (hw, torch.int32)))
+        return cls(data, offset_t, hw_t)
+
+    def _crop_into(self, idx, matrix, out, valid):
+        """One dsnt_crop_affine launch: rows of `idx` / `matrix` into `out` uint8 [B, R, R, 3] and `valid` uint8 [B]."""
+        B, R = out.shape[0], out.shape[1]
+        _lib.call('dsnt_crop_affine', _lib.ptr(self.data), self.data.numel(), _lib.ptr(self.offset), _lib.ptr(self.hw),
+                  len(self), _lib.ptr(idx), _lib.ptr(matrix), B, R, _lib.ptr(out), _lib.ptr(valid))
+
+    def _rows(self, idx, matrix):
+        """`idx` int64 [B] and `matrix` f64 [B, 3, 3] on the pool's device (dtype conversions run there)."""
+        for name, t in (('idx', idx), ('matrix', matrix)):
+            if not isinstance(t, torch.Tensor) or t.device != self.device:
+                raise RuntimeError('dsnt: %s must be a tensor on the pool\'s device %s' % (name, self.device))
+        if idx.dtype.is_floating_point or idx.dtype == torch.bool or idx.dim() != 1 or idx.numel() < 1:
+            raise RuntimeError('dsnt: idx must be an integer tensor [B], got %s %s' % (idx.dtype, tuple(idx.shape)))
+        B = idx.shape[0]
+        if not matrix.dtype.is_floating_point or tuple(matrix.shape) != (B, 3, 3):
+            raise RuntimeError('dsnt: matrix must be a floating-point [%d, 3, 3] tensor, got %s %s'
+                               % (B, matrix.dtype, tuple(matrix.shape)))
+        return idx.to(torch.int64).contiguous(), matrix.to(torch.float64).contiguous()
+
+    def crop(self, idx, matrix, size=384):
+        """Crops of boxes: sample b is image `idx[b]` resampled through `matrix[b]` (f64 `[B, 3, 3]`, image pixels ->
+        [-1, 1]^2, e.g. `box_matrix`) to `size` x `size`.  Returns `(crops uint8 [B, size, size, 3], valid bool [B])`.
+        Equal bit for bit to Pillow's `Image.transform((size, size), AFFINE, data, BILINEAR)` with the coefficients of
+        `csrc/augment.hip`; not to torchdata's `load_cropped_image`, whose resampling is not this one.  A sample with
+        an index outside the pool or a singular (or non-finite) matrix is all zero and not valid.  One launch on the
+        current stream; nothing synchronises with the host.  B <= 65535, 1 <= size <= 8192."""
+        idx, matrix = self._rows(idx, matrix)
+        B, R = idx.shape[0], int(size)
+        if B > 65535 or not 1 <= R <= 8192:
+            raise RuntimeError('dsnt: crop takes B <= 65535 and 1 <= size <= 8192, got B=%d size=%d' % (B, R))
+        out = torch.empty(B, R, R, 3, dtype=torch.uint8, device=self.device)
+        valid = torch.empty(B, dtype=torch.uint8, device=self.device)
+        self._crop_into(idx, matrix, out, valid)
+        return out, valid.view(torch.bool)

@@ -12,6 +12,9 @@ The backbone and the DSNT head run on the HIP path (eval-mode BN from the runnin
 `predict` and `predict_dataset` are the batched form of the same computation (any batch size, flip augmentation
 included, nothing synchronising with the host): the mirrored twin of every input runs in the same forward, and one
 launch (`flip_merge_head`, `dsnt_flip_merge_head`) merges the last stack's logits, runs the head and back-projects.
+
+`predict_boxes` starts from full images instead of crops: person boxes of an `ImagePool` are cropped on the device
+(`dsnt_crop_affine`), then evaluated as `predict` does, and the joints come back in the images' pixels.
 """
 import ctypes
 import time
@@ -199,3 +202,51 @@ def predict_dataset(model, dataset, use_flipped=True, batch_size=32, time_meter=
     if not preds:
         return torch.zeros(0, 16, 2, dtype=torch.float64)
     return torch.cat(preds, 0).cpu()
+
+
+_box_augment = {}
+
+
+def _box_augment_for(specs, mean, std, device):
+    """The identity `DeviceAugment` of `predict_boxes`, one per (specs, statistics), with its constants on `device`
+    uploaded once: a later call enqueues no host-to-device copy."""
+    from .data import DeviceAugment
+    key = (specs.size, specs.subtract_mean, specs.divide_stddev, tuple(float(v) for v in mean),
+           tuple(float(v) for v in std))
+    aug = _box_augment.get(key)
+    if aug is None:
+        aug = _box_augment[key] = DeviceAugment(specs, mean, std, use_aug=False, train=False)
+    aug._consts(device)
+    return aug
+
+
+def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_size=384, return_normalized=False):
+    """Joint positions in original-image pixels for person boxes in full images: f64 `[B, J, 2]` on the device.
+
+    `pool` a `data.ImagePool`; sample b is image `idx[b]` (int64 `[B]`) with the box matrix `matrix[b]` (f64
+    `[B, 3, 3]`, image pixels -> [-1, 1]^2, e.g. `data.box_matrix` of a detector's boxes), both on the pool's device.
+    `mean` / `std`: the dataset statistics the model was trained with (used as `model.image_specs` says).  The chain:
+    `pool.crop(idx, matrix, crop_size)`, then `DeviceAugment(use_aug=False, train=False)` of the crops
+    (`flip_pair=use_flipped`), then `predict(..., paired=use_flipped)` with the keypoints kernel's `transform_m` /
+    `transform_b` of `matrix`.  `predict` back-projects row vectors as `coords @ transform_m + transform_b`, the
+    reference's convention, which is the inverse of `matrix` only when its 2 x 2 part is symmetric (axis-aligned
+    boxes); here `transform_m` is passed transposed, so the result is `inverse(matrix) . [x, y, 1]` for any invertible
+    matrix, and bit for bit what `predict` gives on axis-aligned boxes.  A sample without a crop (index outside the
+    pool, singular matrix) comes out NaN.  Nothing synchronises with the host (the first call on a device uploads the
+    normalisation constants).  `return_normalized=True` returns `(image_coords, normalised f32 coords)`."""
+    crops, valid = pool.crop(idx, matrix, crop_size)
+    B, dev = crops.shape[0], crops.device
+    aug = _box_augment_for(model.image_specs, mean, std, dev)
+    J = HFLIP_INDICES.numel()
+    kp = torch.zeros(B, J, 2, dtype=torch.float64, device=dev)
+    km = torch.zeros(B, J, dtype=torch.float32, device=dev)
+    hl = torch.ones(B, dtype=torch.float64, device=dev)
+    m = matrix.to(torch.float64).contiguous()
+    s = aug(crops, kp, km, m, hl, 0, flip_pair=use_flipped)
+    tm = s['transform_m'].transpose(1, 2).contiguous()
+    img, coords = predict(model, s['input_pair'] if use_flipped else s['input'], tm, s['transform_b'],
+                          use_flipped=use_flipped, paired=use_flipped, return_normalized=True)
+    img = torch.where(valid.view(B, 1, 1), img, float('nan'))
+    if not return_normalized:
+        return img
+    return img, torch.where(valid.view(B, 1, 1), coords, float('nan'))

@@ -766,6 +766,15 @@ int dsnt_augment_keypoints_gather(const double* matrix_pool, const double* kp_po
  * identity.  Needs 0 <= first, 0 < count <= n - first. */
 int dsnt_epoch_indices(int64_t n, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int shuffle, int64_t* out,
                        void* stream);
+/* Person crops of full images (dsnt.data.ImagePool.crop).  dsnt_version() >= 119.  pool: N RGB images, uint8 HWC, image i
+ * at byte offset[i] (int64 [N]) with hw[i] = (h, w) (int32 [N][2]), pool_bytes the size of the buffer.  Sample b < B crops
+ * image idx[b] (int64 [B]) with matrix[b] (f64 [B][3][3], image pixels -> [-1, 1]^2 crop coordinates) into out uint8
+ * [B][R][R][3], equal bit for bit to Pillow's Image.transform((R, R), AFFINE, (a..f), BILINEAR) with the coefficients of
+ * csrc/augment.hip; valid uint8 [B] = 1.  An index outside [0, N), an image record outside the pool or with a side outside
+ * [1, 16384], or a matrix whose determinant is 0 or not finite reads nothing: zero crop, valid 0.  R <= 8192, B <= 65535.
+ * Bit-reproducible (no atomics). */
+int dsnt_crop_affine(const uint8_t* pool, int64_t pool_bytes, const int64_t* offset, const int32_t* hw, int64_t N,
+                     const int64_t* idx, const double* matrix, int B, int R, uint8_t* out, uint8_t* valid, void* stream);
 /* data.py:38-56 (ImageSpecs.convert) on a float image: x f32 [N][C][H][W] -> out f32 [N][C][S][S] =
  * (adaptive_avg_pool2d(x, S) - mean[c]) / stdv[c]; mean, stdv [C] (device). */
 int dsnt_pool_normalize(const float* x, int N, int C, int H, int W, int S, const float* mean, const float* stdv,
