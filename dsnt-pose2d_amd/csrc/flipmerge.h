@@ -52,6 +52,56 @@ __device__ __forceinline__ void flip_backproject(float cx, float cy, const doubl
     img[2 * (size_t)row + 1] = t[1] + fma(y, M[3], x * M[1]);
 }
 
-// the gauss strategy's launch (heatmap.hip); the entry point validates first
+// ---- per-joint statistics of a heat-map row (dsnt_heatmap_stats, dsnt_flip_merge_head_stats)
+// For one row (sample b, joint j) with the post-activation map p[y][x], h x w, and the DSNT grid X = (2x + 1)/w - 1,
+// Y = (2y + 1)/h - 1 (Grid2, head.hip):
+//   peak, peak_index   max p and the first index i = y w + x that holds it (decode_row's rule); NaN is never the peak
+//   mass               sum p (1 for softmax; not for the other preactivations at eps, nor for gauss)
+//   mean = (mx, my)    (sum X p, sum Y p): for the dsnt strategy the coordinates, bit for bit
+//   cov                vxx = sum (X - mx)^2 p, vyy = sum (Y - my)^2 p, vxy = sum (X - mx)(Y - my) p, by a second sweep
+//                      over the row once the mean is known (as reg_context does for `var`), never E[X^2] - mx^2
+//   cov_image          f64 [2][2] = M^T S M, S = [[vxx, vxy], [vxy, vyy]], M = transform_m[b]: with img = t + c . M on row
+//                      vectors (flip_backproject) the covariance of the joint in original-image pixels^2
+// stats f32 [rows][7] = peak, mass, mx, my, vxx, vyy, vxy; peak_index int32 [rows]; cov_image f64 [rows][4].
+// For the gauss strategy peak, peak_index and mass describe the merged map as it is and the rest is NaN.
+// Thread 0 of the row's workgroup writes everything with plain stores.
+//
+// The fused kernels take the outputs as an optional trailing parameter pack (`ST... so`, empty or one StatsOut), so the
+// instantiations without it keep exactly the signature, and the code, they had.
+struct StatsOut {
+    float* stats;
+    int* peak_index;
+    double* cov_image;
+};
+template <typename T>
+__device__ __forceinline__ const T& only(const T& t) { return t; }
+
+// Block-wide (max, first index holding it) from each thread's (best, bi) over ascending indices of its own; bi =
+// 0x7fffffff where a thread saw nothing above -inf.  Indices are < 2^24 (check_rows), exact as floats, so the first index
+// is a block_max of the negated candidates.  A row with nothing above -inf gives index 0.  Every thread gets the result.
+__device__ __forceinline__ void block_peak(float& best, int& bi, float* red) {
+    const float m = block_max(best, red);
+    const float cand = (best == m && bi != 0x7fffffff) ? (float)bi : 16777216.f;
+    const float first = -block_max(-cand, red);
+    best = m;
+    bi = first < 16777216.f ? (int)first : 0;
+}
+
+// cov_image = M^T (S M) in fp64, the products in this order (tests/stats_ref.py follows it)
+__device__ __forceinline__ void stats_cov_image(float vxx, float vyy, float vxy, const double* __restrict__ tm,
+                                                double* __restrict__ cov_image, int B_idx, int row) {
+    const double* M = tm + 4 * (size_t)B_idx;
+    const double a = vxx, d = vyy, c = vxy;
+    const double t00 = a * M[0] + c * M[2], t01 = a * M[1] + c * M[3];      // S M
+    const double t10 = c * M[0] + d * M[2], t11 = c * M[1] + d * M[3];
+    double* o = cov_image + 4 * (size_t)row;
+    o[0] = M[0] * t00 + M[2] * t10;
+    o[1] = M[0] * t01 + M[2] * t11;
+    o[2] = M[1] * t00 + M[3] * t10;
+    o[3] = M[1] * t01 + M[3] * t11;
+}
+
+// the gauss strategy's launch (heatmap.hip); the entry point validates first.  `so`: the statistics' outputs, or NULL.
 int flip_merge_decode_launch(const float* logits, int B, int J, int h, int w, const FlipPerm& perm,
-                             const double* tm, const double* tb, float* hm, float* coords, double* img, void* stream);
+                             const double* tm, const double* tb, float* hm, float* coords, double* img,
+                             const StatsOut* so, void* stream);

@@ -89,16 +89,18 @@ __global__ __launch_bounds__(HB) void heatmap_mse_bwd_kernel(const float* __rest
 // util.py:150-198: first arg-max pixel, (0, 0) when the maximum is not positive, +-0.25 px towards the larger
 // neighbour for interior pixels, then pixel -> normalised coordinates ((p + 0.5) * (2/size) - 1, fp32 steps).
 // One row read from `x` (a `const float*`, or the flip-merged logits of dsnt_flip_merge_head: FlipSrc); thread 0 returns
-// true with the coordinates in (cx, cy).
-template <typename SRC>
+// true with the coordinates in (cx, cy), the maximum in `peak` and its first index in `index`.  `seen(v)` is called with
+// every value a thread reads (the statistics of dsnt_flip_merge_head_stats take the row's sum there).
+template <typename SRC, typename F>
 __device__ __forceinline__ bool decode_row(const SRC& x, int h, int w, int use_neighbours, float sx, float sy, float& cx,
-                                           float& cy) {
+                                           float& cy, float& peak, int& index, F seen) {
     __shared__ float rv[4];
     __shared__ int ri[4];
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = threadIdx.x; i < h * w; i += HB) {
         const float v = x[i];
+        seen(v);
         if (v > best) { best = v; bi = i; }            // ascending i per thread: keeps the first maximum
     }
 #pragma unroll
@@ -114,6 +116,7 @@ __device__ __forceinline__ bool decode_row(const SRC& x, int h, int w, int use_n
         for (int wv = 1; wv < HB / 64; ++wv)
             if (rv[wv] > best || (rv[wv] == best && ri[wv] < bi)) { best = rv[wv]; bi = ri[wv]; }
         if (bi == 0x7fffffff) bi = 0;                    // all -inf / NaN rows
+        peak = best; index = bi;
         float px = (float)(bi % w), py = (float)(bi / h);          // `idx / height` as the reference (util.py:161)
         if (!(best > 0.f)) { px = 0.f; py = 0.f; }
         if (use_neighbours) {
@@ -132,6 +135,13 @@ __device__ __forceinline__ bool decode_row(const SRC& x, int h, int w, int use_n
     }
     return false;
 }
+template <typename SRC>
+__device__ __forceinline__ bool decode_row(const SRC& x, int h, int w, int use_neighbours, float sx, float sy, float& cx,
+                                           float& cy) {
+    float peak;
+    int index;
+    return decode_row(x, h, w, use_neighbours, sx, sy, cx, cy, peak, index, [](float) {});
+}
 
 __global__ __launch_bounds__(HB) void decode_heatmaps_kernel(const float* __restrict__ hm, float* __restrict__ coords,
                                                               int h, int w, int use_neighbours, float sx, float sy) {
@@ -145,12 +155,17 @@ __global__ __launch_bounds__(HB) void decode_heatmaps_kernel(const float* __rest
 
 // dsnt_flip_merge_head, gauss strategy (model.py:268-269 on the merged heat-maps of inference.py:38-48): the merged row
 // is stored when hm != NULL, then decoded as dsnt_decode_heatmaps does (use_neighbours = 1) and back-projected.
-template <bool STORE>
+// With a StatsOut (dsnt_flip_merge_head_stats; flipmerge.h): peak and first index are the decode's own arg-max, the mass
+// is summed in the decode's read of the row (each thread's values in ascending index, then block_sum: not the order of
+// dsnt_heatmap_stats on the stored map), and mean, covariance and cov_image are NaN: the map is no distribution.
+template <bool STORE, typename... ST>
 __global__ __launch_bounds__(HB) void flip_merge_decode_kernel(const float* __restrict__ logits, int B, int J, int h,
                                                                 int w, FlipPerm perm, float sx, float sy,
                                                                 const double* __restrict__ tm,
                                                                 const double* __restrict__ tb, float* __restrict__ hm,
-                                                                float* __restrict__ coords, double* __restrict__ img) {
+                                                                float* __restrict__ coords, double* __restrict__ img,
+                                                                ST... so) {
+    constexpr bool STATS = sizeof...(ST) > 0;
     const int row = blockIdx.x, hw = h * w;
     const FlipSrc x = flip_src(logits, B, J, hw, w, perm, row);
     if (STORE) {
@@ -158,16 +173,48 @@ __global__ __launch_bounds__(HB) void flip_merge_decode_kernel(const float* __re
         for (int i = threadIdx.x; i < hw; i += HB) o[i] = x[i];
     }
     float cx, cy;
-    if (decode_row(x, h, w, 1, sx, sy, cx, cy)) {
-        coords[2 * (size_t)row] = cx;
-        coords[2 * (size_t)row + 1] = cy;
-        flip_backproject(cx, cy, tm, tb, img, row / J, row);
+    if constexpr (STATS) {
+        __shared__ float red[4];
+        float peak = 0.f, mass[1] = {0.f};
+        int index = 0;
+        const bool lead = decode_row(x, h, w, 1, sx, sy, cx, cy, peak, index, [&](float v) { mass[0] += v; });
+        block_sum<1>(mass, red);
+        if (lead) {
+            coords[2 * (size_t)row] = cx;
+            coords[2 * (size_t)row + 1] = cy;
+            flip_backproject(cx, cy, tm, tb, img, row / J, row);
+            const StatsOut o = only(so...);
+            const float nan = __int_as_float(0x7fc00000);
+            float* s = o.stats + 7 * (size_t)row;
+            s[0] = peak; s[1] = mass[0];
+            for (int k = 2; k < 7; ++k) s[k] = nan;
+            o.peak_index[row] = index;
+            for (int k = 0; k < 4; ++k) o.cov_image[4 * (size_t)row + k] = (double)nan;
+        }
+    } else {
+        if (decode_row(x, h, w, 1, sx, sy, cx, cy)) {
+            coords[2 * (size_t)row] = cx;
+            coords[2 * (size_t)row + 1] = cy;
+            flip_backproject(cx, cy, tm, tb, img, row / J, row);
+        }
     }
 }
 
 int flip_merge_decode_launch(const float* logits, int B, int J, int h, int w, const FlipPerm& perm, const double* tm,
-                             const double* tb, float* hm, float* coords, double* img, void* stream) {
+                             const double* tb, float* hm, float* coords, double* img, const StatsOut* so, void* stream) {
     const float sx = (float)(2.0 / (double)w), sy = (float)(2.0 / (double)h);
+    const dim3 grid((unsigned)(B * J));
+    hipStream_t st = (hipStream_t)stream;
+    if (so) {
+        const StatsOut o = *so;
+        if (hm)
+            DSNT_LAUNCH((flip_merge_decode_kernel<true, StatsOut>), grid, dim3(HB), 0, st, logits, B, J, h, w, perm, sx, sy,
+                        tm, tb, hm, coords, img, o);
+        else
+            DSNT_LAUNCH((flip_merge_decode_kernel<false, StatsOut>), grid, dim3(HB), 0, st, logits, B, J, h, w, perm, sx,
+                        sy, tm, tb, hm, coords, img, o);
+        return DSNT_OK;
+    }
     if (hm)
         DSNT_LAUNCH(flip_merge_decode_kernel<true>, dim3((unsigned)(B * J)), dim3(HB), 0, (hipStream_t)stream, logits, B,
                     J, h, w, perm, sx, sy, tm, tb, hm, coords, img);

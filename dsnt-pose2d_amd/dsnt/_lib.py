@@ -87,6 +87,8 @@ SIGNATURES = {
     'dsnt_masked_avg_bwd': [P, P, P, P, L, P],
     'dsnt_head_fwd': [P, P, P, L, I, I, P],
     'dsnt_flip_merge_head': [P, L, I, I, I, P, I, I, F, F, P, P, P, P, P, P],
+    'dsnt_flip_merge_head_stats': [P, L, I, I, I, P, I, I, F, F, P, P, P, P, P, P, P, P, P],
+    'dsnt_heatmap_stats': [P, L, I, I, P, P, P],
     'dsnt_head_loss_rows': [P, P, P, P, P, L, I, I, F, I, P],
     'dsnt_head_bwd': [P, P, P, P, P, P, P, L, I, I, F, I, P],
     'dsnt_head_loss_grad': [P, P, P, P, P, P, P, P, L, I, I, F, I, F, P],

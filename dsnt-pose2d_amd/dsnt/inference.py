@@ -15,6 +15,9 @@ launch (`flip_merge_head`, `dsnt_flip_merge_head`) merges the last stack's logit
 
 `predict_boxes` starts from full images instead of crops: person boxes of an `ImagePool` are cropped on the device
 (`dsnt_crop_affine`), then evaluated as `predict` does, and the joints come back in the images' pixels.
+
+`return_stats=True` on the three adds a confidence and a spread per joint, taken from the heat-map the coordinates come
+from (see `STATS_DOC`).
 """
 import ctypes
 import time
@@ -90,7 +93,42 @@ def _host_perm(perm):
     return arr
 
 
-def flip_merge_head(logits, transform_m, transform_b, strategy='dsnt', preact='softmax', perm=None, heatmaps=True):
+STATS_DOC = """The per-joint statistics dict (`return_stats=True`, `flip_merge_head(stats=True)`): device tensors
+  * `peak` f32 `[B, J]`: the largest pixel of the joint's heat-map; `peak_index` int32 `[B, J]`: the first flat index
+    `y * w + x` that holds it (-1 for a `predict_boxes` sample without a crop);
+  * `mass` f32 `[B, J]`: the sum of the map (1 for softmax);
+  * `mean` f32 `[B, J, 2]`: the DSNT expectation of the map.  For the 'dsnt' strategy these are the normalised
+    coordinates: bit for bit from the fused flip launch, and to the last bit or two without flip, where the statistics
+    come from `dsnt_heatmap_stats` on the stored map and the softmax head sums in another order.  For 'fc' the
+    prediction comes from the linear layer and `mean` is NOT it;
+  * `cov` f32 `[B, J, 3]`: `(vxx, vyy, vxy)` about that mean, normalised units;
+  * `cov_image` f64 `[B, J, 2, 2]`: `transform_m^T . cov . transform_m`, the covariance in original-image pixels^2.
+For the 'gauss' strategy the map is the raw merged heat-map, no distribution: `peak`, `peak_index` and `mass` describe it
+as it is, and `mean`, `cov` and `cov_image` are NaN.  Nothing is calibrated to [0, 1]: `peak` (confidence, higher is
+better) and `sqrt(trace(cov_image))` (spread in pixels, lower is better) are the two quantities to threshold on."""
+
+
+def _cov_image(cov, tm):
+    """`M^T S M` in fp64 for `cov` f32 `[B, J, 3]` = (vxx, vyy, vxy) and `tm` f64 `[B, 2, 2]`: `[B, J, 2, 2]`."""
+    c = cov.double()
+    S = torch.stack([c[..., 0], c[..., 2], c[..., 2], c[..., 1]], -1).view(*c.shape[:-1], 2, 2)
+    M = tm.reshape(-1, 1, 2, 2)
+    return M.transpose(-1, -2) @ (S @ M)
+
+
+def _map_stats(hm, tm, distribution=True):
+    """The statistics dict of materialised heat-maps `[B, J, h, w]` (`dsnt_heatmap_stats`, then `cov_image` by the fused
+    launch's fp64 rule).  `distribution=False` (raw 'gauss' maps): mean, cov and cov_image are NaN."""
+    st = dnn.heatmap_stats(hm)
+    if not distribution:
+        st['mean'] = torch.full_like(st['mean'], float('nan'))
+        st['cov'] = torch.full_like(st['cov'], float('nan'))
+    st['cov_image'] = _cov_image(st['cov'], tm)
+    return st
+
+
+def flip_merge_head(logits, transform_m, transform_b, strategy='dsnt', preact='softmax', perm=None, heatmaps=True,
+                    stats=False):
     """The merge and head of flip test-time augmentation for a paired batch, in one launch (`dsnt_flip_merge_head`).
 
     `logits` f32 `[2B, J, h, w]`: the last stack's heat-map logits, rows `B..2B-1` those of the mirrored inputs.
@@ -99,7 +137,9 @@ def flip_merge_head(logits, transform_m, transform_b, strategy='dsnt', preact='s
     logits) and 'gauss' decodes the arg-max (`util.decode_heatmaps`).  `perm` defaults to `HFLIP_INDICES` (a host
     sequence; it is checked there, never read from the device).  Returns `(image_coords, coords, heatmaps)`: f64
     `[B, J, 2]` = `transform_b + coords @ transform_m`, the normalised f32 `[B, J, 2]`, and the merged heat-maps
-    `[B, J, h, w]` (or None when `heatmaps=False`).  `transform_m` f64 `[B, 2, 2]`, `transform_b` f64 `[B, 1, 2]`."""
+    `[B, J, h, w]` (or None when `heatmaps=False`).  `transform_m` f64 `[B, 2, 2]`, `transform_b` f64 `[B, 1, 2]`.
+    `stats=True` (`dsnt_flip_merge_head_stats`, the same launch) appends the statistics dict of `STATS_DOC`; the first
+    three results keep their bits, and the heat-maps need not be stored for it."""
     if strategy not in _STRATEGIES:
         raise RuntimeError('dsnt: flip_merge_head supports the dsnt and gauss strategies, not %r' % (strategy,))
     if preact not in dnn.PREACT_MODES:
@@ -119,9 +159,19 @@ def flip_merge_head(logits, transform_m, transform_b, strategy='dsnt', preact='s
     coords = torch.empty(B, J, 2, device=x.device, dtype=torch.float32)
     img = torch.empty(B, J, 2, device=x.device, dtype=torch.float64)
     hm = torch.empty(B, J, h, w, device=x.device, dtype=torch.float32) if heatmaps else None
-    _lib.call('dsnt_flip_merge_head', _lib.ptr(x), B, J, h, w, _host_perm(perm), _STRATEGIES[strategy], mode, thr, eps,
-              _lib.ptr(tm), _lib.ptr(tb), _lib.ptr(hm), _lib.ptr(coords), _lib.ptr(img))
-    return img, coords, hm
+    if not stats:
+        _lib.call('dsnt_flip_merge_head', _lib.ptr(x), B, J, h, w, _host_perm(perm), _STRATEGIES[strategy], mode, thr,
+                  eps, _lib.ptr(tm), _lib.ptr(tb), _lib.ptr(hm), _lib.ptr(coords), _lib.ptr(img))
+        return img, coords, hm
+    packed = torch.empty(B * J, 7, device=x.device, dtype=torch.float32)
+    index = torch.empty(B * J, device=x.device, dtype=torch.int32)
+    cov_image = torch.empty(B, J, 2, 2, device=x.device, dtype=torch.float64)
+    _lib.call('dsnt_flip_merge_head_stats', _lib.ptr(x), B, J, h, w, _host_perm(perm), _STRATEGIES[strategy], mode, thr,
+              eps, _lib.ptr(tm), _lib.ptr(tb), _lib.ptr(hm), _lib.ptr(coords), _lib.ptr(img), _lib.ptr(packed),
+              _lib.ptr(index), _lib.ptr(cov_image))
+    st = dnn._stats_dict(packed, index, (B, J))
+    st['cov_image'] = cov_image
+    return img, coords, hm, st
 
 
 def _last(out):
@@ -133,6 +183,12 @@ def _is_hourglass(model):
     return isinstance(model, HourglassHumanPoseModel)
 
 
+def _predicted_map(model):
+    """The heat-map the returned coordinates come from: the LAST stack's for an hourglass (`model.heatmaps` is the
+    first stack's, a quirk kept from the reference)."""
+    return model.heatmaps_array[-1] if _is_hourglass(model) else model.heatmaps
+
+
 def _set_heatmaps(model, hm):
     if _is_hourglass(model):
         model.heatmaps_array = [hm]           # `model.heatmaps` is heatmaps_array[0]
@@ -140,7 +196,8 @@ def _set_heatmaps(model, hm):
         model.heatmaps = hm
 
 
-def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=False, return_normalized=False):
+def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=False, return_normalized=False,
+            return_stats=False):
     """Joint positions in original-image pixels for a batch, on the device: f64 `[B, J, 2]`.
 
     `inputs` f32 `[B, 3, S, S]` on the device, or with `paired=True` the `[2B, 3, S, S]` `input_pair` of
@@ -153,7 +210,13 @@ def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=Fa
         `forward_part2`, then `baddbmm`.
       * otherwise: `forward`, the device-side `compute_coords` and `baddbmm`.
     The model is put in eval mode.  Nothing synchronises with the host.  `model.heatmaps` holds the (merged)
-    heat-maps afterwards.  `return_normalized=True` returns `(image_coords, normalised f32 coords)`."""
+    heat-maps afterwards.  `return_normalized=True` returns `(image_coords, normalised f32 coords)`.
+    `return_stats=True` appends the statistics dict of `STATS_DOC` to the result (coordinates unchanged bit for bit),
+    still without a host synchronisation.  It describes the map the coordinates come from:
+      * flip, 'dsnt' / 'gauss': from the fused launch itself (`dsnt_flip_merge_head_stats`);
+      * flip, 'fc': `dsnt_heatmap_stats` on the post-activation map of the merged logits;
+      * no flip: `dsnt_heatmap_stats` on the last stack's heat-maps (for an hourglass NOT `model.heatmaps`, which is the
+        first stack's) after the forward."""
     model.eval()
     S = 2 if (use_flipped and paired) else 1
     if inputs.size(0) % S:
@@ -167,7 +230,7 @@ def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=Fa
             logits = _last(model.forward_part1(pair))
             strat = model.output_strat
             if strat in _STRATEGIES:
-                img, coords, hm = flip_merge_head(logits, tm, tb, strat, model.preact)
+                img, coords, hm, *st = flip_merge_head(logits, tm, tb, strat, model.preact, stats=return_stats)
                 _set_heatmaps(model, hm)
             else:
                 hm1, hm2 = logits.split(B)
@@ -176,32 +239,45 @@ def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=Fa
                 # a bare tensor would be iterated per sample by the hourglass head (the reference's batch-1 quirk)
                 coords = _last(model.forward_part2([hm] if _is_hourglass(model) else hm)).detach().float()
                 img = torch.baddbmm(tb, coords.double(), tm)
+                st = [_map_stats(_predicted_map(model), tm)] if return_stats else []
         else:
             out = _last(model(inputs))
             coords = dutil.decode_heatmaps(out) if model.output_strat == 'gauss' else out.detach().float()
             img = torch.baddbmm(tb, coords.double(), tm)
-    return (img, coords) if return_normalized else img
+            st = [_map_stats(_predicted_map(model), tm, model.output_strat != 'gauss')] if return_stats else []
+    res = (img, coords) if return_normalized else (img,)
+    res += tuple(st)
+    return res if len(res) > 1 else res[0]
 
 
-def predict_dataset(model, dataset, use_flipped=True, batch_size=32, time_meter=None):
+def predict_dataset(model, dataset, use_flipped=True, batch_size=32, time_meter=None, return_stats=False):
     """`generate_predictions` at any batch size: a CPU DoubleTensor `[len(dataset), J, 2]` of joint positions in
     original-image pixels, per sample what the batch-1 flip loop gives.  Predictions stay on the device until the
-    one copy at the end; with a `time_meter` each batch is timed, which synchronises once per batch."""
+    one copy at the end; with a `time_meter` each batch is timed, which synchronises once per batch.
+    `return_stats=True` returns `(predictions, stats)`: the statistics dict of `STATS_DOC` over the whole dataset as CPU
+    tensors, concatenated on the device and copied once like the predictions."""
     model.cuda()
     model.eval()
     loader = DataLoader(dataset, batch_size, num_workers=0)
-    preds = []
+    preds, stats = [], []
     for batch in loader:
         start = time.perf_counter()
         img = predict(model, batch['input'].cuda(), batch['transform_m'].cuda(), batch['transform_b'].cuda(),
-                      use_flipped=use_flipped)
+                      use_flipped=use_flipped, return_stats=return_stats)
+        if return_stats:
+            img, st = img
+            stats.append(st)
         if time_meter is not None:
             torch.cuda.synchronize()
             time_meter.add(time.perf_counter() - start)
         preds.append(img)
     if not preds:
-        return torch.zeros(0, 16, 2, dtype=torch.float64)
-    return torch.cat(preds, 0).cpu()
+        empty = torch.zeros(0, 16, 2, dtype=torch.float64)
+        return (empty, {}) if return_stats else empty
+    out = torch.cat(preds, 0).cpu()
+    if not return_stats:
+        return out
+    return out, {k: torch.cat([s[k] for s in stats], 0).cpu() for k in stats[0]}
 
 
 _box_augment = {}
@@ -220,7 +296,8 @@ def _box_augment_for(specs, mean, std, device):
     return aug
 
 
-def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_size=384, return_normalized=False):
+def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_size=384, return_normalized=False,
+                  return_stats=False):
     """Joint positions in original-image pixels for person boxes in full images: f64 `[B, J, 2]` on the device.
 
     `pool` a `data.ImagePool`; sample b is image `idx[b]` (int64 `[B]`) with the box matrix `matrix[b]` (f64
@@ -233,7 +310,10 @@ def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_si
     boxes); here `transform_m` is passed transposed, so the result is `inverse(matrix) . [x, y, 1]` for any invertible
     matrix, and bit for bit what `predict` gives on axis-aligned boxes.  A sample without a crop (index outside the
     pool, singular matrix) comes out NaN.  Nothing synchronises with the host (the first call on a device uploads the
-    normalisation constants).  `return_normalized=True` returns `(image_coords, normalised f32 coords)`."""
+    normalisation constants).  `return_normalized=True` returns `(image_coords, normalised f32 coords)`.
+    `return_stats=True` appends the statistics dict of `STATS_DOC`; `cov_image` follows the transposed `transform_m`, so
+    it is in the image's pixels for any invertible box matrix, and a sample without a crop has NaN statistics (its
+    `peak_index` is -1)."""
     crops, valid = pool.crop(idx, matrix, crop_size)
     B, dev = crops.shape[0], crops.device
     aug = _box_augment_for(model.image_specs, mean, std, dev)
@@ -244,9 +324,13 @@ def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_si
     m = matrix.to(torch.float64).contiguous()
     s = aug(crops, kp, km, m, hl, 0, flip_pair=use_flipped)
     tm = s['transform_m'].transpose(1, 2).contiguous()
-    img, coords = predict(model, s['input_pair'] if use_flipped else s['input'], tm, s['transform_b'],
-                          use_flipped=use_flipped, paired=use_flipped, return_normalized=True)
+    img, coords, *st = predict(model, s['input_pair'] if use_flipped else s['input'], tm, s['transform_b'],
+                               use_flipped=use_flipped, paired=use_flipped, return_normalized=True,
+                               return_stats=return_stats)
     img = torch.where(valid.view(B, 1, 1), img, float('nan'))
-    if not return_normalized:
-        return img
-    return img, torch.where(valid.view(B, 1, 1), coords, float('nan'))
+    res = (img, torch.where(valid.view(B, 1, 1), coords, float('nan'))) if return_normalized else (img,)
+    if return_stats:
+        def mask(t):
+            return torch.where(valid.view(B, *([1] * (t.dim() - 1))), t, -1 if t.dtype == torch.int32 else float('nan'))
+        res += ({k: mask(v) for k, v in st[0].items()},)
+    return res if len(res) > 1 else res[0]

@@ -72,6 +72,35 @@ def dsnt(heatmaps):
     return _Dsnt.apply(heatmaps)
 
 
+# ------------------------------------------------------------------ per-joint statistics of heat-maps
+def _stats_dict(stats, index, lead):
+    """The packed kernel outputs (`stats` f32 [rows, 7], `index` int32 [rows]) as the public dict of views."""
+    st = stats.view(*lead, 7)
+    return {'peak': st[..., 0], 'peak_index': index.view(*lead), 'mass': st[..., 1], 'mean': st[..., 2:4],
+            'cov': st[..., 4:7]}
+
+
+def heatmap_stats(heatmaps):
+    """Per-joint statistics of post-activation heat-maps `[..., H, W]` (`dsnt_heatmap_stats`, one read of the maps).
+
+    A dict of device tensors over the leading dimensions `[...]`, all views of two buffers:
+      * `peak` f32 `[...]`: the largest pixel, and `peak_index` int32 `[...]`: the first flat index `y * W + x` holding it;
+      * `mass` f32 `[...]`: the sum of the map (1 for softmax, not for the other preactivations or raw maps);
+      * `mean` f32 `[..., 2]`: `(sum X p, sum Y p)` on the DSNT grid, bit for bit what `dsnt(heatmaps)` returns;
+      * `cov` f32 `[..., 3]`: `(vxx, vyy, vxy)`, the second central moments about that mean in normalised units.
+    Nothing is calibrated: `peak` (confidence) and the spread `sqrt(vxx + vyy)` are the two quantities to threshold on.
+    Forward only: the result carries no gradient, whatever `heatmaps` requires.  Device tensors only."""
+    hm = f32(heatmaps.detach()).contiguous()
+    if hm.dim() < 2:
+        raise RuntimeError('dsnt: heatmap_stats needs [..., H, W], got %s' % (tuple(hm.shape),))
+    h, w = hm.shape[-2], hm.shape[-1]
+    rows = _rows(hm, 2)
+    stats = torch.empty(rows, 7, device=hm.device, dtype=torch.float32)
+    index = torch.empty(rows, device=hm.device, dtype=torch.int32)
+    call('dsnt_heatmap_stats', ptr(hm), rows, h, w, ptr(stats), ptr(index))
+    return _stats_dict(stats, index, hm.shape[:-2])
+
+
 # ------------------------------------------------------------------ 'fc' output strategy (model.py:222-223, 293-303)
 class _Fc2(Function):
     @staticmethod

@@ -153,6 +153,26 @@ int dsnt_head_fwd(const float* logits, float* hm, float* coords, int64_t rows, i
 int dsnt_flip_merge_head(const float* logits, int64_t B, int J, int h, int w, const int* perm, int strategy,
                          int preact, float threshold, float eps, const double* transform_m, const double* transform_b,
                          float* hm, float* coords, double* img, void* stream);
+/* Per-joint statistics of heat-maps (a confidence and a spread for every predicted joint).  hm f32 [rows][h][w], the
+ * post-activation maps.  With the DSNT grid X = (2x + 1)/w - 1, Y = (2y + 1)/h - 1, per row:
+ *   stats f32 [rows][7] = peak (max p), mass (sum p), mx = sum X p, my = sum Y p (dsnt_expect_fwd's values bit for bit),
+ *                         vxx = sum (X - mx)^2 p, vyy = sum (Y - my)^2 p, vxy = sum (X - mx)(Y - my) p (a second sweep
+ *                         about the mean, not raw moments);
+ *   peak_index int32 [rows] = the first index y w + x that holds the peak (NaN is never the peak; 0 when nothing is
+ *                         above -inf).
+ * Forward only.  Maps as dsnt_expect_fwd accepts; rows of up to 4096 pixels are read once.  dsnt_version() >= 120. */
+int dsnt_heatmap_stats(const float* hm, int64_t rows, int h, int w, float* stats, int* peak_index, void* stream);
+/* dsnt_flip_merge_head with the statistics of the merged heat-maps from the same launch (no second read of the logits
+ * for rows of up to 4096 pixels; longer rows read them twice).  coords, img and hm are dsnt_flip_merge_head's bit for bit.
+ * stats [B J][7] and peak_index [B J] as dsnt_heatmap_stats gives them on hm (bit for bit, except mass, mean and cov of
+ * softmax rows whose width is a multiple of 4, which are summed in the coordinates' order: fp32 rounding); cov_image f64 [B J][2][2] = M^T S M with
+ * S = [[vxx, vxy], [vxy, vyy]] and M = transform_m[b]: the covariance of the joint in original-image pixels^2
+ * (sqrt(trace) is its spread in pixels).  DSNT_FLIP_GAUSS: peak, peak_index and mass of the merged map as it is, the
+ * rest NaN.  All three outputs are required.  dsnt_version() >= 120. */
+int dsnt_flip_merge_head_stats(const float* logits, int64_t B, int J, int h, int w, const int* perm, int strategy,
+                               int preact, float threshold, float eps, const double* transform_m,
+                               const double* transform_b, float* hm, float* coords, double* img, float* stats,
+                               int* peak_index, double* cov_image, void* stream);
 /* Fused head, loss: model.py:233-246 — per-row Euclidean distance and regulariser value
  * (reg_kind -1 = none) from the saved heat-maps; reductions by dsnt_masked_avg_fwd. */
 int dsnt_head_loss_rows(const float* hm, const float* coords, const float* target,
