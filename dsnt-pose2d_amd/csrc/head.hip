@@ -910,15 +910,20 @@ __global__ __launch_bounds__(HB) void head_loss_reduce_kernel(const float* __res
     }
 }
 
-// x *= s[0] unless s[0] == 1 (then the kernel returns at once: the usual `loss.backward()` costs no memory pass)
-__global__ void scale_by_scalar_kernel(float4* __restrict__ x, const float* __restrict__ s, long n4) {
+// x *= s[0] unless s[0] == 1 (then the kernel returns at once: the usual `loss.backward()` costs no memory pass).
+// n4 16-byte vectors (0 when x is not 16-byte aligned), then the n - 4 n4 elements behind them one by one: the logits of
+// a single 7 x 7 row are 49 floats
+__global__ void scale_by_scalar_kernel(float* __restrict__ x, const float* __restrict__ s, long n4, long n) {
     const float a = s[0];
     if (a == 1.f) return;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        float4 v = x[i];
+    const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x, step = (long)gridDim.x * blockDim.x;
+    float4* x4 = reinterpret_cast<float4*>(x);
+    for (long i = t0; i < n4; i += step) {
+        float4 v = x4[i];
         v.x *= a; v.y *= a; v.z *= a; v.w *= a;
-        x[i] = v;
+        x4[i] = v;
     }
+    for (long i = 4 * n4 + t0; i < n; i += step) x[i] *= a;
 }
 
 // ------------------------------------------------------------------ host wrappers
@@ -1261,11 +1266,11 @@ extern "C" int dsnt_head_loss_reduce(const float* dist, const float* reg_row, co
 }
 
 extern "C" int dsnt_scale_by_scalar(float* x, const float* s, int64_t n, void* stream) {
-    DSNT_REQUIRE(x && s && n > 0 && n % 4 == 0 && dsnt_aligned16(x), DSNT_ERR_ARG,
-                 "dsnt_scale_by_scalar: n must be a positive multiple of 4, x 16-byte aligned");
-    long gsz = (n / 4 + 255) / 256;
+    DSNT_REQUIRE(x && s && n > 0, DSNT_ERR_ARG, "dsnt_scale_by_scalar: null pointer or n <= 0");
+    const long n4 = dsnt_aligned16(x) ? (long)(n / 4) : 0;
+    long gsz = ((n4 ? n4 : (long)n) + 255) / 256;
     if (gsz > 4096) gsz = 4096;
-    DSNT_LAUNCH(scale_by_scalar_kernel, dim3((unsigned)gsz), dim3(256), 0, (hipStream_t)stream, (float4*)x, s, (long)(n / 4));
+    DSNT_LAUNCH(scale_by_scalar_kernel, dim3((unsigned)gsz), dim3(256), 0, (hipStream_t)stream, x, s, n4, (long)n);
     DSNT_CHECK_LAUNCH("dsnt_scale_by_scalar");
 }
 

@@ -193,7 +193,8 @@ int dsnt_head_loss_grad(const float* hm, const float* coords, const float* targe
  * e2 = {masked_average(dist), denominator} as dsnt_masked_avg_fwd leaves it. */
 int dsnt_head_loss_reduce(const float* dist, const float* reg_row, const float* mask, const float* denom2,
                           float reg_coeff, float* loss, float* e2, int64_t rows, void* stream);
-/* x[0..n) *= s[0] (device scalar); returns at once when s[0] == 1. */
+/* x[0..n) *= s[0] (device scalar); returns at once when s[0] == 1.  Any n > 0 and any alignment of x (16-byte stores
+ * where x allows them); dsnt_version() >= 121, earlier versions refuse n % 4 != 0 and unaligned x. */
 int dsnt_scale_by_scalar(float* x, const float* s, int64_t n, void* stream);
 /* Fused head, backward: d loss / d logits in one pass, given per-row upstream factors
  * g_dist[row] (for the Euclidean term) and g_reg[row] (for the regulariser), i.e.

@@ -257,9 +257,9 @@ def test_fused_head_upstream_gradient_and_second_backward(dev):
     assert abs(l3.item() - loss.item()) <= 1e-5 * abs(loss.item())
 
 
-@pytest.mark.parametrize('h,w', [(5, 5), (7, 7), (14, 14), (28, 28), (8, 8), (64, 48), (96, 96)])
+@pytest.mark.parametrize('h,w', [(5, 5), (7, 7), (14, 14), (28, 28), (8, 8), (64, 48), (96, 96), (4, 1024)])
 def test_odd_shapes(dev, h, w):
-    """Ragged / unaligned rows (ResNet heat-maps 7..28, H*W not a multiple of 4, > 4096)."""
+    """Ragged / unaligned rows (ResNet heat-maps 7..28, H*W not a multiple of 4, > 4096, W + H > HEAD_SEP_MAX)."""
     import dsnt.nn as dn
     from dsnt_oracle import nn as onn, model as omodel
     x = synthetic.tensor('odd', (3, 16, h, w), seed=h * 100 + w) * 2
