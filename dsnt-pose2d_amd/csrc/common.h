@@ -119,7 +119,7 @@ __device__ __forceinline__ void block_sum(float (&v)[NV], float* red) {
         v[i] = s;
     }
 }
-// fp16x3 operand bounds: raise the 64-slot bound `amax` (see bound64 in conv.hip) to this 256-thread workgroup's
+// fp16x3 operand bounds: raise the 64-slot bound `amax` (see bound64 in conv_split.h) to this 256-thread workgroup's
 // max |value|: wave shuffles, four LDS floats, ONE fire-and-forget integer atomic on the float bits per workgroup,
 // slot = workgroup index mod 64 (order-independent: the result is bit-reproducible).
 // (`which` = 0 / 1: two commits in a row use separate LDS floats, so the second needs no barrier against the first)

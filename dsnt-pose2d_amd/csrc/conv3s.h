@@ -1,4 +1,4 @@
-// Internal interface of the symmetric 3x3 convolution kernel (conv3s.hip), used by the dispatch in conv.hip.
+// Internal interface of the symmetric 3x3 convolution kernel (conv3s.hip), used by the dispatch in conv_split6.hip.
 #pragma once
 #include "conv_split.h"
 

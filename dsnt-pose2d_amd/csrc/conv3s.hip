@@ -1,5 +1,5 @@
 // 3x3 / stride 1 / pad 1 convolutions of the full-resolution levels (hourglass.py:22-23: conv2 of every Bottleneck, forward
-// and as data gradients) on the fp16 matrix cores, fp16x3 split — the SYMMETRIC successor of conv3x3_bf16x6_kernel (conv.hip).
+// and as data gradients) on the fp16 matrix cores, fp16x3 split — the SYMMETRIC successor of conv3x3_bf16x6_kernel (conv_split6.hip).
 //
 // What that kernel lost (profiles/r02_timeline_halo.txt, r02_pmc_issue_accounting.txt): its four loader waves share the
 // SIMDs with the four MFMA waves, lose the issue arbitration against them and arrive last at 80 % of the per-K-step

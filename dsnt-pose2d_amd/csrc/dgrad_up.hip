@@ -10,7 +10,7 @@
 // Against dsnt_zero_insert + the stride-1 kernel (round 1..2) that is 1 / stride^2 of the multiply-adds, no
 // stride^2-times-dY scratch tensor and one launch instead of two.
 //
-// Kernel: the K-split form of conv.hip (conv_ksplit_kernel) — these launches have few rows and long reductions.  A
+// Kernel: the K-split form of conv_f32.hip (conv_ksplit_kernel) — these launches have few rows and long reductions.  A
 // 512-thread workgroup owns one 32 x 32 tile (32 pixels of ONE phase x 32 channels of dX); its eight waves split the
 // phase's reduction (taps x Cout, 16 channels at a time), every lane streaming its operands straight from memory into
 // v_mfma_f32_32x32x2_f32 (exact fp32: the results match the stuffed path to accumulation order), the eight partial
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(512) void conv_dgrad_up_kernel(UpP p) {
     // weight row of this lane
     const int nb = ntile * 32 + i;
     // a lane owns row i and CW / 2 = 8 consecutive k values of a 16-wide chunk: two adjacent 16-byte loads per operand, so
-    // that a row's two lanes use 64 bytes of a line at once (conv_ksplit_kernel in conv.hip has the measurements)
+    // that a row's two lanes use 64 bytes of a line at once (conv_ksplit_kernel in conv_f32.hip has the measurements)
     constexpr int CW = 16, NL = CW / 8;
     const int kl = (CW / 2) * h;
     const unsigned boff = nb < p.Cx ? (unsigned)((size_t)nb * p.K + kl) * 4u : OOB;

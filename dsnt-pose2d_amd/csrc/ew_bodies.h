@@ -1,5 +1,5 @@
 // Bodies of the small NHWC kernels that can also run inside a persistent stage (stage.h): device functions of a VIRTUAL workgroup
-// index, so that the stand-alone launch (elementwise.hip) and the stage's loop (conv.hip) execute the same instructions.  Each is
+// index, so that the stand-alone launch (elementwise.hip) and the stage's loop (conv_f32.hip) execute the same instructions.  Each is
 // written for 256 live threads; in a 512-thread stage workgroup the upper half skips the work and keeps the barriers.
 #pragma once
 #include "common.h"

@@ -1,4 +1,4 @@
-// Internal interface of the streaming 1x1 convolution kernel (gemm1.hip), used by the dispatch in conv.hip.
+// Internal interface of the streaming 1x1 convolution kernel (gemm1.hip), used by the dispatch in conv_split6.hip.
 #pragma once
 #include "conv_split.h"
 

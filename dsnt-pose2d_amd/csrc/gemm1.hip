@@ -2,7 +2,7 @@
 // data gradients; :104-148 the lin / score convolutions) on the fp16 matrix cores, fp16x3 split, as a STREAMING kernel.
 //
 // These launches are HBM-bound by a wide margin (128->256 @64x64, batch 32: 335 MB per launch, 8.6 GFLOP = 10 us of
-// matrix pipe) — what the tiled implicit-GEMM kernel (conv.hip) loses on them is memory-level parallelism and issue
+// matrix pipe) — what the tiled implicit-GEMM kernel (conv_split6.hip) loses on them is memory-level parallelism and issue
 // slots: a 128 x 128 tile lives ~46 k cycles for 3 k cycles of MFMA, its loader waves hold two 8 KB K-steps in
 // flight, every A element is transformed once per 128-column tile and every output element crosses LDS to be
 // re-shaped for 16-byte stores.  Here:
@@ -16,7 +16,7 @@
 //   * the EPILOGUE works from the MFMA result layout as it stands: a register is 2 rows x 32 consecutive columns, i.e.
 //     two 128-byte runs — residuals are loaded and results stored as full lines by dword accesses, bias / BatchNorm
 //     vectors are per-lane scalars (lane = column), column sums need no transposition.
-// Same contract as conv_fwd_bf16x6_kernel<..., F16> (conv.hip): BN+ReLU prologue, bias, two residuals, per-128-row
+// Same contract as conv_fwd_bf16x6_kernel<..., F16> (conv_split6.hip): BN+ReLU prologue, bias, two residuals, per-128-row
 // column statistics, the BatchNorm-backward epilogue of data-gradient launches, the bounds of dsnt_out_bounds.
 #include "gemm1.h"
 #include <stdlib.h>

@@ -1,4 +1,4 @@
-// Internal interface of the halo weight-gradient kernels (wgrad3.hip), used by the dispatch in conv.hip.
+// Internal interface of the halo weight-gradient kernels (wgrad3.hip), used by the dispatch in conv_wgrad.hip.
 #pragma once
 #include "common.h"
 

@@ -1,9 +1,9 @@
 // Weight gradient of the 3x3 / stride 1 / pad 1 convolutions (hourglass.py:22-23, the conv2 of every Bottleneck) on the
-// fp16 matrix cores, fp16x3 split (conv.hip: "fp16x3"), as a HALO kernel:
+// fp16 matrix cores, fp16x3 split (conv_split.h: "fp16x3"), as a HALO kernel:
 //
 //   dW[n][tap][c] = sum over pixels  A[pixel + tap][c] * dY[pixel][n],   A = relu(bn(x)) (zero outside the image)
 //
-// The implicit-GEMM weight gradient (conv.hip) gives each (tap, 128-channel) k-tile its own workgroup: every input
+// The implicit-GEMM weight gradient (conv_wgrad.hip) gives each (tap, 128-channel) k-tile its own workgroup: every input
 // element is BatchNorm-transformed, split and TRANSPOSED nine times, every dY element nine times too — 12 VALU
 // instructions per MFMA on a kernel whose bound is the SIMD's issue port.  Here a workgroup owns 64 input channels x
 // ALL nine taps x 128 (or 64) output channels for a strip of pixels:

@@ -221,7 +221,6 @@ PLAIN = {
     'dsnt_conv_wgrad_desc_bytes': (I, []),
     'dsnt_conv_wgrad_desc': (I, [P, P, P, I, P, P, GP, P]),
     'dsnt_conv_wgrad_desc_f16x3': (I, [P, P, P, I, P, P, P, P, GP, P]),
-    'dsnt_debug_set_timeline': (I, [P, I]),
 }
 
 _lib = None

@@ -10,8 +10,8 @@
  * Conventions
  *  - plain pointers + sizes; every pointer is DEVICE memory owned by the caller
  *    (PyTorch's allocator); the library allocates nothing and the product entry points
- *    declared here keep no state except a thread-local error string (the calibration /
- *    timeline diagnostics live in dsnt_hip_debug.h, are not part of this ABI and are the
+ *    declared here keep no state except a thread-local error string (the calibration
+ *    probes and debug switches live in dsnt_hip_debug.h, are not part of this ABI and are the
  *    only code with process-wide switches);
  *  - all arithmetic is fp32; activations are NHWC ([N][H][W][C], C innermost);
  *    conv weights are OHWI ([Cout][R][S][Cin]); heat-maps for the DSNT head are
@@ -272,7 +272,7 @@ int dsnt_conv_fwd_bf16x6_ex(const float* x, const void* w_planes, int64_t plane_
                             void* stream);
 
 /* fp16x3 variant: x * s = h1 + h2 on TWO fp16 planes after a power-of-two scale, three MFMAs per product (error vs
- * fp64 below a plain fp32 GEMM's: conv.hip, tools/split_numerics.py).  a_bound / w_bound are DEVICE scalars >= the
+ * fp64 below a plain fp32 GEMM's: conv_split.h, tools/split_numerics.py).  a_bound / w_bound are DEVICE scalars >= the
  * largest |value| of the A operand AFTER its BN+ReLU prologue (or of x when there is none) and of the weights; the
  * kernels derive the scales from them (pow2: bound * scale in [2^13, 2^14)), so a loose bound is fine and a bound
  * that is too SMALL overflows fp16.  w_planes: two fp16 planes made by dsnt_split_f16x2 with the SAME w_bound.

@@ -1,9 +1,9 @@
 /*
- * dsnt_hip_debug.h — calibration probes and kernel-timeline switches of libdsnt_hip.so.
+ * dsnt_hip_debug.h — calibration probes and debug switches of libdsnt_hip.so.
  *
  * NOT part of the product ABI (include/dsnt_hip.h): nothing on the dsnt-pose2d hot path calls these; they exist
- * for tools/ (peak-rate calibration, issue-starvation probe, in-kernel s_memtime timelines) and, unlike the
- * product entry points, dsnt_debug_set_timeline / dsnt_debug_force_gemm6 flip process-wide switches.
+ * for tools/ (peak-rate calibration, issue-starvation probe) and, unlike the product entry points,
+ * dsnt_debug_force_gemm6 flips a process-wide switch.
  */
 #ifndef DSNT_HIP_DEBUG_H
 #define DSNT_HIP_DEBUG_H
@@ -16,9 +16,6 @@ extern "C" {
  * sustained v_mfma_f32_32x32x2_f32 rate of this device
  * (blocks x threads, `iters` x 16 MFMAs per wave; dep = 1 independent / 4 dependent chains). */
 int dsnt_debug_mfma_peak(float* out, int blocks, int threads, int iters, int dep, void* stream);
-/* Debug timeline of the conv kernel: lane 0 of every wave of workgroup `block` stamps s_memtime
- * into buf[wave*128 + slot] (buf = 8*128 int64 on the device; NULL switches it off). */
-int dsnt_debug_set_timeline(long long* buf, int block);
 /* MFMA / VALU co-execution probe (512-thread blocks: 4 MFMA waves + 4 v_fma waves). */
 int dsnt_debug_coexec(float* out, int blocks, int mfma_iters, int valu_iters, void* stream);
 /* bf16 MFMA rate (v_mfma_f32_32x32x16_bf16) and its co-execution with VALU (threads 256 or 512). */

@@ -1,5 +1,5 @@
 """The fp16x3 default is only safe while every operand bound dominates its operand (an fp16 overflow would be
-fatal: csrc/conv.hip `pow2_scale` leaves 4x head-room and nothing else).  These tests walk a FULL-SIZE train step
+fatal: csrc/conv_split.h `pow2_scale` leaves 4x head-room and nothing else).  These tests walk a FULL-SIZE train step
 launch by launch — hg2 batch 32 and hg8 batch 16 at 256 px (BASELINE configs 3 and 5), hg1 batch 32 (config 2) —
 and, right before every fp16x3 launch, hold each bound slot against the tensor it must dominate AS IT IS AT THAT
 MOMENT (gradient buffers are donated and accumulated into, so the end-of-step content is not what a consumer read):

@@ -8,7 +8,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADERS = [os.path.join(ROOT, 'include', 'dsnt_hip.h'),          # the product ABI
-           os.path.join(ROOT, 'include', 'dsnt_hip_debug.h')]    # calibration / timeline diagnostics (tools/ only)
+           os.path.join(ROOT, 'include', 'dsnt_hip_debug.h')]    # calibration probes and debug switches (tools/ only)
 
 
 def _declared(headers=HEADERS):
@@ -46,6 +46,14 @@ def test_argument_validation_without_gpu():
     g = _lib.ConvGeom(1, 8, 8, 8, 8, 8, 8, 3, 3, 1, 1, 1)
     rc = lib.dsnt_conv_fwd(None, None, None, None, None, None, 0, None, None, None, C.byref(g), None)
     assert rc == 3 and b'null' in lib.dsnt_last_error()
+    # the split-precision entry point checks its arguments through the same helper, in the same order
+    fwd6 = lambda g: lib.dsnt_conv_fwd_bf16x6(None, None, 0, None, None, None, None, 0, None, None, None, C.byref(g), None)
+    rc = fwd6(_lib.ConvGeom(1, 8, 8, 6, 8, 8, 8, 1, 1, 1, 0, 1))            # Cin % 4 != 0
+    assert rc == 2 and b'dsnt_conv_fwd_bf16x6: Cin=6 must be a multiple of 4' in lib.dsnt_last_error()
+    rc = fwd6(_lib.ConvGeom(1, 8, 8, 16, 7, 8, 8, 3, 3, 1, 1, 1))           # inconsistent output size
+    assert rc == 1 and b'dsnt_conv_fwd_bf16x6: output 7x8 inconsistent' in lib.dsnt_last_error()
+    rc = fwd6(_lib.ConvGeom(1, 8, 8, 16, 8, 8, 8, 3, 3, 1, 1, 1))           # a geometry the kernels take, null tensors
+    assert rc == 3 and b'dsnt_conv_fwd_bf16x6: null tensor' in lib.dsnt_last_error()
     assert lib.dsnt_head_fwd(None, None, None, 4, 8, 8, None) == 3
     assert lib.dsnt_reg_fwd(None, None, None, 4, 8, 8, 0.1, 9, None) == 3
     assert lib.dsnt_maxpool2_fwd(C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), 1, 7, 8, 4, None) == 1

@@ -401,7 +401,7 @@ WGRAD_CASES = {
     # name: (N, H, W, Cin, Cout, k, stride, pad, dil) of dsnt_conv_wgrad_f16x3, and the kernel it reaches
     'wgrad3': (2, 16, 16, 64, 64, 3, 1, 1, 1),       # 3x3 / stride 1: the halo kernel (csrc/wgrad3.hip)
     'wgrad1': (2, 128, 128, 64, 64, 1, 1, 0, 1),     # 1x1 of >= 16384 rows (csrc/wgrad1.hip)
-    'generic': (2, 16, 16, 64, 128, 3, 2, 1, 1),     # stride 2: the generic split kernel (csrc/conv.hip)
+    'generic': (2, 16, 16, 64, 128, 3, 2, 1, 1),     # stride 2: the generic split kernel (csrc/conv_split6.hip)
     'stem4': (2, 33, 33, 16, 64, 4, 1, 1, 1),        # the space-to-depth stem (csrc/stem4.hip), a raw operand
 }
 WGRAD_ROUTE = {'wgrad3': 2, 'wgrad1': 3, 'generic': 0, 'stem4': 1}       # dsnt_conv_f16x3_route(g, 1)

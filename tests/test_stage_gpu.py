@@ -92,7 +92,7 @@ def test_stage_first_step_of_a_cold_process_hg8(tmp_path, monkeypatch):
     """The case that exposed the one real bug of the stage: the FIRST step of hg8 at batch 16 in a fresh process.  `__syncthreads()`
     fences LDS only, so a wave could wait in the stage's barrier with global stores still in flight while lane 0 announced the launch
     as done — a workgroup on another XCD then read stale bytes (3 % error in ONE layer's gradients, found by running the whole suite
-    under DSNT_STAGE=1).  Every wave now releases at agent scope in front of the barrier (csrc/conv.hip `stage_barrier`); this run
+    under DSNT_STAGE=1).  Every wave now releases at agent scope in front of the barrier (csrc/conv_f32.hip `stage_barrier`); this run
     compares every gradient of that first step, stage on against off, bit for bit, each in a child process of its own."""
     import test_fallback_gpu as tf
     monkeypatch.setenv('DSNT_STAGE', '1')
