@@ -86,8 +86,18 @@ __global__ __launch_bounds__(HB) void heatmap_mse_bwd_kernel(const float* __rest
     }
 }
 
+// torch.max's order on (value, index) pairs: does (ov, oi) come before (v, i)?  NaN above every number, NaN beside NaN
+// and equal numbers by the lower index.  Without a NaN this is `ov > v || (ov == v && oi < i)`.
+__device__ __forceinline__ bool argmax_before(float ov, int oi, float v, int i) {
+    const bool on = ov != ov, vn = v != v;
+    if (on || vn) return on && (!vn || oi < i);
+    return ov > v || (ov == v && oi < i);
+}
+
 // util.py:150-198: first arg-max pixel, (0, 0) when the maximum is not positive, +-0.25 px towards the larger
 // neighbour for interior pixels, then pixel -> normalised coordinates ((p + 0.5) * (2/size) - 1, fp32 steps).
+// The arg-max is torch.max's: a NaN is the maximum and the first NaN's index the arg-max, so a row that holds a NaN
+// decodes to pixel (0, 0) (`peak` NaN is not positive) with `index` at its first NaN.
 // One row read from `x` (a `const float*`, or the flip-merged logits of dsnt_flip_merge_head: FlipSrc); thread 0 returns
 // true with the coordinates in (cx, cy), the maximum in `peak` and its first index in `index`.  `seen(v)` is called with
 // every value a thread reads (the statistics of dsnt_flip_merge_head_stats take the row's sum there).
@@ -101,21 +111,22 @@ __device__ __forceinline__ bool decode_row(const SRC& x, int h, int w, int use_n
     for (int i = threadIdx.x; i < h * w; i += HB) {
         const float v = x[i];
         seen(v);
-        if (v > best) { best = v; bi = i; }            // ascending i per thread: keeps the first maximum
+        // ascending i per thread: keeps the first maximum, and the first NaN once one is met
+        if (v > best || (v != v && best == best)) { best = v; bi = i; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        if (argmax_before(ov, oi, best, bi)) { best = ov; bi = oi; }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { rv[wave] = best; ri[wave] = bi; }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int wv = 1; wv < HB / 64; ++wv)
-            if (rv[wv] > best || (rv[wv] == best && ri[wv] < bi)) { best = rv[wv]; bi = ri[wv]; }
-        if (bi == 0x7fffffff) bi = 0;                    // all -inf / NaN rows
+            if (argmax_before(rv[wv], ri[wv], best, bi)) { best = rv[wv]; bi = ri[wv]; }
+        if (bi == 0x7fffffff) bi = 0;                    // all -inf rows
         peak = best; index = bi;
         float px = (float)(bi % w), py = (float)(bi / h);          // `idx / height` as the reference (util.py:161)
         if (!(best > 0.f)) { px = 0.f; py = 0.f; }

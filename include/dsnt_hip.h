@@ -168,7 +168,9 @@ int dsnt_heatmap_stats(const float* hm, int64_t rows, int h, int w, float* stats
  * softmax rows whose width is a multiple of 4, which are summed in the coordinates' order: fp32 rounding); cov_image f64 [B J][2][2] = M^T S M with
  * S = [[vxx, vxy], [vxy, vyy]] and M = transform_m[b]: the covariance of the joint in original-image pixels^2
  * (sqrt(trace) is its spread in pixels).  DSNT_FLIP_GAUSS: peak, peak_index and mass of the merged map as it is, the
- * rest NaN.  All three outputs are required.  dsnt_version() >= 120. */
+ * rest NaN; peak and peak_index are the decode's own arg-max, so there a NaN in the map IS the peak (peak NaN,
+ * peak_index its first NaN: dsnt_decode_heatmaps' rule, not dsnt_heatmap_stats').  All three outputs are required.
+ * dsnt_version() >= 120. */
 int dsnt_flip_merge_head_stats(const float* logits, int64_t B, int J, int h, int w, const int* perm, int strategy,
                                int preact, float threshold, float eps, const double* transform_m,
                                const double* transform_b, float* hm, float* coords, double* img, float* stats,
@@ -488,7 +490,9 @@ int dsnt_conv_dgrad_f16x3_stream_apply(const float* dz, const dsnt_bn_bwd_apply*
  * dsnt_heatmap_mse_bwd: dhm = gscale[0] * 2 / (rows*h*w) * (hm - encode(target)); gscale is a device scalar.
  * dsnt_decode_heatmaps: util.py:150-198 (get_preds + decode_heatmaps): first arg-max pixel ((0,0) when the
  *   maximum is not positive; y = index / h as the reference), optional quarter-pixel shift towards the larger
- *   neighbour, then (p + 0.5) * 2/size - 1.  coords [rows][2]. */
+ *   neighbour, then (p + 0.5) * 2/size - 1.  coords [rows][2].  The arg-max is torch.max's: a NaN is the maximum
+ *   (the first one's index the arg-max), so a row that holds a NaN decodes to pixel (0,0) as it does in the
+ *   reference. */
 int dsnt_encode_heatmaps(const float* target, float* out, int64_t rows, int h, int w, float sigma, void* stream);
 int dsnt_heatmap_mse_fwd(const float* hm, const float* target, float* per_row, int64_t rows, int h, int w,
                          float sigma, void* stream);

@@ -35,7 +35,9 @@ def stats_ref(hm, transform_m=None):
     h, w = p.shape[-2:]
     flat = p.reshape(p.shape[:-2] + (h * w,))
     X, Y = grid(h, w)
-    out = {'peak': flat.max(-1), 'peak_index': flat.argmax(-1).astype(np.int64),       # argmax: the first maximum
+    # numpy's max and argmax are torch.max's: the first maximum, and a NaN is the maximum (the first NaN the arg-max).  That is
+    # the gauss decode's rule (`decode_row`); dsnt_heatmap_stats on a map with a NaN is not defined by this file
+    out = {'peak': flat.max(-1), 'peak_index': flat.argmax(-1).astype(np.int64),
            'mass': flat.sum(-1)}
     mx, my = (X * p).sum((-2, -1)), (Y * p).sum((-2, -1))
     dx, dy = X - mx[..., None, None], Y - my[..., None, None]

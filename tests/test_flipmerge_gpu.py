@@ -107,6 +107,30 @@ def test_kernel_matches_aten_merge_and_model_head(head_model, strategy, preact, 
         assert none is None and torch.equal(c2, coords)
 
 
+ORACLE_SHAPES = [(64, 64), (7, 7), (12, 20), (20, 12)]
+
+
+@pytest.mark.parametrize('h,w', ORACLE_SHAPES)
+def test_gauss_decode_matches_the_oracle(h, w):
+    """The flip-merged gauss coordinates against the CPU oracle's decode of a merge made on the CPU (the test above takes
+    the device's own decode as the expected value).  Both sides form (a + b) / 2 as an fp32 addition and an fp32 division
+    by two; the division is exact, so the merged maps are equal bit for bit and so must the coordinates be."""
+    from dsnt import inference
+    from dsnt_oracle import util as ou
+    g = torch.Generator().manual_seed(h * 1000 + w + 7)
+    for B in (1, 3):
+        L = 3 * torch.randn(2 * B, 16, h, w, generator=g)
+        tm = torch.eye(2, dtype=torch.float64) * 150 + torch.rand(B, 2, 2, generator=g, dtype=torch.float64)
+        tb = 200 * torch.rand(B, 1, 2, generator=g, dtype=torch.float64)
+        hm1, hm2 = L.split(B)
+        merged = (hm1 + hm2.flip(-1).index_select(-3, inference.HFLIP_INDICES)) / 2
+        want = ou.decode_heatmaps(merged)
+        for store in (True, False):
+            _, coords, hm = inference.flip_merge_head(L.cuda(), tm.cuda(), tb.cuda(), 'gauss', 'softmax', heatmaps=store)
+            assert torch.equal(coords.cpu(), want), (B, store, (coords.cpu() - want).abs().max().item())
+            assert (hm is None) if not store else torch.equal(hm.cpu(), merged)
+
+
 # ------------------------------------------------------------------ 2, 6. batch B against batch 1
 @pytest.mark.parametrize('name', ['hg1_dsnt', 'hg1_gauss', 'resnet18_dsnt'])
 def test_predict_batch_matches_batch_one(models, data5, batch1, name):

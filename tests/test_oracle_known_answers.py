@@ -174,3 +174,77 @@ def test_decode_heatmaps_use_neighbours():  # tests/test_util.py:66-77
                                [0.0, 0.1, 0.0, 0.0]]]], dtype=torch.float32)
     actual = outil.decode_heatmaps(heatmaps, use_neighbours=True)
     assert (torch.tensor([[[-0.125, 0.375]]], dtype=torch.float32) - actual).abs().max().item() <= 1e-7
+
+
+# ---------------------------------------------------------------- hand-derived answers off the square map
+# (none in the reference's tests: get_preds' `idx / height` differs from the true row as soon as H != W, util.py:161)
+_ULP2 = 2.4e-7        # the expected values are fp64 arithmetic rounded to fp32; the chain of fp32 steps lands within two
+                      # ulp of a value below 2 (a pixel is 0.2 or more on these maps)
+
+
+def _map(h, w, cells):
+    hm = torch.zeros(1, 1, h, w, dtype=torch.float32)
+    for (r, c), v in cells.items():
+        hm[0, 0, r, c] = v
+    return hm
+
+
+def _f32(rows):
+    return torch.tensor([[list(r) for r in rows]], dtype=torch.float32)
+
+
+def test_decode_wide_map():
+    """H=5, W=9, 9.0 at [3, 7]: idx = 34, x = 34 % 9 = 7, y = 34 // 5 = 6, past the last row, so no neighbour step."""
+    hm = _map(5, 9, {(3, 7): 9.0})
+    assert torch.equal(outil.get_preds(hm), _f32([(7.0, 6.0)]))
+    for nb in (True, False):
+        got = outil.decode_heatmaps(hm, use_neighbours=nb)
+        assert (got - _f32([(7.5 * 2 / 9 - 1, 6.5 * 2 / 5 - 1)])).abs().max().item() <= _ULP2      # (0.66667, 1.6)
+
+
+def test_decode_tall_map():
+    """H=9, W=5, 9.0 at [7, 2]: idx = 37, x = 37 % 5 = 2, y = 37 // 9 = 4 while the true row is 7.  (2, 4) is interior,
+    so the neighbour step reads ROW 4: hm[4, 3] - hm[4, 1] = 1 > 0 and hm[5, 2] - hm[3, 2] = -2 < 0."""
+    hm = _map(9, 5, {(7, 2): 9.0, (4, 3): 1.0, (3, 2): 2.0})
+    assert torch.equal(outil.get_preds(hm), _f32([(2.0, 4.0)]))
+    got = outil.decode_heatmaps(hm, use_neighbours=False)
+    assert (got - _f32([(2.5 * 2 / 5 - 1, 4.5 * 2 / 9 - 1)])).abs().max().item() <= _ULP2           # (0, 0)
+    got = outil.decode_heatmaps(hm, use_neighbours=True)
+    assert (got - _f32([(2.75 * 2 / 5 - 1, 4.25 * 2 / 9 - 1)])).abs().max().item() <= _ULP2         # (0.1, -0.05556)
+
+
+def test_decode_nan_is_the_maximum():
+    """torch.max propagates NaN: the maximum is NaN, `maxval.gt(0)` is false and the prediction is pixel (0, 0), whatever
+    else the map holds."""
+    hm = _map(6, 6, {(2, 3): float('nan'), (4, 4): 50.0})
+    assert torch.equal(outil.get_preds(hm), _f32([(0.0, 0.0)]))
+    for nb in (True, False):
+        got = outil.decode_heatmaps(hm, use_neighbours=nb)
+        assert (got - _f32([(-5 / 6, -5 / 6)])).abs().max().item() <= _ULP2
+
+
+# target, bump centre (x, y) and window columns / rows on a 5 x 9 map (W/2 = 4.5, H/2 = 2.5; util.py:132-144 and
+# draw_gaussian with radius 3.5):
+#   (-1, 1):   px = 0 * 4.5 - 0.5 = -0.5 -> round-half-even -> 0;  py = 2 * 2.5 - 0.5 = 4.5 -> 4
+#   (0, 0):    px = 4.5 - 0.5 = 4;  py = 2.5 - 0.5 = 2
+#   (1.2, 0):  px = 2.2 * 4.5 - 0.5 = 9.4 -> 9, one pixel right of the map; 9 < 8 + 3.5, so drawn, clipped to columns
+#              ceil(9 - 3.5) = 6 .. 8
+#   (2.0, 0):  px = 3 * 4.5 - 0.5 = 13 >= 8 + 3.5: skipped
+_ENCODE_5x9 = [((-1.0, 1.0), (0, 4), range(0, 4), range(1, 5)),
+               ((0.0, 0.0), (4, 2), range(1, 8), range(0, 5)),
+               ((1.2, 0.0), (9, 2), range(6, 9), range(0, 5)),
+               ((2.0, 0.0), (13, 2), range(0, 0), range(0, 0))]
+
+
+def test_encode_heatmaps_wide_map():
+    import math
+    coords = torch.tensor([[list(t) for t, _, _, _ in _ENCODE_5x9]], dtype=torch.float32)
+    got = outil.encode_heatmaps(coords, 9, 5)
+    assert got.shape == (1, 4, 5, 9)
+    for j, (_, (cx, cy), cols, rows) in enumerate(_ENCODE_5x9):
+        want = torch.zeros(5, 9, dtype=torch.float32)
+        for r in rows:
+            for c in cols:
+                want[r, c] = math.exp(-((c - cx) ** 2 + (r - cy) ** 2) / 2)
+        assert torch.equal(got[0, j] != 0, want != 0), j
+        assert (got[0, j] - want).abs().max().item() <= 1e-6, j

@@ -169,6 +169,45 @@ def test_fused_stats_match_plain_launch_and_standalone_kernel(strategy, preact, 
         _cov_image_ok(st['cov_image'], st['cov'], tm)
 
 
+# NaN pairs of one merged row, as flat indices.  Thread t reads t, t + 256, ...; a wave is 64 threads.  70 | h w - 2: two
+# waves, the lower index met first by the four-wave merge; 257 | 200: wave 0 (second trip) and wave 3, the merge meets the
+# HIGHER index first; 259 | 3: both trips of thread 3; 9 | 5: two lanes of one wave (the shuffle steps decide).
+_NAN_PAIRS = {(64, 64): [(64 * 64 - 2, 70), (257, 200), (259, 3), (9, 5)], (12, 20): [(12 * 20 - 2, 70), (200, 130), (9, 5)]}
+
+
+@pytest.mark.parametrize('h,w', sorted(_NAN_PAIRS))
+def test_fused_gauss_stats_take_a_nan_as_the_peak(h, w):
+    """gauss: peak and peak_index are the decode's arg-max, which is torch.max's (numpy's in stats_ref): a merged map that
+    holds NaNs has peak NaN and peak_index at its FIRST NaN, wherever the two sit among threads, waves and trips, and
+    decodes to pixel (0, 0).  The rows beside it keep the values they have without it."""
+    from dsnt import inference
+    from dsnt_oracle import util as ou
+    B = 2
+    g = torch.Generator().manual_seed(h * 1000 + w + 3)
+    L0 = 3 * torch.randn(2 * B, 16, h, w, generator=g)
+    tm = (torch.eye(2, dtype=torch.float64) * 150).expand(B, 2, 2).contiguous().cuda()
+    tb = torch.zeros(B, 1, 2, dtype=torch.float64).cuda()
+    clean = inference.flip_merge_head(L0.cuda(), tm, tb, 'gauss', 'softmax', stats=True)
+    for pair in _NAN_PAIRS[h, w]:
+        L = L0.clone()
+        L[0, 3].view(-1)[list(pair)] = float('nan')                # merged row (0, 3): NaN at both indices
+        L[1, 5, 0, 1] = 100.0                                       # and a plain maximum in another row
+        merged = (L[:B] + L[B:].flip(-1).index_select(-3, inference.HFLIP_INDICES)) / 2
+        ref = stats_ref.stats_ref(merged.numpy())
+        assert np.isnan(ref['peak'][0, 3]) and ref['peak_index'][0, 3] == min(pair) and ref['peak_index'][1, 5] == 1
+        for store in (True, False):
+            _, coords, _, st = inference.flip_merge_head(L.cuda(), tm, tb, 'gauss', 'softmax', heatmaps=store, stats=True)
+            assert np.array_equal(_np(st['peak']), ref['peak'], equal_nan=True), pair
+            assert np.array_equal(_np(st['peak_index']), ref['peak_index']), (pair, int(st['peak_index'][0, 3]))
+            assert torch.equal(coords.cpu(), ou.decode_heatmaps(merged)), pair
+            assert ((coords[0, 3].cpu() + 1) * torch.tensor([w / 2, h / 2]) - 0.5).round().tolist() == [0.0, 0.0]
+            keep = torch.ones(B, 16, dtype=torch.bool)
+            keep[0, 3] = keep[1, 5] = False
+            assert torch.equal(st['peak'].cpu()[keep], clean[3]['peak'].cpu()[keep])
+            assert torch.equal(st['peak_index'].cpu()[keep], clean[3]['peak_index'].cpu()[keep])
+            assert torch.equal(coords.cpu()[keep], clean[1].cpu()[keep])
+
+
 def test_sharp_joints_score_higher_and_tighter_than_flat_ones():
     """Logits whose merged map is a sharp bump for some joints and nearly flat for the others: every sharp joint has a
     higher peak and a smaller trace(cov_image) than every flat one."""
