@@ -5,7 +5,14 @@ Same class surface as the reference's `PCKhEvaluator` (`JOINT_NAMES`, `JOINT_GRO
 Python double loop with a D2H copy per step (`bin/train.py:376-377`); `add_normalized` also folds
 in the back-projection to image space (`bin/train.py:243-258`, fp64 like the reference).
 Meter values are accumulated as device tensors and only read when `.value()` is called.
+
+`PCKhCurve` answers every threshold at once: one launch per batch adds into a device-resident histogram of the
+normalised distance per joint (`dsnt_pckh_hist`), and PCKh at each threshold, for each joint and group,
+is a cumulative sum of that table taken when the user asks.
 """
+import ctypes
+
+import numpy as np
 import torch
 
 from ._lib import ptr, call
@@ -103,3 +110,186 @@ class PCKhEvaluator:
     def reset(self):
         for m in self.meters.values():
             m.reset()
+
+
+class PCKhCurve:
+    """PCKh at many thresholds, and the area under that curve, from one integer table on the device.
+
+    `table[j][k]` counts the valid joints `j` whose distance lies in `(thresholds[k - 1], thresholds[k]]`; column `T`
+    holds those beyond the last threshold (NaN and inf among them).  Each threshold is held as the fp64 value of its
+    fp32 rounding, as `dsnt_pckh` holds its one threshold, so `pckh(t)` is the very count `PCKhEvaluator(t)` gives.
+    `name` below is a joint name, a group name or a joint index."""
+
+    JOINT_NAMES = PCKhEvaluator.JOINT_NAMES
+    JOINT_GROUPS = PCKhEvaluator.JOINT_GROUPS
+    MAX_THRESHOLDS = 64                   # DSNT_PCKH_HIST_MAX_T
+
+    def __init__(self, thresholds=None, n_joints=16, joint_names=None, joint_groups=None):
+        self.n_joints = int(n_joints)
+        if self.n_joints < 1:
+            raise ValueError('n_joints must be positive')
+        if joint_names is None and self.n_joints == len(self.JOINT_NAMES):
+            joint_names = self.JOINT_NAMES
+            if joint_groups is None:
+                joint_groups = self.JOINT_GROUPS
+        self.joint_names = list(joint_names) if joint_names is not None else []
+        if self.joint_names and len(self.joint_names) != self.n_joints:
+            raise ValueError('%d joint names for %d joints' % (len(self.joint_names), self.n_joints))
+        groups = {g: sorted(self.joint_names.index(n) for n in names) for g, names in (joint_groups or {}).items()}
+        groups.setdefault('all', list(range(self.n_joints)))
+        self.groups = groups
+        self._set_thresholds(np.arange(51) / 100 if thresholds is None else thresholds)
+        self._tables = {}                 # device -> int64 [J, T + 1], the kernel adds into it
+        self._host = torch.zeros(self.n_joints, self.T + 1, dtype=torch.int64)    # merged, loaded and reduced counts
+        self._identity = {}               # (device, B) -> (m, b) of `add`
+
+    def _set_thresholds(self, thresholds):
+        thr = [float(np.float32(t)) for t in np.asarray(thresholds, dtype=np.float64).reshape(-1)]
+        if not 1 <= len(thr) <= self.MAX_THRESHOLDS:
+            raise ValueError('between 1 and %d thresholds, got %d' % (self.MAX_THRESHOLDS, len(thr)))
+        if not all(np.isfinite(thr)) or any(b <= a for a, b in zip(thr, thr[1:])):
+            raise ValueError('thresholds must be finite and strictly ascending as fp32 values')
+        self.thresholds = torch.tensor(thr, dtype=torch.float64)
+        self.T = len(thr)
+        self._thr_arg = (ctypes.c_double * self.T)(*thr)          # host array, passed by value to the kernel
+
+    # ------------------------------------------------------------------ adding batches
+    def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b,
+                       return_distances=False):
+        """Add a batch given in normalised coords (back-projected in fp64 as in `PCKhEvaluator.add_normalized`): one
+        kernel, no reduction and no host synchronisation.  `return_distances`: the f64 [B, J] distances in head lengths,
+        NaN where the mask is not 1."""
+        B, J = norm_pred.shape[0], norm_pred.shape[1]
+        if J != self.n_joints:
+            raise ValueError('%d joints, the table has %d' % (J, self.n_joints))
+        dev = norm_pred.device
+        pred = norm_pred.detach().to(torch.float32).contiguous()
+        target = norm_target.detach().to(device=dev, dtype=torch.float32).contiguous()
+        m = transform_m.to(device=dev, dtype=torch.float64).contiguous()
+        b = transform_b.to(device=dev, dtype=torch.float64).reshape(B, 2).contiguous()
+        mask = joint_mask.to(device=dev, dtype=torch.float32).contiguous()
+        head = head_lengths.to(device=dev, dtype=torch.float64).contiguous()
+        table = self._tables.get(dev)
+        if table is None:
+            table = self._tables[dev] = torch.zeros(J, self.T + 1, dtype=torch.int64, device=dev)
+        dist = torch.empty(B, J, dtype=torch.float64, device=dev) if return_distances else None
+        call('dsnt_pckh_hist', ptr(pred), ptr(target), ptr(m), ptr(b), ptr(mask), ptr(head), self._thr_arg, self.T,
+             ptr(table), ptr(dist), B, J)
+        return dist
+
+    def add(self, pred, target, joint_mask, head_lengths):
+        """Add a batch whose coords are already in image space."""
+        B, dev = pred.shape[0], pred.device
+        ident = self._identity.get((dev, B))
+        if ident is None:
+            ident = self._identity[dev, B] = (torch.eye(2, dtype=torch.float64, device=dev).repeat(B, 1, 1),
+                                              torch.zeros(B, 2, dtype=torch.float64, device=dev))
+        self.add_normalized(pred, target, joint_mask, head_lengths, *ident)
+
+    def reset(self):
+        for t in self._tables.values():
+            t.zero_()
+        self._host.zero_()
+
+    # ------------------------------------------------------------------ reading results
+    def counts(self):
+        """The table, int64 [J, T + 1] on the host."""
+        total = self._host.clone()
+        for t in self._tables.values():
+            total += t.cpu()
+        return total
+
+    def _rows(self, name):
+        if isinstance(name, (int, np.integer)) and not isinstance(name, bool):
+            if not 0 <= name < self.n_joints:
+                raise KeyError(name)
+            return [int(name)]
+        if name in self.groups:
+            return self.groups[name]
+        if name in self.joint_names:
+            return [self.joint_names.index(name)]
+        raise KeyError(name)
+
+    def _names(self):
+        return (self.joint_names or list(range(self.n_joints))) + list(self.groups)
+
+    def _index(self, threshold):
+        t = float(np.float32(threshold))
+        hit = (self.thresholds == t).nonzero()
+        if hit.numel() != 1:
+            raise KeyError('PCKh@%r was not accumulated: not one of the %d thresholds' % (threshold, self.T))
+        return int(hit)
+
+    def _valid(self, counts, name):
+        return int(counts[self._rows(name)].sum())
+
+    def _curve(self, counts, name):
+        row = counts[self._rows(name)].sum(0)
+        hits, n = row[:self.T].cumsum(0).double(), int(row.sum())
+        return hits / n if n else torch.full((self.T,), float('nan'), dtype=torch.float64)
+
+    def _auc(self, curve):
+        if self.T == 1:
+            raise ValueError('the area under the curve needs at least two thresholds')
+        t, c = self.thresholds.numpy(), curve.numpy()
+        area = (np.diff(t) * (c[1:] + c[:-1]) / 2.0).sum()
+        return float(area / (t[-1] - t[0]))
+
+    def valid(self, name='total_mpii'):
+        return self._valid(self.counts(), name)
+
+    def curve(self, name='total_mpii'):
+        """PCKh at every threshold, f64 [T]; NaN where nothing was valid."""
+        return self._curve(self.counts(), name)
+
+    def pckh(self, threshold, name='total_mpii'):
+        """PCKh at one of the constructed thresholds (KeyError for any other)."""
+        return float(self._curve(self.counts(), name)[self._index(threshold)])
+
+    def auc(self, name='total_mpii'):
+        """Trapezoid of the curve over the thresholds, divided by their span."""
+        return self._auc(self._curve(self.counts(), name))
+
+    def summary(self, threshold=0.5):
+        """PCKh of every joint and group at `threshold`, and under 'auc' the area for every group."""
+        k, counts = self._index(threshold), self.counts()
+        out = {name: float(self._curve(counts, name)[k]) for name in self._names()}
+        if self.T > 1:
+            out['auc'] = {g: self._auc(self._curve(counts, g)) for g in self.groups}
+        return out
+
+    # ------------------------------------------------------------------ combining and saving
+    def _take(self, counts):
+        """Make `counts` (host) the whole state."""
+        for t in self._tables.values():
+            t.zero_()
+        self._host = counts.to(device='cpu', dtype=torch.int64).clone()
+
+    def merge(self, other):
+        if other.n_joints != self.n_joints or not torch.equal(other.thresholds, self.thresholds):
+            raise ValueError('merge needs the same joints and identical thresholds')
+        self._host += other.counts()
+
+    def state_dict(self):
+        return {'thresholds': self.thresholds.clone(), 'table': self.counts()}
+
+    def load_state_dict(self, state):
+        table, thresholds = state['table'], state['thresholds']
+        if table.dim() != 2 or tuple(table.shape) != (self.n_joints, thresholds.numel() + 1):
+            raise ValueError('table of shape %s for %d joints and %d thresholds'
+                             % (tuple(table.shape), self.n_joints, thresholds.numel()))
+        self._set_thresholds(thresholds.cpu().numpy())
+        self._tables = {}                 # (their width may have changed)
+        self._take(table)
+
+    def all_reduce(self, group=None):
+        """Sum the table over the ranks of a `torch.distributed` group (evaluation sharded with
+        `EpochLoader(rank=, world_size=)`); nothing to do in a single process."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        counts = self.counts()
+        if dist.get_backend(group) == 'nccl':
+            counts = counts.cuda()
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
+        self._take(counts)

@@ -744,6 +744,25 @@ int dsnt_list_stage_errors(const dsnt_list* l);
 int dsnt_pckh(const float* pred, const float* target, const double* m, const double* b,
               const float* mask, const double* head, float threshold, float* hits,
               float* valid, int B, int J, void* stream);
+/* evaluator.py:66-81 + train.py:243-258 for a whole PCKh curve: one launch ADDS a batch to a histogram of the normalised
+ * distance per joint, whose bin edges are the thresholds.  d is dsnt_pckh's distance (same fp64 expression); a joint
+ * with mask == 1 adds 1 to table[j][k], k the smallest index with d <= thresholds[k], or to table[j][T] when there is
+ * none (d beyond the last threshold, NaN, inf from a zero head length); other masks add nothing.  Hits at thresholds[k]
+ * are sum(table[j][0..k]), the valid count is the row sum.
+ * thresholds: HOST double[T], 1 <= T <= DSNT_PCKH_HIST_MAX_T, finite and strictly ascending, passed by value to the
+ * kernel (DSNT_ERR_ARG otherwise, nothing launched).  table: device u64 [J][T + 1]; the kernel only adds (64-bit integer
+ * atomics: order-independent, bit-reproducible), the caller zeroes.  dist (may be NULL): device f64 [B][J] = d where
+ * mask == 1, NaN elsewhere.
+ * The grid is min(ceil(B * J / DSNT_PCKH_HIST_BLOCK), DSNT_PCKH_HIST_MAX_BLOCKS) workgroups striding over B * J.  While
+ * J * (T + 1) <= DSNT_PCKH_HIST_LDS_CELLS each workgroup counts in LDS and flushes its non-zero cells once; above that
+ * every joint adds to `table` directly.  dsnt_version() >= 122. */
+#define DSNT_PCKH_HIST_MAX_T 64
+#define DSNT_PCKH_HIST_LDS_CELLS 4096
+#define DSNT_PCKH_HIST_BLOCK 256
+#define DSNT_PCKH_HIST_MAX_BLOCKS 64
+int dsnt_pckh_hist(const float* pred, const float* target, const double* m, const double* b,
+                   const float* mask, const double* head, const double* thresholds, int T,
+                   unsigned long long* table, double* dist, int B, int J, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation
  * data.py:118-226 (MPIIDataset.__getitem__, use_aug) batched on the device; semantics in csrc/augment.hip.
