@@ -171,6 +171,7 @@ SIGNATURES = {
     'dsnt_augment_keypoints_gather': [P, P, P, P, L, P, I, I, P, P, P, P, I, P, P, P, P, P, P],
     'dsnt_epoch_indices': [L, C.c_uint64, C.c_uint64, L, L, I, P, P],
     'dsnt_crop_affine': [P, L, P, P, L, P, P, I, I, P, P, P],
+    'dsnt_render_pose': [P, I, P, P, I, I, I, I, P, I, I, P, L, P, F, P, P, I, P, P, I, F, F, P, P],
     'dsnt_debug_mfma_peak': [P, I, I, I, I, P],
     'dsnt_debug_coexec': [P, I, I, I, P],
     'dsnt_debug_bf16_peak': [P, I, I, I, I, P],

@@ -824,6 +824,42 @@ int dsnt_crop_affine(const uint8_t* pool, int64_t pool_bytes, const int64_t* off
 int dsnt_pool_normalize(const float* x, int N, int C, int H, int W, int S, const float* mean, const float* stdv,
                         float* out, void* stream);
 
+/* ------------------------------------------------------------------ looking at predictions
+ * train.py:455-483 (unconvert + util.draw_skeleton per image, the wrist heat-maps as pictures) for a whole batch in one
+ * launch (dsnt.vis.render_pose; formulas in DESIGN.md section 15).  out uint8 [B][H][W][3] =
+ * trunc(clamp(skeleton(heat(canvas)), 0, 255)); every byte is written once, out may be the uint8 canvas itself.
+ * canvas, by canvas_kind: DSNT_RENDER_CANVAS_BLACK (canvas ignored); DSNT_RENDER_CANVAS_F32, model input f32 [B][3][H][W],
+ * base = clamp((x * stdv[c] + mean[c]) * 255, 0, 255), each step rounded to fp32 (mean, stdv: HOST float[3], NULL = 0 and
+ * 1); DSNT_RENDER_CANVAS_U8, uint8 [B][H][W][3].
+ * Heat-map layer, when heatmaps != NULL: heatmaps f32 [B][J][h][w]; the peak of map (b, j) is peak[(b * J + j) *
+ * peak_stride] (peak_stride 7 reads the stats buffer of dsnt_heatmap_stats in place); heat_rgb HOST float [J][3] in
+ * [0, 1].  For every joint whose colour is not black v_j = clamp(sample_j / peak_j, 0, 1), 0 where peak_j is not positive
+ * and finite or the sample is NaN; sample_j is bilinear with pixel centres aligned and the edge clamped, the stored value
+ * when (h, w) == (H, W).  value_c = base_c + (255 - base_c) * (heat_alpha * clamp(sum_j v_j heat_rgb[j][c], 0, 1)).
+ * Skeleton layer, when nbones > 0: coords f32 [B][J][2], normalised (u = (x + 1) W / 2, v = (y + 1) H / 2) or, with
+ * pixel_coords != 0, continuous pixels (pixel i spans [i, i + 1)); mask f32 [B][J] or NULL; bone k joins joints
+ * bone_joints[2k], bone_joints[2k + 1] (HOST int32) in colour bone_rgb[3k..] (HOST float, 0..255).  In table order, for
+ * every bone with two finite ends: cov = clamp(width / 2 + 0.5 - d, 0, 1), d the distance of the pixel centre to the
+ * segment, value = value (1 - cov) + rgb cov, rgb = (100, 100, 100) when mask is 0 at either end.  Then, when
+ * joint_radius > 0, in joint order a disc cov = clamp(joint_radius + 0.5 - d, 0, 1) on every finite joint that a bone
+ * names, in the colour of the first such bone, grey when masked.
+ * All host tables travel as kernel arguments: no copy, no synchronisation.  DSNT_ERR_ARG: out, a used canvas, peak or
+ * heat_rgb of a heat-map layer, coords or the bone table of a skeleton layer is NULL.  DSNT_ERR_SHAPE: unknown
+ * canvas_kind; B outside 1..65535; H, W (h, w, peak_stride with heat-maps) outside 1..DSNT_RENDER_MAX_SIDE; with a layer,
+ * J outside 1..DSNT_RENDER_MAX_JOINTS; nbones outside 0..DSNT_RENDER_MAX_BONES; a bone index outside 0..J-1; width not
+ * positive.  Bit-reproducible (no atomics).  dsnt_version() >= 123. */
+#define DSNT_RENDER_CANVAS_BLACK 0
+#define DSNT_RENDER_CANVAS_F32 1
+#define DSNT_RENDER_CANVAS_U8 2
+#define DSNT_RENDER_MAX_JOINTS 64
+#define DSNT_RENDER_MAX_BONES 32
+#define DSNT_RENDER_MAX_SIDE 16384
+int dsnt_render_pose(const void* canvas, int canvas_kind, const float* mean, const float* stdv, int B, int H, int W, int J,
+                     const float* heatmaps, int h, int w, const float* peak, int64_t peak_stride, const float* heat_rgb,
+                     float heat_alpha, const float* coords, const float* mask, int pixel_coords,
+                     const int32_t* bone_joints, const float* bone_rgb, int nbones, float width, float joint_radius,
+                     uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
