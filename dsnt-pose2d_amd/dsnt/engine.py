@@ -20,6 +20,7 @@ the fused optimiser and the RCCL all-reduce operate on).
 """
 import ctypes as C
 import os
+import struct
 
 import torch
 
@@ -101,6 +102,17 @@ class Normed:
     __slots__ = ('x', 'bn', 'mean', 'invstd', 'scale', 'shift', 'relu', 'abound', 'pending', 'lane')
 
 
+class _Conv:
+    """One traced convolution: what `Tape.conv` decided forward and what the methods that emit its backward read."""
+    __slots__ = ('src', 'x', 'y', 'p', 'g', 'res1', 'res2', 'name', 'normed', 'sc', 'sh', 'relu', 'x_amax', 'use6', 'use16',
+                 'slot', 'slot_k', 'bucket', 'fuse1', 'fold3_ok', 'need_input_grad', 'gd')
+
+
+class _Dgrad:
+    """The operands of one data-gradient launch (`Tape._conv_dgrad_operands`)."""
+    __slots__ = ('native', 'gd', 'gsrc', 'wd', 'wq', 'wq_stride', 'wq16', 'wbd', 'g_amax', 'd6', 'd16', 'd_stream')
+
+
 class Tape:
     def __init__(self, device, training, record=None):
         self.device = device
@@ -118,6 +130,44 @@ class Tape:
         self.lib = _lib.load()
         self.nbytes = 0
         self.bytes_fwd, self.bytes_bwd, self.bytes_by_name, self._ws_ptrs = 0, 0, {}, set()
+        self._read_switches()
+        self.lane = 0           # the lane being traced onto
+        self.side_stream, self.wgrad_stream, self.more_streams = None, None, ()
+        self.stage_census = []      # (stage launches, recorded launches inside) per compiled list
+        self._f16_w_stream = {}
+        self.cur_bucket = 0         # parameter bucket of the layers being traced (mark_bucket)
+        self._wgrad_lane_reads = set()
+        self._writer_base = None
+        self._ident = None
+        self._release_total, self._release_left, self._held = 0, 0, []
+        self.acts = []          # every activation in creation order (debugging / introspection)
+        self.dgrad_slots = []   # (conv params, dst offset) of every conv whose data gradient is needed
+        self.dgrad_total, self.dgrad_f32, self.dgrad_planes = 0, None, None
+        self.param_arena = None  # flat fp32 parameter arena (set by the Program) for the one-launch pack
+        self._pending_reduce = []   # table rows of the slabs written since the last flush
+        self._pending_group = []    # (descriptor bytes, workgroups) since the last flush
+        self._f16_w_rows, self._f16_w_seen = [], set()
+        self._f16_bn_rows = []
+        self._eval_bn_rows = []     # eval mode: every BatchNorm's vectors come from ONE table-driven launch per forward
+        # backward bounds, zeroed at the start of every backward: they follow the gradient through every writer that can report
+        # one (apply, axpy, pool / upsample backward) and through donations
+        self._amax_buf, self._amax_used = None, 0
+        self._planar_src, self._prep_exempt, self._post_reduce = {}, set(), []
+        self._famax_buf, self._famax_used, self._famax_of, self._famax_bn_of = None, 0, {}, {}   # forward activations: zeroed at the start of every forward
+        self._f16_dw_rows = []      # fp16x3 planes of the re-packed data-gradient weights
+        self._dgrad_pack = None     # arguments of the one re-packing launch (set by finish, emitted by emit_f16_prep)
+        self.dgrad_planes16, self.dgrad_bounds = None, None
+        # every fp16x3 launch with the tensors behind its operands and bounds: (list entry, {...}) — lets a test walk a
+        # step launch by launch and hold each bound against the operand it must dominate (tests/test_bounds_gpu.py)
+        self.f16_uses = []
+        self._pending_group_uses = []
+        # replay from C (dsnt_list_*): a launch list is recorded once into the library and then issued by ONE call per
+        # segment instead of one ctypes call per launch (`_run`)
+        self._clists = {}
+
+    def _read_switches(self):
+        """The switches and thresholds of the schedule: product defaults, each with the environment variable that overrides it
+        for an A/B measurement or a test (read once, when the tape is created)."""
         # fp32-accurate split-bf16 matrix-core path for the large convolutions (DSNT_MFMA=f32 disables)
         self.use_bf16x6 = os.environ.get('DSNT_MFMA', 'bf16x6') != 'f32'
         # (16384 -> 8192, the 16x16 level at batch 32: -0.08 ms; -> 4096 once fwd1 took the 1x1 convolutions of that size: the 16x16
@@ -125,36 +175,39 @@ class Tape:
         self.bf16x6_min_rows = int(os.environ.get('DSNT_BF16X6_MIN_ROWS', '4096'))
         # lanes: 0 = the caller's stream, 1 = a side stream for independent branches (the full-resolution
         # skip branch of every hourglass level runs beside the low-resolution recursion)
-        self.lane = 0
         self.use_lanes = os.environ.get('DSNT_LANES', '1') != '0'
-        self.fuse_join = True      # hourglass.Hourglass._level: branch gradients joined inside the pool's backward (-0.15 ms)
-        self.side_stream = None
-        self.wgrad_stream = None
         # lanes 3.. : more side lanes (the skip branches of the hourglass levels alternate over them: an inner level's
         # branch, which the main lane needs back first, does not queue behind the outer level's large kernels)
         self.side_lanes = (1, 3)   # two side lanes (one: +0.13 ms, four: +0.35 ms: DESIGN.md "round 2")
         self.n_lanes = 3 + len(self.side_lanes) - 1
         self.chain_lanes = (0,) + self.side_lanes
-        self.more_streams = ()
-        # weight gradients feed nothing downstream in backward.  The large ones (>= DSNT_WGRAD_LANE_ROWS output rows; 0 =
-        # all) go to a third lane: the chip then has work while the dependency chain walks the launch-bound
+        # weight gradients feed nothing downstream in backward.  The large ones (>= DSNT_X_WGRAD_LANE_ROWS output rows; 0 =
+        # all) of the chain's lanes go to a third lane: the chip then has work while the dependency chain walks the launch-bound
         # low-resolution levels, and the main lane neither runs nor waits for the slab reductions (-0.9 ms/step on hg2).
-        # DSNT_WGRAD_LANE_RES=1 also moves convolutions with residual inputs, whose dY buffer is donated onwards and
-        # written again — the writer then has to wait for the lane (measured: +0.45 ms, off).
+        # Not the convolutions with residual inputs, whose dY buffer is donated onwards and written again — the writer then
+        # has to wait for the lane (measured: +0.45 ms).
         self.wgrad_lane = 2 if (self.use_lanes and os.environ.get('DSNT_WGRAD_LANE', '1') != '0') else None
         self.wgrad_lane_rows = int(os.environ.get('DSNT_X_WGRAD_LANE_ROWS', '16000'))
-        self.wgrad_lane_res = False
-        self.wgrad_lane_from = self.chain_lanes
+        # ... and they are HELD BACK (launches collected, not yet on the list) until the chain enters a launch-bound
+        # phase: a `release point` is the backward of an up-sampling whose low-resolution operand has at most
+        # DSNT_X_RELEASE_ROWS rows.  Issued as they come, the weight gradients share the chip with the large
+        # data-gradient kernels and are gone by the time the small levels start; held back, they run beside them.
+        # Only while a release point is still ahead in the backward order (a ResNet has none: nothing is held back).
+        # (8192 -> 4096 in round 6: at batch 32 the 16 x 16 level — 8192 rows — still fills the chip by itself; released one level
+        # further in, the held weight gradients run beside the 8 x 8 / 4 x 4 chains only: hg2 -0.07 ms, hg8 batch 16 unchanged — its
+        # 16 x 16 level has 4096 rows; profiles/r06_ab_switches.txt box A)
+        self.release_rows = int(os.environ.get('DSNT_X_RELEASE_ROWS', '4096'))
+        off = set(os.environ.get('DSNT_OFF', '').replace('+', ',').split(','))       # DSNT_OFF=conv3s,gemm1,wgrad3,wgrad1
         # 3x3 forward / data gradient: the symmetric persistent kernel of csrc/conv3s.hip (stream-ordered weight planes)
-        self.conv3s = 'conv3s' not in os.environ.get('DSNT_OFF', '').replace('+', ',').split(',')       # DSNT_OFF=conv3s,gemm1,wgrad3,wgrad1
+        self.conv3s = 'conv3s' not in off
         # the whole backward of a 1x1 convolution in one launch (csrc/bwd1.hip): data gradient with the BatchNorm-backward
         # epilogue + weight gradient + (conv1 of a Bottleneck) the BatchNorm backward of the layer behind, each tensor read once
-        self.bwd1 = 'bwd1' not in os.environ.get('DSNT_OFF', '').replace('+', ',').split(',')
-        self.fwd1 = 'fwd1' not in os.environ.get('DSNT_OFF', '').replace('+', ',').split(',')      # ... and their forward (csrc/fwd1.hip)
+        self.bwd1 = 'bwd1' not in off
+        self.fwd1 = 'fwd1' not in off      # ... and their forward (csrc/fwd1.hip)
         # round 5: the BatchNorm backward behind a 3x3 convolution folded into that convolution's data gradient (conv3s.hip MODE 4)
-        self.fold3 = 'fold3' not in os.environ.get('DSNT_OFF', '').replace('+', ',').split(',')
+        self.fold3 = 'fold3' not in off
         self.fold3_rows = int(os.environ.get('DSNT_X_FOLD3_ROWS', '16384'))
-        self.stem4 = 'stem4' not in os.environ.get('DSNT_OFF', '').replace('+', ',').split(',')    # the stem's forward (csrc/stem4.hip)
+        self.stem4 = 'stem4' not in off    # the stem's forward (csrc/stem4.hip)
         # round 6: runs of small dependent launches of one lane as ONE persistent launch (csrc/stage.h).  OFF by default — built,
         # bit-identical to the launches it replaces (tests/test_stage_gpu.py), and measured SLOWER: hg2 batch 32 11.06 -> 11.97 ms,
         # hg8 batch 16 24.1 -> 25.7 ms with every run fused; 11.17 / 24.04 (no gain) with only the <= 64-workgroup launches of the
@@ -163,12 +216,6 @@ class Tape:
         self.stage_min_run = int(os.environ.get('DSNT_X_STAGE_MIN_RUN', '3'))
         self.stage_max_vgrid = int(os.environ.get('DSNT_X_STAGE_MAX_VGRID', '512'))
         self.stage_grid = int(os.environ.get('DSNT_X_STAGE_GRID', '64'))
-        self.stage_census = []      # (stage launches, recorded launches inside) per compiled list
-        self._f16_w_stream = {}
-        # DSNT_CONV_SHARE_CHIP on the side lanes' launches of the two persistent kernels (3x3: 3/2 workgroups per CU; 1x1: half of
-        # the CUs): both hold most of a CU's LDS for the whole launch, and the chain's kernels need LDS too (-0.2 ms)
-        self.conv_share = True
-        self.wgrad_share = True    # DSNT_WGRAD_SHARE_CHIP on every launch of that lane (-0.2 ms)
         # DSNT_X=<name>=<value>,...: A/B overrides of scheduling constants (tools/ab_env.sh); not product switches
         self._x = dict(kv.split('=') for kv in os.environ.get('DSNT_X', '').split(',') if '=' in kv)
         self.wgrad_narrow = self._x.get('wgrad_narrow', '1')      # DSNT_WGRAD_NARROW: 0 never, 1 always, 2 stem bucket only, 3 stacks only
@@ -185,39 +232,13 @@ class Tape:
         # the per-step preparation in two halves: what the FORWARD reads (arena planes, weight planes, BatchNorm bounds) and what only
         # the backward reads (re-packed + split data-gradient weights); the main lane waits for the first half only (A/B: prep_split=0)
         self.prep_split = self._x.get('prep_split', '1') != '0'
-        self.cur_bucket = 0         # parameter bucket of the layers being traced (mark_bucket)
-        self._wgrad_lane_reads = set()
-        self._writer_base = None
-        self._ident = None
-        # ... and they are HELD BACK (launches collected, not yet on the list) until the chain enters a launch-bound
-        # phase: a `release point` is the backward of an up-sampling whose low-resolution operand has at most
-        # DSNT_WGRAD_RELEASE_ROWS rows.  Issued as they come, the weight gradients share the chip with the large
-        # data-gradient kernels and are gone by the time the small levels start; held back, they run beside them.
-        # Only while a release point is still ahead in the backward order (a ResNet has none: nothing is held back).
-        # (8192 -> 4096 in round 6: at batch 32 the 16 x 16 level — 8192 rows — still fills the chip by itself; released one level
-        # further in, the held weight gradients run beside the 8 x 8 / 4 x 4 chains only: hg2 -0.07 ms, hg8 batch 16 unchanged — its
-        # 16 x 16 level has 4096 rows; profiles/r06_ab_switches.txt box A)
-        self.release_rows = int(os.environ.get('DSNT_X_RELEASE_ROWS', '4096'))
-        self._release_total, self._release_left = 0, 0
-        self._held = []
-        self.acts = []          # every activation in creation order (debugging / introspection)
-        self.dgrad_slots = []   # (conv params, dst offset) of every conv whose data gradient is needed
-        self.dgrad_total = 0
-        self.dgrad_f32 = None
-        self.dgrad_planes = None
-        self.param_arena = None  # flat fp32 parameter arena (set by the Program) for the one-launch pack
         # weight-gradient slabs are kept per convolution and reduced once per parameter bucket (one launch
         # instead of one per convolution); DSNT_DEFER_REDUCE=0 reduces inside every dsnt_conv_wgrad call
         self.defer_reduce = os.environ.get('DSNT_DEFER_REDUCE', '1') != '0'
-        self._pending_reduce = []   # table rows of the slabs written since the last flush
         # weight gradients of the low-resolution levels (few workgroups each, nothing downstream in backward
         # needs them) wait for the end of their parameter bucket and run side by side in one grouped launch;
-        # DSNT_WGRAD_GROUP_ROWS = largest N*Ho*Wo that is deferred (0 disables)
+        # DSNT_X_GROUP_ROWS = largest N*Ho*Wo that is deferred (0 disables)
         self.group_rows = int(os.environ.get('DSNT_X_GROUP_ROWS', '8192')) if self.defer_reduce else 0
-        self._pending_group = []    # (descriptor bytes, workgroups) since the last flush
-        # max-pool / upsample+add write the BatchNorm statistics of their output themselves (DSNT_FUSE_OP_STATS=0:
-        # a separate dsnt_bn_stats pass when a BatchNorm asks for them)
-        self.fuse_op_stats = True
         # BatchNorm finalisation of few-tile statistics inside the consumer's prologue (DSNT_FUSE_FINALIZE=0: separate launches)
         self.fuse_finalize = os.environ.get('DSNT_FUSE_FINALIZE', '1') != '0'
         # ... up to this many (tiles x channels) of partial sums.  Measured (tools/bench_bn_prologue.py, MI355X): a finalise
@@ -232,29 +253,6 @@ class Tape:
         self.use_f16x3 = self.use_bf16x6 and os.environ.get('DSNT_SPLIT', 'f16x3') == 'f16x3'
         if self.record and not self.training:
             self.use_f16x3 = False      # (its backward operand bounds come from BATCH statistics: |xhat| <= sqrt(M))
-        self._f16_w_rows, self._f16_w_seen = [], set()
-        self._f16_bn_rows = []
-        self._eval_bn_rows = []     # eval mode: every BatchNorm's vectors come from ONE table-driven launch per forward
-        self._amax_buf, self._amax_used = None, 0      # zeroed at the start of every backward
-        self.raw_f16 = True        # bounds of raw operands from the producers' epilogues (-0.24 ms)
-        self._planar_src, self._prep_exempt, self._post_reduce = {}, set(), []
-        self.stem_s2d_on = True    # the stem as a space-to-depth convolution (-0.08 ms)
-        self._famax_buf, self._famax_used, self._famax_of, self._famax_bn_of = None, 0, {}, {}   # forward activations: zeroed at the start of every forward
-        # DSNT_AMAX_ALL=0: only single-writer BN-backward outputs get a bound (A/B switch); default: bounds follow the
-        # gradient through every writer that can report one (apply, axpy, pool / upsample backward) and through donations
-        self.amax_all = True
-        self._f16_dw_rows = []      # fp16x3 planes of the re-packed data-gradient weights
-        self._dgrad_pack = None     # arguments of the one re-packing launch (set by finish, emitted by emit_f16_prep)
-        self.prep_on_side_lane = self.use_lanes      # per-step preparation beside the stem (-0.15 ms)
-        self.dgrad_planes16, self.dgrad_bounds = None, None
-        # every fp16x3 launch with the tensors behind its operands and bounds: (list entry, {...}) — lets a test walk a
-        # step launch by launch and hold each bound against the operand it must dominate (tests/test_bounds_gpu.py)
-        self.f16_uses = []
-        self._pending_group_uses = []
-        # replay from C (dsnt_list_*): a launch list is recorded once into the library and then issued by ONE call per
-        # segment instead of one ctypes call per launch (DSNT_C_REPLAY=0: the Python loop below)
-        self.c_replay = True
-        self._clists = {}
 
     # ------------------------------------------------------------------ buffers
     def empty(self, *shape, dtype=torch.float32):
@@ -263,28 +261,15 @@ class Tape:
         self._keep.append(t)
         return t
 
-    def scratch(self, key, numel):
+    def scratch(self, key, numel, dtype=torch.float32, least=1):
         """Shared scratch (valid only within one op's launches on the single stream)."""
-        if False:      # (debugging aid: private buffers instead of the shared scratch)
-            return self.empty(max(numel, 1))
         key = (key, self.lane)
         t = self._scratch.get(key)
         if t is None or t.numel() < numel:
             if t is not None:
                 self._keep.append(t)   # earlier launches recorded the old pointer
-            t = torch.empty(max(numel, 1), device=self.device, dtype=torch.float32)
-            self.nbytes += t.numel() * 4
-            self._scratch[key] = t
-        return t
-
-    def scratch_bf16(self, key, numel):
-        key = (key, self.lane)
-        t = self._scratch.get(key)
-        if t is None or t.numel() < numel:
-            if t is not None:
-                self._keep.append(t)
-            t = torch.empty(max(numel, 8), device=self.device, dtype=torch.bfloat16)
-            self.nbytes += t.numel() * 2
+            t = torch.empty(max(numel, least), device=self.device, dtype=dtype)
+            self.nbytes += t.numel() * t.element_size()
             self._scratch[key] = t
         return t
 
@@ -313,7 +298,6 @@ class Tape:
         """Device scalar >= |relu?(bn(x))| of the train-mode BatchNorm seen through Normed n."""
         if n.abound is None:
             n.abound = self.empty(64)            # a bound = 64 slots (DSNT_BOUND_SLOTS)
-            import struct
             bits = struct.unpack('<I', struct.pack('<f', float(n.x.M) ** 0.5))[0]
             self._f16_bn_rows.append([n.bn.gamma.data_ptr(), n.bn.beta.data_ptr(), n.abound.data_ptr(), n.bn.C, bits])
         return n.abound
@@ -328,9 +312,9 @@ class Tape:
     def operand_amax(self, x):
         """Bound slot for activation x used as a RAW fp16x3 operand (no BatchNorm in between: skip projections, `lin`
         convolutions): the launch that produced x is asked — through its dsnt_out_bounds, read at launch time — to leave
-        max|x| there.  None if the producer cannot."""
+        max|x| there (-0.24 ms against bf16x6 for those convolutions).  None if the producer cannot."""
         t = x.amax_tail
-        if t is None or not self.use_f16x3 or not self.raw_f16:
+        if t is None or not self.use_f16x3:
             return None
         slot = self._famax_of.get(id(t))
         if slot is None:
@@ -353,7 +337,7 @@ class Tape:
         the operand itself and leave its exact maximum (dsnt_out_bounds.amax_bn).  One BatchNorm per producer; None if
         the producer cannot or is already taken by another BatchNorm."""
         t = n.x.amax_tail
-        if t is None or not self.use_f16x3 or not self.raw_f16 or self.training:
+        if t is None or not self.use_f16x3 or self.training:
             return None
         got = self._famax_bn_of.get(id(t))
         if got is not None:
@@ -382,7 +366,7 @@ class Tape:
         preparation (the bf16 split of the arena).  With lanes, all of it runs on the side lane beside the stem
         convolution (which reads fp32 weights) and the main lane waits right before the first launch that needs it."""
         # (eval mode: the BN vectors are needed at once, and there is nothing to hide the launches behind)
-        side = 1 if (self.use_lanes and self.prep_on_side_lane and self.training) else 0
+        side = 1 if (self.use_lanes and self.training) else 0      # (beside the stem: -0.15 ms)
         saved, self.fwd = self.fwd, []
         saved_lane, self.lane = self.lane, side
         for fn, args, name, _ in head:
@@ -702,7 +686,7 @@ class Tape:
     def _run(self, lst, main, bucket_hook, probe):
         streams = (main, self.side_stream, self.wgrad_stream) + self.more_streams
         ptrs = tuple(st.cuda_stream if st is not None else 0 for st in streams)
-        if self.c_replay and probe is None:
+        if probe is None:
             cl = self._clists.get(id(lst))
             if cl is None:
                 cl = self._clists[id(lst)] = self._compile(lst)
@@ -718,11 +702,8 @@ class Tape:
                     with torch.cuda.stream(streams[lane]):
                         bucket_hook(k)
             return
-        if self.use_lanes:
-            self.side_stream.wait_stream(main)
-            self.wgrad_stream.wait_stream(main)
-            for st in self.more_streams:
-                st.wait_stream(main)
+        for st in streams[1:] if self.use_lanes else ():
+            st.wait_stream(main)
         for entry in lst:
             fn, args, name, lane = entry
             if fn is None:
@@ -741,11 +722,8 @@ class Tape:
                 torch.cuda.synchronize()
                 raise RuntimeError('%s failed (%d): %s' % (
                     name, rc, _lib.load().dsnt_last_error().decode()))
-        if self.use_lanes:
-            main.wait_stream(self.side_stream)
-            main.wait_stream(self.wgrad_stream)
-            for st in self.more_streams:
-                main.wait_stream(st)
+        for st in streams[1:] if self.use_lanes else ():
+            main.wait_stream(st)
 
     # ------------------------------------------------------------------ gradient plumbing
     def add_later(self, a, g, g_amax=None):
@@ -785,10 +763,7 @@ class Tape:
             # read the base itself (base_ok: `take_base`) does that in its own pass; any other finds a copy in place
             base, base_amax, a.base, a.base_amax = a.base, a.base_amax, None, None
             a._grad, a.grad_shared = self.empty(a.N, a.H, a.W, a.C), False
-            if self.use_f16x3 and amax and self.amax_all:
-                a.grad_amax = self.amax_slot()
-            else:
-                a.grad_amax = None
+            a.grad_amax = self.amax_slot() if (self.use_f16x3 and amax) else None
             if base_ok:
                 self._writer_base = base
                 return a._grad, 0
@@ -805,7 +780,7 @@ class Tape:
             self._wgrad_lane_reads.discard(a.grad.data_ptr())
             self.release_wgrads()                            # a held-back launch that reads it must be on the list first
             self.sync_bwd(self.wgrad_lane, self.lane)        # a weight gradient on its own lane still reads this buffer
-        if self.use_f16x3 and amax and (self.amax_all or (amax == 'apply' and acc == 0)):
+        if self.use_f16x3 and amax:
             if a.grad_amax is None:
                 a.grad_amax = self.amax_slot()
         else:
@@ -822,7 +797,7 @@ class Tape:
             self._flush_add(a)
         if a.grad is None and donate:
             a.grad = g
-            a.grad_amax = g_amax if self.amax_all else None
+            a.grad_amax = g_amax
             return True
         buf, acc = self.grad_target(a, amax=True)
         if a.grad_amax is not None:
@@ -866,7 +841,6 @@ class Tape:
                 self.f('dsnt_bn_finalize', part, tiles, x.M, bn.C, bn.gamma, bn.beta, bn.rmean, bn.rvar,
                        bn.momentum, bn.eps, 1, n.mean, n.invstd, n.scale, n.shift)
         else:
-            import struct
             bits = struct.unpack('<I', struct.pack('<f', float(bn.eps)))[0]
             self._eval_bn_rows.append([bn.gamma.data_ptr(), bn.beta.data_ptr(), bn.rmean.data_ptr(), bn.rvar.data_ptr(),
                                        n.mean.data_ptr(), n.invstd.data_ptr(), n.scale.data_ptr(), n.shift.data_ptr(),
@@ -903,7 +877,7 @@ class Tape:
         x got a second gradient contribution, so its gradient has to exist in memory."""
         ap, x.pending_apply = x.pending_apply, None
         n = ap['n']
-        buf, acc = self.grad_target(x, amax='apply')
+        buf, acc = self.grad_target(x, amax=True)
         if x.grad_amax is not None:
             self.b('dsnt_bn_act_bwd_apply_amax', ap['dz'], x.buf, n.scale, n.shift, n.mean, n.invstd, ap['coef'], 0,
                    buf, acc, x.M, n.bn.C, x.grad_amax)
@@ -948,7 +922,7 @@ class Tape:
             bn.uses += 1
             if not fused:
                 self.b('dsnt_bn_bwd_finalize', part, tiles, x.M, bn.C, bn.ggamma, bn.gbeta, acc_p | (2 if frozen else 0), coef)
-        buf, acc = self.grad_target(x, amax='apply', base_ok=True)
+        buf, acc = self.grad_target(x, amax=True, base_ok=True)
         base = self.take_base()         # x's gradient continues one it does not own: dx = base + value (`conv`, defer_res)
         if fused:
             # few tiles: the apply launch sums them itself in its prologue (coef) and writes dgamma / dbeta
@@ -969,34 +943,85 @@ class Tape:
             self.b('dsnt_bn_act_bwd_apply', da, x.buf, n.scale, n.shift, n.mean, n.invstd, coef, relu,
                    buf, acc, x.M, bn.C)
 
+    # ------------------------------------------------------------------ convolution
     def conv(self, src, p, res1=None, res2=None, want_stats=False, need_input_grad=True, name=''):
         """y = conv(src) + bias [+ res1 + res2]; src is an Act (raw) or a Normed (BN+ReLU folded)."""
-        normed = isinstance(src, Normed)
-        x = src.x if normed else src
-        g = self.geom(x, p)
-        y = self.act(x.N, g.Ho, g.Wo, p.Cout, name)
+        c = _Conv()
+        c.src, c.p, c.res1, c.res2, c.name, c.need_input_grad = src, p, res1, res2, name, need_input_grad
+        c.normed = isinstance(src, Normed)
+        c.x = x = src.x if c.normed else src
+        c.g = self.geom(x, p)
+        c.y = y = self.act(x.N, c.g.Ho, c.g.Wo, p.Cout, name)
         x.uses += 1
         for r in (res1, res2):
             if r is not None:
                 r.uses += 1
                 y.gives_away = True             # dL/dy's buffer is handed to a residual input in backward
-        sc = src.scale if normed else None
-        sh = src.shift if normed else None
-        relu = 1 if (normed and src.relu) else 0
+        c.sc, c.sh, c.relu = (src.scale, src.shift, 1 if src.relu else 0) if c.normed else (None, None, 0)
+        self._conv_forward(c, want_stats)
+        if self.record:
+            self._conv_backward_plan(c)
+            self.on_backward(lambda: self._conv_backward(c))
+        return y
+
+    def _share(self, persistent=True):
+        """DSNT_CONV_SHARE_CHIP (bit 1 of a launch's flag word) on the side lanes' launches of the persistent kernels (3x3: 3/2
+        workgroups per CU; 1x1: half of the CUs): they hold most of a CU's LDS for the whole launch, and the chain's kernels
+        need LDS too (-0.2 ms)."""
+        return 2 if (persistent and self.lane != 0) else 0
+
+    def _operand_bound(self, c):
+        """The bound slot of c's A operand as its producer leaves it (None if it cannot); the first call claims the producer's tail."""
+        return self.operand_amax_bn(c.src) if c.normed else self.operand_amax(c.x)
+
+    @staticmethod
+    def _bn_epilogue(x, n):
+        """The BatchNorm(+ReLU) n in front of x's consumer (None: a raw operand) as a data gradient's epilogue reads it."""
+        vectors = (n.scale, n.shift, n.mean, n.invstd) if n is not None else (None,) * 4
+        return BnBwdEpilogue(_lib.ptr(x.buf), *(_lib.ptr(v) for v in vectors), 1 if (n is not None and n.relu) else 0)
+
+    @staticmethod
+    def _bn_apply(y, ap):
+        """(BnBwdApply of y's pending BatchNorm backward, the tensors behind it for `f16_uses`)."""
+        n = ap['n']
+        return (BnBwdApply(_lib.ptr(y.buf), _lib.ptr(n.scale), _lib.ptr(n.mean), _lib.ptr(n.invstd), _lib.ptr(ap['coef'])),
+                dict(dz=ap['dz'], y=y.buf, scale=n.scale, mean=n.mean, invstd=n.invstd, coef=ap['coef']))
+
+    def _dz_buffer(self, x, private):
+        """dz of the BatchNorm in front of x's consumer: the op's scratch, or — read again by the backward of the 1x1 convolution
+        that produced x (`fold_ok`) — a buffer that outlives this op's launches."""
+        n = x.M * x.C
+        return self.empty(n) if private else self.scratch('da', n).view(-1)[:n]
+
+    def _reduce_row(self, ws, p, splits):
+        self._pending_reduce.append([ws.data_ptr(), p.gw.data_ptr(), p.gb.data_ptr() if p.gb is not None else 0,
+                                     splits, p.Cout * p.R * p.S * p.Cin, p.Cout, 0])
+
+    def _struct_bytes(self, name, nb):
+        """Algorithmic bytes of the tensors a backward launch names inside a struct (`_emit` counts the plain arguments)."""
+        self.bytes_bwd += nb
+        self.bytes_by_name[name] = self.bytes_by_name.get(name, 0) + nb
+
+    def _conv_forward(self, c, want_stats):
+        """Choose c's forward kernel — fwd1 / stem4 / stream or tiled fp16x3 / bf16x6 / fp32 with the BatchNorm finalised in its
+        prologue / fp32 — and emit it."""
+        src, x, y, p, g, normed, res2 = c.src, c.x, c.y, c.p, c.g, c.normed, c.res2
+        sc, sh, relu = c.sc, c.sh, c.relu
         if normed:
             self.check_lane(src)
         part, tail = None, None
-        use6 = self._use6(g) and p.wq is not None
+        use6 = c.use6 = self._use6(g) and p.wq is not None
+        can16 = use6 and p.wq16 is not None
         # the large 1x1 convolutions with both operand bounds: the LDS-staged streaming kernel (csrc/fwd1.hip) — its statistics
-        # come one row per WORKGROUP, and how many that is depends on the launch's share flag (below)
-        x_amax_pre = None
-        if use6 and p.wq16 is not None and p.R == 1 and res2 is None and self.fwd1:
-            x_amax_pre = self.operand_amax_bn(src) if normed else self.operand_amax(x)
-        f1 = bool(use6 and self.use_f16x3 and p.wq16 is not None and p.R == 1 and res2 is None and self.fwd1 and
-                  ((self.training and normed) or x_amax_pre is not None) and self.lib.dsnt_conv1x1_fwd_ok(C.byref(g)))
-        f1_shr = 2 if (f1 and self.lane != 0 and self.conv_share) else 0
+        # come one row per WORKGROUP, and how many that is depends on the launch's share flag, so a candidate claims its bound
+        # (and keeps it if f1 turns out false) BEFORE the statistics buffer is allocated; every other convolution after it
+        early = can16 and p.R == 1 and res2 is None and self.fwd1
+        x_amax = self._operand_bound(c) if early else None
+        f1 = bool(early and self.use_f16x3 and ((self.training and normed) or x_amax is not None) and
+                  self.lib.dsnt_conv1x1_fwd_ok(C.byref(g)))
+        f1_shr = self._share(f1)
         # the stem's space-to-depth convolution (4x4, 16 -> 64 channels, a raw operand): the halo kernel of csrc/stem4.hip
-        s4 = bool(use6 and self.use_f16x3 and self.stem4 and p.wq16 is not None and not normed and res1 is None and res2 is None and
+        s4 = bool(can16 and self.use_f16x3 and self.stem4 and not normed and c.res1 is None and res2 is None and
                   self.lib.dsnt_stem4_fwd_ok(C.byref(g)))
         if want_stats and self.training:
             bm = 128 if use6 else self.lib.dsnt_conv_fwd_bm(C.byref(g))
@@ -1007,23 +1032,21 @@ class Tape:
         if use6 and self.use_f16x3:
             # the large-tile kernels can leave max|y| behind: a later consumer of the raw y claims it (operand_amax)
             y.amax_tail = tail = BnTail()
-        r1 = res1.buf if res1 is not None else None
+        r1 = c.res1.buf if c.res1 is not None else None
         r2 = res2.buf if res2 is not None else None
         if self.use_f16x3 and self.training and normed:
             self.f16_bn_bound(src)              # also for the weight gradient of convs whose forward is not fp16x3
         # fp16x3 needs a bound of the A operand: train-mode BatchNorm parameters, or the producer's max|x| for a raw x
-        x_amax = x_amax_pre
-        if x_amax is None and use6 and p.wq16 is not None:
-            x_amax = self.operand_amax_bn(src) if normed else self.operand_amax(x)
-        use16 = use6 and self.use_f16x3 and p.wq16 is not None and ((self.training and normed) or x_amax is not None)
+        if can16 and not early:
+            x_amax = self._operand_bound(c)
+        c.x_amax = x_amax
+        use16 = c.use16 = can16 and self.use_f16x3 and ((self.training and normed) or x_amax is not None)
         if normed and (use16 or use6):
             self.materialize(src)
         if use16:
             st = self.stream_ok(p, g, y.M, res2)
             self.f16_weights(p, stream=st)
             ab = self.f16_bn_bound(src) if (normed and self.training) else x_amax
-            # (bit 1 of in_relu: a persistent kernel on a side lane leaves CUs with free LDS for the chain's kernels)
-            shr = 2 if ((st or p.R == 1) and self.lane != 0 and self.conv_share) else 0
             if f1:
                 e = self.f('dsnt_conv1x1_fwd_f16x3', x.buf, p.wq16, p.wq_stride, p.wb, ab, p.b, y.buf, sc, sh, relu | f1_shr, r1,
                            part, g, tail)
@@ -1031,8 +1054,8 @@ class Tape:
                 e = self.f('dsnt_stem4_fwd_f16x3', x.buf, p.wq16, p.wq_stride, p.wb, ab, p.b, y.buf, part, g, tail)
             else:
                 e = self.f('dsnt_conv_fwd_f16x3_stream' if st else 'dsnt_conv_fwd_f16x3_ex', x.buf, p.wq16, p.wq_stride, p.wb, ab,
-                           p.b, y.buf, sc, sh, relu | shr, r1, r2, part, g, None, tail)
-            self.f16_uses.append((e, dict(kind='fwd', name=name, x=x.buf, sc=sc, sh=sh, relu=relu, a_bound=ab,
+                           p.b, y.buf, sc, sh, relu | self._share(st or p.R == 1), r1, r2, part, g, None, tail)
+            self.f16_uses.append((e, dict(kind='fwd', name=c.name, x=x.buf, sc=sc, sh=sh, relu=relu, a_bound=ab,
                                           w=p.w, w_bound=p.wb)))
         elif use6:
             self.f('dsnt_conv_fwd_bf16x6_ex', x.buf, p.wq, p.wq_stride, p.b, y.buf, sc, sh, relu, r1, r2, part, g,
@@ -1051,335 +1074,339 @@ class Tape:
             if normed:
                 self.materialize(src)
             self.f('dsnt_conv_fwd_ex', x.buf, p.w, p.b, y.buf, sc, sh, relu, r1, r2, part, g, None, tail)
-        if not self.record:
-            return y
-        slot = None
-        if need_input_grad and self.param_arena is not None:
-            slot = self.dgrad_total
-            slot_k = len(self.dgrad_slots)
-            self.dgrad_slots.append((p, slot))
+
+    def _conv_backward_plan(self, c):
+        """Decided while the forward is traced: c's slot among the re-packed data-gradient weights, and whether its backward can take
+        over the BatchNorm backward of its consumer (`Act.fold_ok`: that BatchNorm's backward, emitted first, leaves its apply pending)."""
+        x, y, p, g = c.x, c.y, c.p, c.g
+        c.slot = c.slot_k = None
+        if c.need_input_grad and self.param_arena is not None:
+            c.slot, c.slot_k = self.dgrad_total, len(self.dgrad_slots)
+            self.dgrad_slots.append((p, c.slot))
             self.dgrad_total += (p.w.numel() + 7) // 8 * 8
+        c.bucket = self.cur_bucket
         # the whole backward of this convolution as ONE launch (csrc/bwd1.hip): 1x1 behind a train-mode BatchNorm, both
         # operand bounds known on the device
-        bucket = self.cur_bucket
-        fuse1 = bool(self.bwd1 and (normed or x_amax is not None) and self.use_f16x3 and self.defer_reduce and
-                     slot is not None and p.R == 1 and p.S == 1 and p.post_reduce is None and
-                     self.lib.dsnt_conv1x1_bwd_ok(C.byref(g)))
+        one_pass = self.bwd1 and self.use_f16x3 and self.defer_reduce and c.slot is not None
+        c.fuse1 = bool(one_pass and (c.normed or c.x_amax is not None) and p.R == 1 and p.S == 1 and p.post_reduce is None and
+                       self.lib.dsnt_conv1x1_bwd_ok(C.byref(g)))
         # ... and without residual inputs (whose gradient IS dL/dy) it can also take over the BatchNorm backward of its consumer
-        y.fold_ok = fuse1 and normed and res1 is None and res2 is None
+        plain = c.normed and c.res1 is None and c.res2 is None
+        # the geometry of the stride-1 data gradient: decided here, read again by `_conv_dgrad_operands`
+        c.gd = None
+        if p.stride == 1:
+            c.gd = ConvGeom(x.N, g.Ho, g.Wo, p.Cout, x.H, x.W, p.Cin, p.R, p.S, 1, p.dil * (p.R - 1) - p.pad, p.dil)
         # the same for a 3x3 convolution on the persistent fp16x3 kernel (conv2 of a Bottleneck: bn3's backward rides in the operand
-        # load of conv2's data gradient, csrc/conv3s.hip MODE 4), from DSNT_X_FOLD3_ROWS output rows
-        # (the predicate is the one emit_dgrad's fp16x3 stream branch needs — `d16 and d_stream and not native` — so that a geometry
-        # that branch refuses is decided HERE, while the consumer BatchNorm can still be told to apply by itself)
-        gd3 = ConvGeom(x.N, g.Ho, g.Wo, p.Cout, x.H, x.W, p.Cin, p.R, p.S, 1, p.dil * (p.R - 1) - p.pad, p.dil)
-        fold3_ok = bool(self.fold3 and self.bwd1 and normed and self.training and res1 is None and res2 is None and slot is not None and
-                        self.use_f16x3 and self.defer_reduce and p.R == 3 and p.S == 3 and p.stride == 1 and use16 and
-                        y.M >= self.fold3_rows and self._use6(gd3) and self.stream_ok(p, gd3, x.M, None))
-        y.fold_ok = y.fold_ok or fold3_ok
+        # load of conv2's data gradient, csrc/conv3s.hip MODE 4), from DSNT_X_FOLD3_ROWS output rows — if the data gradient of
+        # THAT geometry takes the fp16x3 stream kernel: a geometry it refuses is decided HERE, while the consumer BatchNorm can
+        # still be told to apply by itself
+        c.fold3_ok = bool(self.fold3 and one_pass and plain and self.training and p.R == 3 and p.S == 3 and c.gd is not None and
+                          c.use16 and y.M >= self.fold3_rows and self._use6(c.gd) and self.stream_ok(p, c.gd, x.M, None))
+        y.fold_ok = bool(c.fuse1 and plain) or c.fold3_ok
 
-        def backward():
-            gy = y.grad
-            ap = y.pending_apply
-            fused = fuse1 and self.dgrad_planes16 is not None
-            fold3 = bool(fold3_ok and ap is not None and gy is None and self.dgrad_planes16 is not None and need_input_grad and
-                         ap['bound'] is not None)
-            if ap is not None and (not fused or gy is not None) and not fold3:
-                self.materialize_apply(y)
-                ap, gy = None, y.grad
-            assert gy is not None or ap is not None, 'no gradient reached conv output ' + name
-            if fused and ap is None and y.grad_amax is None:
-                fused = False
-            cur = wl = self.lane
-            defer_res = False
-            if fused:
-                nw = p.w.numel()
-                shr = 2 if (self.lane != 0 and self.conv_share) else 0
-                nsp = self.lib.dsnt_conv1x1_bwd_splits(C.byref(g), shr)
-                ws = self.empty(self.lib.dsnt_conv1x1_bwd_ws_floats(C.byref(g), shr))      # lives until the bucket's reduction
-                self._ws_ptrs.add(ws.data_ptr())
-                wd = self.dgrad_f32[slot:slot + nw]
-                wq16 = self.dgrad_planes16[slot:slot + nw]
-                wbd = self.dgrad_bounds[64 * slot_k:64 * slot_k + 64]
-                self._f16_dw_rows.append([wd.data_ptr(), wq16.data_ptr(), wbd.data_ptr(), nw, self.dgrad_total, 0, 0])
-                if ap is not None:
-                    n2 = ap['n']
-                    aps = BnBwdApply(_lib.ptr(y.buf), _lib.ptr(n2.scale), _lib.ptr(n2.mean), _lib.ptr(n2.invstd), _lib.ptr(ap['coef']))
-                    dy, gb = ap['dz'], ap['bound']
-                    y.pending_apply = None
-                else:
-                    aps, dy, gb = None, gy, y.grad_amax
-                if normed:
-                    ab = self.f16_bn_bound_bwd(src)
-                    # (the BatchNorm in front of THIS convolution may in turn be left to the 1x1 convolution before it)
-                    fold = self.fold_ok(src)
-                    dz = self.empty(x.M * x.C) if fold else self.scratch('da', x.M * x.C).view(-1)[:x.M * x.C]
-                    dz_amax = self.amax_slot() if fold else None
-                    part = self.scratch('bnpart', nsp * 2 * x.C).view(-1)
-                    xs = BnBwdEpilogue(_lib.ptr(x.buf), _lib.ptr(src.scale), _lib.ptr(src.shift), _lib.ptr(src.mean),
-                                       _lib.ptr(src.invstd), 1 if src.relu else 0)
-                    e = self.b('dsnt_conv1x1_bwd_f16x3', xs, dy, aps, wq16, self.dgrad_total, wbd, ab, gb, dz, part, ws,
-                               dz_amax, shr, g)
-                    u = dict(kind='bwd1', name=name, x=x.buf, sc=src.scale, sh=src.shift, relu=1 if src.relu else 0,
-                             a_bound=ab, w=wd, w_bound=wbd)
-                else:
-                    # no BatchNorm in front of it (projection shortcuts, the `fc` convolutions): dL/dx itself is written, or
-                    # added to what x's gradient holds already
-                    ab = x_amax
-                    buf, acc = self.grad_target(x, amax=self.raw_f16)
-                    xs = BnBwdEpilogue(_lib.ptr(x.buf), None, None, None, None, 0)
-                    e = self.b('dsnt_conv1x1_bwd_f16x3', xs, dy, None, wq16, self.dgrad_total, wbd, ab, gb, buf, None, ws,
-                               x.grad_amax, shr | acc, g)
-                    u = dict(kind='bwd1', name=name, x=x.buf, sc=None, sh=None, relu=0, a_bound=ab, w=wd, w_bound=wbd)
-                nb = 4 * (x.buf.numel() + (y.buf.numel() if ap is not None else 0))      # (tensors named inside the structs)
-                self.bytes_bwd += nb
-                self.bytes_by_name['dsnt_conv1x1_bwd_f16x3'] = self.bytes_by_name.get('dsnt_conv1x1_bwd_f16x3', 0) + nb
-                if ap is not None:
-                    u.update(g_apply=dict(dz=dy, y=y.buf, scale=n2.scale, mean=n2.mean, invstd=n2.invstd, coef=ap['coef']),
-                             g_bound=gb)
-                else:
-                    u.update(g=dy, g_bound=gb)
-                self.f16_uses.append((e, u))
-                self._pending_reduce.append([ws.data_ptr(), p.gw.data_ptr(), p.gb.data_ptr() if p.gb is not None else 0,
-                                             nsp, p.Cout * g.Cin, p.Cout, 0])
-                if normed:
-                    self._norm_backward(src, dz, reduced=(part, nsp), finalised=False, dz_amax=dz_amax)
+    def _conv_backward(self, c):
+        """Emit c's backward: the one-launch 1x1 form, or weight gradient and data gradient; then the residual inputs' gradients."""
+        y = c.y
+        gy, ap = y.grad, y.pending_apply
+        fused = c.fuse1 and self.dgrad_planes16 is not None
+        fold3 = bool(c.fold3_ok and ap is not None and gy is None and self.dgrad_planes16 is not None and c.need_input_grad and
+                     ap['bound'] is not None)
+        if ap is not None and (not fused or gy is not None) and not fold3:
+            self.materialize_apply(y)
+            ap, gy = None, y.grad
+        assert gy is not None or ap is not None, 'no gradient reached conv output ' + c.name
+        if fused and ap is None and y.grad_amax is None:
+            fused = False
+        wl, defer_res = self.lane, False
+        if fused:
+            self._conv_bwd_fused1(c, ap, gy)
+        elif fold3:
+            # the BatchNorm backward of the layer behind a 3x3 convolution, left pending by that layer's own backward
+            # (`fold_ok`), rides in this convolution's data gradient (csrc/conv3s.hip MODE 4): the launch forms dL/dy from
+            # (dz, y) while it stages its operand and writes it out for the weight gradient, which therefore comes SECOND
+            gy = y._grad = self.empty(y.N, y.H, y.W, y.C)
+            y.grad_amax, y.pending_apply = ap['bound'], None
+            self._conv_dgrad(c, gy, ap)
+            wl, defer_res = self._conv_wgrad(c, gy)
+        else:
+            wl, defer_res = self._conv_wgrad(c, gy)
+            self._conv_dgrad(c, gy, None)
+        self._conv_residual_grads(c, gy, wl, defer_res)
+
+    def _conv_bwd_fused1(self, c, ap, gy):
+        """The one-launch backward of a 1x1 convolution (dsnt_conv1x1_bwd_f16x3).  ap: the pending BatchNorm backward of c's
+        consumer, applied in the operand load (else dL/dy = gy is read as it is)."""
+        src, x, y, p, g, name = c.src, c.x, c.y, c.p, c.g, 'dsnt_conv1x1_bwd_f16x3'
+        nw = p.w.numel()
+        shr = self._share()
+        nsp = self.lib.dsnt_conv1x1_bwd_splits(C.byref(g), shr)
+        ws = self.empty(self.lib.dsnt_conv1x1_bwd_ws_floats(C.byref(g), shr))      # lives until the bucket's reduction
+        self._ws_ptrs.add(ws.data_ptr())
+        wd = self.dgrad_f32[c.slot:c.slot + nw]
+        wq16 = self.dgrad_planes16[c.slot:c.slot + nw]
+        wbd = self.dgrad_bounds[64 * c.slot_k:64 * c.slot_k + 64]
+        self._f16_dw_rows.append([wd.data_ptr(), wq16.data_ptr(), wbd.data_ptr(), nw, self.dgrad_total, 0, 0])
+        if ap is not None:
+            aps, applied = self._bn_apply(y, ap)
+            dy, gb = ap['dz'], ap['bound']
+            y.pending_apply = None
+            grad = dict(g_apply=applied, g_bound=gb)
+        else:
+            aps, dy, gb = None, gy, y.grad_amax
+            grad = dict(g=dy, g_bound=gb)
+        if c.normed:
+            ab = self.f16_bn_bound_bwd(src)
+            # (the BatchNorm in front of THIS convolution may in turn be left to the 1x1 convolution before it)
+            fold = self.fold_ok(src)
+            dz = self._dz_buffer(x, fold)
+            dz_amax = self.amax_slot() if fold else None
+            part = self.scratch('bnpart', nsp * 2 * x.C).view(-1)
+            e = self.b(name, self._bn_epilogue(x, src), dy, aps, wq16, self.dgrad_total, wbd, ab, gb, dz, part, ws, dz_amax, shr, g)
+        else:
+            # no BatchNorm in front of it (projection shortcuts, the `fc` convolutions): dL/dx itself is written, or
+            # added to what x's gradient holds already
+            ab = c.x_amax
+            buf, acc = self.grad_target(x, amax=True)
+            e = self.b(name, self._bn_epilogue(x, None), dy, None, wq16, self.dgrad_total, wbd, ab, gb, buf, None, ws,
+                       x.grad_amax, shr | acc, g)
+        self._struct_bytes(name, 4 * (x.buf.numel() + (y.buf.numel() if ap is not None else 0)))
+        u = dict(kind='bwd1', name=c.name, x=x.buf, sc=c.sc, sh=c.sh, relu=c.relu, a_bound=ab, w=wd, w_bound=wbd)
+        u.update(grad)
+        self.f16_uses.append((e, u))
+        self._reduce_row(ws, p, nsp)
+        if c.normed:
+            self._norm_backward(src, dz, reduced=(part, nsp), finalised=False, dz_amax=dz_amax)
+
+    def _conv_wgrad(self, c, gy):
+        """Parameter gradients of c (flat arena, overwritten every step).  Returns (the lane they run on, whether dL/dy stays
+        intact for them as the `base` of the residual inputs' gradients)."""
+        p, g = c.p, c.g
+        cur = wl = self.lane
+        # the weight gradient feeds nothing downstream in backward: run it on its own lane so the data-gradient chain never waits
+        # for it.  DSNT_X_WGRAD_LANE_ROWS > 0: only the large convolutions of the chain's lanes whose dY nobody writes again (no
+        # residual inputs: the gradient buffer is not donated onwards) — their weight gradients then fill the chip while the
+        # main lane walks the launch-bound low-resolution levels
+        if self.wgrad_lane is not None and (self.wgrad_lane_rows == 0 or (
+                cur in self.chain_lanes and c.res1 is None and c.res2 is None and g.N * g.Ho * g.Wo >= self.wgrad_lane_rows)):
+            wl = self.wgrad_lane
+        hold = wl != cur and self._release_left > 0
+        if hold:
+            listed, self.bwd = self.bwd, self._held
+        self.sync_bwd(cur, wl)
+        self.lane = wl
+        if wl != cur:
+            # gy may be donated onwards and accumulated into by a later launch of another lane: that writer waits
+            # for the weight-gradient lane first (grad_target)
+            self._wgrad_lane_reads.add(gy.data_ptr())
+        # DSNT_WGRAD_SHARE_CHIP (-0.2 ms): one workgroup per CU beside the chain — except for the first convolution of the
+        # network (no data gradient: it is the LAST launch of backward and has the chip to itself)
+        share = 2 if (wl != cur and c.need_input_grad) else 0
+        # DSNT_WGRAD_NARROW for the hourglass stacks' 3x3 weight gradients: the lane has slack there (the 1x1 weight
+        # gradients left it), the stem's bucket is the tail of backward and keeps the wider plan
+        if share and self.wgrad_narrow in ('1', {0: '2'}.get(c.bucket, '3')):
+            share |= 4
+        w6 = self.use_bf16x6 and bool(self.lib.dsnt_conv_wgrad_bf16x6_ok(C.byref(g)))
+        defer_res = False
+        if self.defer_reduce:
+            defer_res = self._conv_wgrad_slab(c, gy, share, w6, wl == cur)
+        else:
+            ws = self.scratch('wgrad', self.lib.dsnt_conv_wgrad_ws_floats(C.byref(g)))
+            self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', c.x.buf, c.sc, c.sh, c.relu, gy, ws, p.gw, p.gb, 0, g)
+            if p.post_reduce is not None:      # the stem's space-to-depth gradient -> the parameter's 7x7 layout
+                self.b(p.post_reduce[0], *p.post_reduce[1])
+        self.lane = cur
+        if hold:
+            self.bwd = listed
+        return wl, defer_res
+
+    def _conv_wgrad_slab(self, c, gy, share, w6, on_chain):
+        """c's weight gradient into a slab of its own that the bucket's one reduction launch sums (`flush_wgrad`): a launch here,
+        or — low-resolution convolutions — a descriptor for the bucket's grouped launch.  Returns `defer_res`."""
+        x, y, p, g, normed, sc, sh, relu = c.x, c.y, c.p, c.g, c.normed, c.sc, c.sh, c.relu
+        # deferred to the bucket's grouped launch: x, gy and the BN vectors are written once per
+        # step and gy is not donated onwards (no residual inputs), so they are intact at the flush
+        # (... nor shared with an activation whose gradient is accumulated into later: `share_grads`)
+        # (a RAW operand — conv1 of a torchvision BasicBlock, resnet.py — rides with the identity prologue: scale 1, shift 0)
+        groupable = (w6 and (normed or self.share_grads) and on_chain and not y.grad_shared and
+                     0 < g.N * g.Ho * g.Wo <= self.group_rows)
+        # ... or, WITH residual inputs (conv3 of the low-resolution Bottlenecks): dL/dy is not donated to them but
+        # handed over as the `base` their own gradient continues out of place, and so stays intact as well
+        residuals = [r for r in (c.res1, c.res2) if r is not None]
+        defer_res = bool(groupable and residuals and self.share_grads and self.defer_res and all(
+            r._grad is None and r.base is None and r.pending_apply is None and r.pending_add is None for r in residuals))
+        grouped = groupable and (not residuals or defer_res)
+        # fp16x3: both operand bounds exist (A: train-mode BN parameters, dY: one bn-backward apply wrote it)
+        w16 = w6 and self.use_f16x3 and (normed or c.x_amax is not None) and y.grad_amax is not None
+        ab = (self.f16_bn_bound_bwd(c.src) if normed else c.x_amax) if w16 else None
+        if w16 and not grouped:
+            # dsnt_conv_wgrad_f16x3 cuts the pixels of a 3x3 convolution into its own slabs (halo kernel)
+            nws = self.lib.dsnt_conv_wgrad_f16x3_ws_floats(C.byref(g), share)
+            splits = self.lib.dsnt_conv_wgrad_f16x3_splits(C.byref(g), share)
+        else:
+            nws, splits = self.lib.dsnt_conv_wgrad_ws_floats(C.byref(g)), self.lib.dsnt_conv_wgrad_splits(C.byref(g))
+        ws = self.empty(nws)         # lives until the bucket's reduction
+        self._ws_ptrs.add(ws.data_ptr())
+        use = dict(kind='wgrad', name=c.name, x=x.buf, sc=sc, sh=sh, relu=relu, a_bound=ab, g=gy, g_bound=y.grad_amax)
+        if grouped:
+            desc = C.create_string_buffer(self.lib.dsnt_conv_wgrad_desc_bytes())
+            gsc, gsh = (sc, sh) if normed else self.identity_bn(x.C)
+            if w16:
+                nblk = self.lib.dsnt_conv_wgrad_desc_f16x3(_lib.ptr(x.buf), _lib.ptr(gsc), _lib.ptr(gsh), relu, _lib.ptr(gy),
+                                                           _lib.ptr(ws), _lib.ptr(ab), _lib.ptr(y.grad_amax), C.byref(g), desc)
+                self._pending_group_uses.append(use)
             else:
-                # the BatchNorm backward of the layer behind a 3x3 convolution, left pending by that layer's own backward
-                # (`fold_ok`), rides in this convolution's data gradient (csrc/conv3s.hip MODE 4): the launch forms dL/dy from
-                # (dz, y) while it stages its operand and writes it out for the weight gradient, which therefore comes SECOND
-                if fold3:
-                    gy = y._grad = self.empty(y.N, y.H, y.W, y.C)
-                    y.grad_amax, y.pending_apply = ap['bound'], None
+                nblk = self.lib.dsnt_conv_wgrad_desc(_lib.ptr(x.buf), _lib.ptr(gsc), _lib.ptr(gsh), relu, _lib.ptr(gy),
+                                                     _lib.ptr(ws), C.byref(g), desc)
+            if nblk <= 0:
+                raise RuntimeError('dsnt_conv_wgrad_desc failed: %s' % self.lib.dsnt_last_error().decode())
+            self._pending_group.append((desc.raw, nblk))
+        elif w16:
+            e = self.b('dsnt_conv_wgrad_f16x3', x.buf, sc, sh, relu, gy, ws, None, None, share, ab, y.grad_amax, g)
+            self.f16_uses.append((e, use))
+        else:
+            self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', x.buf, sc, sh, relu, gy, ws, None, None,
+                   share if w6 else 0, g)
+        if p.post_reduce is not None:
+            self._post_reduce.append(p.post_reduce)
+        self._reduce_row(ws, p, splits)
+        return defer_res
 
-                def emit_wgrad():
-                    defer_res = False
-                    # parameter gradients (flat arena, overwritten every step)
-                    # the weight gradient feeds nothing downstream in backward: run it on its own lane so the
-                    # data-gradient chain never waits for it
-                    cur = self.lane
-                    wl = cur
-                    if self.wgrad_lane is not None:
-                        # DSNT_WGRAD_LANE_ROWS > 0: only the large main-lane convolutions whose dY nobody writes again (no
-                        # residual inputs: the gradient buffer is not donated onwards) — their weight gradients then fill the
-                        # chip while the main lane walks the launch-bound low-resolution levels
-                        if self.wgrad_lane_rows == 0 or (cur in self.wgrad_lane_from and (self.wgrad_lane_res or (res1 is None and res2 is None)) and
-                                                         g.N * g.Ho * g.Wo >= self.wgrad_lane_rows):
-                            wl = self.wgrad_lane
-                    hold = wl != cur and self._release_left > 0
-                    if hold:
-                        listed, self.bwd = self.bwd, self._held
-                    self.sync_bwd(cur, wl)
-                    self.lane = wl
-                    if wl != cur:
-                        # gy may be donated onwards and accumulated into by a later launch of another lane: that writer waits
-                        # for the weight-gradient lane first (grad_target)
-                        self._wgrad_lane_reads.add(gy.data_ptr())
-                    nws = self.lib.dsnt_conv_wgrad_ws_floats(C.byref(g))
-                    # DSNT_WGRAD_SHARE_CHIP: one workgroup per CU beside the chain — except for the first convolution of the
-                    # network (no data gradient: it is the LAST launch of backward and has the chip to itself)
-                    share = 2 if (wl != cur and self.wgrad_share and need_input_grad) else 0
-                    # DSNT_WGRAD_NARROW for the hourglass stacks' 3x3 weight gradients: the lane has slack there (the 1x1 weight
-                    # gradients left it), the stem's bucket is the tail of backward and keeps the wider plan
-                    if share and self.wgrad_narrow in ('1', {0: '2'}.get(bucket, '3')):
-                        share |= 4
-                    w6 = self.use_bf16x6 and bool(self.lib.dsnt_conv_wgrad_bf16x6_ok(C.byref(g)))
-                    if self.defer_reduce:
-                        # deferred to the bucket's grouped launch: x, gy and the BN vectors are written once per
-                        # step and gy is not donated onwards (no residual inputs), so they are intact at the flush
-                        # (... nor shared with an activation whose gradient is accumulated into later: `share_grads`)
-                        # (a RAW operand — conv1 of a torchvision BasicBlock, resnet.py — rides with the identity prologue: scale 1, shift 0)
-                        groupable = (w6 and (normed or self.share_grads) and wl == cur and not y.grad_shared and
-                                     0 < g.N * g.Ho * g.Wo <= self.group_rows)
-                        # ... or, WITH residual inputs (conv3 of the low-resolution Bottlenecks): dL/dy is not donated to them but
-                        # handed over as the `base` their own gradient continues out of place, and so stays intact as well
-                        residuals = [r for r in (res1, res2) if r is not None]
-                        defer_res = bool(groupable and residuals and self.share_grads and self.defer_res and all(
-                            r._grad is None and r.base is None and r.pending_apply is None and r.pending_add is None
-                            for r in residuals))
-                        grouped = groupable and (not residuals or defer_res)
-                        # fp16x3: both operand bounds exist (A: train-mode BN parameters, dY: one bn-backward apply wrote it)
-                        w16 = w6 and self.use_f16x3 and (normed or x_amax is not None) and y.grad_amax is not None
-                        ab = (self.f16_bn_bound_bwd(src) if normed else x_amax) if w16 else None
-                        splits = self.lib.dsnt_conv_wgrad_splits(C.byref(g))
-                        if w16 and not grouped:
-                            # dsnt_conv_wgrad_f16x3 cuts the pixels of a 3x3 convolution into its own slabs (halo kernel)
-                            nws = self.lib.dsnt_conv_wgrad_f16x3_ws_floats(C.byref(g), share)
-                            splits = self.lib.dsnt_conv_wgrad_f16x3_splits(C.byref(g), share)
-                        ws = self.empty(nws)         # lives until the bucket's reduction
-                        self._ws_ptrs.add(ws.data_ptr())
-                        if grouped:
-                            desc = C.create_string_buffer(self.lib.dsnt_conv_wgrad_desc_bytes())
-                            gsc, gsh = (sc, sh) if normed else self.identity_bn(x.C)
-                            if w16:
-                                nblk = self.lib.dsnt_conv_wgrad_desc_f16x3(_lib.ptr(x.buf), _lib.ptr(gsc), _lib.ptr(gsh), relu,
-                                                                           _lib.ptr(gy), _lib.ptr(ws), _lib.ptr(ab),
-                                                                           _lib.ptr(y.grad_amax), C.byref(g), desc)
-                            else:
-                                nblk = self.lib.dsnt_conv_wgrad_desc(_lib.ptr(x.buf), _lib.ptr(gsc), _lib.ptr(gsh), relu,
-                                                                     _lib.ptr(gy), _lib.ptr(ws), C.byref(g), desc)
-                            if nblk <= 0:
-                                raise RuntimeError('dsnt_conv_wgrad_desc failed: %s' % self.lib.dsnt_last_error().decode())
-                            self._pending_group.append((desc.raw, nblk))
-                            if w16:
-                                self._pending_group_uses.append(dict(kind='wgrad', name=name, x=x.buf, sc=sc if normed else None,
-                                                                     sh=sh if normed else None, relu=relu,
-                                                                     a_bound=ab, g=gy, g_bound=y.grad_amax))
-                        elif w16:
-                            e = self.b('dsnt_conv_wgrad_f16x3', x.buf, sc, sh, relu, gy, ws, None, None, share, ab, y.grad_amax, g)
-                            self.f16_uses.append((e, dict(kind='wgrad', name=name, x=x.buf, sc=sc, sh=sh, relu=relu, a_bound=ab,
-                                                          g=gy, g_bound=y.grad_amax)))
-                        else:
-                            self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', x.buf, sc, sh, relu, gy, ws,
-                                   None, None, share if w6 else 0, g)
-                        if p.post_reduce is not None:
-                            self._post_reduce.append(p.post_reduce)
-                        self._pending_reduce.append([ws.data_ptr(), p.gw.data_ptr(), p.gb.data_ptr() if p.gb is not None else 0,
-                                                     splits, p.Cout * g.R * g.S * g.Cin, p.Cout, 0])
-                    else:
-                        ws = self.scratch('wgrad', nws)
-                        self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', x.buf, sc, sh, relu, gy, ws,
-                               p.gw, p.gb, 0, g)
-                        if p.post_reduce is not None:      # the stem's space-to-depth gradient -> the parameter's 7x7 layout
-                            self.b(p.post_reduce[0], *p.post_reduce[1])
-                    self.lane = cur
-                    if hold:
-                        self.bwd = listed
-                    return wl, defer_res
+    def _conv_dgrad_operands(self, c, gy):
+        """What c's data gradient launches on: the geometry (`c.gd`, or — a strided convolution the phase kernel of csrc/dgrad_up.hip
+        refuses — the stride-1 one over a zero-stuffed dL/dy) and the re-packed weights in the precision the launch takes."""
+        x, p, g = c.x, c.p, c.g
+        d = _Dgrad()
+        nw = p.w.numel()
+        pad_d = p.dil * (p.R - 1) - p.pad
+        assert pad_d >= 0, 'data gradient needs pad <= dil * (R - 1)'
+        # strided convolution (ResNet stage transitions): dsnt_conv_dgrad_strided computes the pixels of dX phase by phase
+        # straight from dY
+        d.native = p.stride != 1 and c.slot is not None and self.lib.dsnt_conv_dgrad_strided_ok(C.byref(g))
+        d.gd, d.gsrc = c.gd, gy
+        if p.stride != 1 and not d.native:
+            # ... or, for the shapes that kernel refuses: the stride-1 data gradient of dY with zeros stuffed between the pixels
+            Hs, Ws = x.H + 2 * p.pad - p.dil * (p.R - 1), x.W + 2 * p.pad - p.dil * (p.S - 1)
+            d.gsrc = self.scratch('stuffed', x.N * Hs * Ws * p.Cout).view(-1)[:x.N * Hs * Ws * p.Cout]
+            self.b('dsnt_zero_insert', gy, d.gsrc, x.N, g.Ho, g.Wo, p.Cout, Hs, Ws, p.stride)
+            d.gd = ConvGeom(x.N, Hs, Ws, p.Cout, x.H, x.W, p.Cin, p.R, p.S, 1, pad_d, p.dil)
+        d.wq = d.wq_stride = d.wq16 = d.wbd = d.d_stream = None
+        if c.slot is not None:
+            d.wd = self.dgrad_f32[c.slot:c.slot + nw]
+            d.wq, d.wq_stride = self.dgrad_planes[c.slot:c.slot + nw], self.dgrad_total
+            d.d6 = d.gd is not None and self._use6(d.gd)
+        else:       # stand-alone use without a parameter arena
+            d.wd = self.scratch('wdgrad', nw)
+            self.b('dsnt_conv_pack_dgrad', p.w, d.wd, p.Cout, p.R, p.S, p.Cin)
+            d.d6 = self._use6(d.gd) and nw % 8 == 0
+            if d.d6:
+                d.wq, d.wq_stride = self.scratch('wdgrad6', 3 * nw, torch.bfloat16, 8), nw
+                self.b('dsnt_split_bf16x3', d.wd, d.wq, nw)
+        d.g_amax = c.y.grad_amax if (self.use_f16x3 and p.stride == 1) else None
+        d.d16 = d.d6 and d.g_amax is not None and c.slot is not None and self.dgrad_planes16 is not None
+        if d.d16:
+            d.wq16 = self.dgrad_planes16[c.slot:c.slot + nw]
+            d.wbd = self.dgrad_bounds[64 * c.slot_k:64 * c.slot_k + 64]
+            # (the data gradient's filter is [Cin][3][3][Cout]: its "Cout" is this convolution's Cin)
+            d.d_stream = self.stream_ok(p, d.gd, x.M, None)
+            self._f16_dw_rows.append([d.wd.data_ptr(), d.wq16.data_ptr(), d.wbd.data_ptr(), nw, self.dgrad_total] +
+                                     ([p.Cin, p.Cout] if d.d_stream else [0, 0]))
+        return d
 
-                def emit_dgrad():
-                    if not need_input_grad:
-                        return
-                    nw = p.w.numel()
-                    pad_d = p.dil * (p.R - 1) - p.pad
-                    assert pad_d >= 0, 'data gradient needs pad <= dil * (R - 1)'
-                    native = p.stride != 1 and slot is not None and self.lib.dsnt_conv_dgrad_strided_ok(C.byref(g))
-                    if p.stride == 1:
-                        gd = ConvGeom(x.N, g.Ho, g.Wo, p.Cout, x.H, x.W, p.Cin, p.R, p.S, 1, pad_d, p.dil)
-                    elif native:
-                        # strided convolution (ResNet stage transitions): dsnt_conv_dgrad_strided computes the pixels of dX
-                        # phase by phase straight from dY (csrc/dgrad_up.hip)
-                        gd = None
-                    else:
-                        # ... or, for the shapes that kernel refuses: the stride-1 data gradient of dY with stride-1
-                        # zeros stuffed between the pixels
-                        Hs = x.H + 2 * p.pad - p.dil * (p.R - 1)
-                        Ws = x.W + 2 * p.pad - p.dil * (p.S - 1)
-                        stuffed = self.scratch('stuffed', x.N * Hs * Ws * p.Cout).view(-1)[:x.N * Hs * Ws * p.Cout]
-                        self.b('dsnt_zero_insert', gy, stuffed, x.N, g.Ho, g.Wo, p.Cout, Hs, Ws, p.stride)
-                        gy_d = stuffed
-                        gd = ConvGeom(x.N, Hs, Ws, p.Cout, x.H, x.W, p.Cin, p.R, p.S, 1, pad_d, p.dil)
-                    if slot is not None:
-                        wd = self.dgrad_f32[slot:slot + nw]
-                        wq, wq_stride = self.dgrad_planes[slot:slot + nw], self.dgrad_total
-                        d6 = gd is not None and self._use6(gd)
-                    else:       # stand-alone use without a parameter arena
-                        wd = self.scratch('wdgrad', nw)
-                        self.b('dsnt_conv_pack_dgrad', p.w, wd, p.Cout, p.R, p.S, p.Cin)
-                        d6 = self._use6(gd) and nw % 8 == 0
-                        if d6:
-                            wq, wq_stride = self.scratch_bf16('wdgrad6', 3 * nw), nw
-                            self.b('dsnt_split_bf16x3', wd, wq, nw)
+    def _conv_dgrad_launch(self, c, d, out, res, part=None, bnb=None, tail=None):
+        """out = data gradient of c [+ res], with the BatchNorm-backward epilogue bnb (partial sums into part) and the bound tail."""
+        if d.native:
+            self.b('dsnt_conv_dgrad_strided', d.gsrc, d.wd, out, res, part, c.g, bnb, tail)
+        elif d.d16:
+            e = self.b('dsnt_conv_fwd_f16x3_stream' if d.d_stream else 'dsnt_conv_fwd_f16x3_ex', d.gsrc, d.wq16, self.dgrad_total,
+                       d.wbd, d.g_amax, None, out, None, None, self._share(d.d_stream or c.p.R == 1), res, None, part, d.gd, bnb, tail)
+            self.f16_uses.append((e, dict(kind='dgrad', name=c.name, g=d.gsrc, g_bound=d.g_amax, w=d.wd, w_bound=d.wbd)))
+        elif d.d6:
+            self.b('dsnt_conv_fwd_bf16x6_ex', d.gsrc, d.wq, d.wq_stride, None, out, None, None, 0, res, None, part, d.gd, bnb, tail)
+        else:
+            self.b('dsnt_conv_fwd_ex', d.gsrc, d.wd, None, out, None, None, 0, res, None, part, d.gd, bnb, tail)
 
-                    gsrc = gy if (p.stride == 1 or native) else gy_d
+    def _conv_dgrad(self, c, gy, ap):
+        """The data gradient of c.  ap: the pending BatchNorm backward of c's consumer, applied in the operand load of the
+        launch, which also writes the dL/dy it forms to gy (`fold3`; None: gy is read)."""
+        if not c.need_input_grad:
+            return
+        src, x, y = c.src, c.x, c.y
+        d = self._conv_dgrad_operands(c, gy)
+        if not c.normed:
+            # (d6: the large-tile kernels; their epilogue can leave max|written gradient| as the next bound)
+            buf, acc = self.grad_target(x, amax=bool(d.d6 or d.native), base_ok=True)
+            base = self.take_base()         # (x's gradient continues one it does not own: the residual operand)
+            tl = None
+            if x.grad_amax is not None:
+                tl = BnTail()
+                tl.amax = x.grad_amax.data_ptr()
+            self._conv_dgrad_launch(c, d, buf, base if base is not None else (buf if acc else None), tail=tl)
+            return
+        # the ReLU mask and the two per-channel sums of the BatchNorm backward ride in the
+        # data-gradient epilogue; only finalise + apply remain as separate launches
+        # (fold: the 1x1 convolution that produced x forms this BatchNorm's dx in its own backward — dz then has
+        # to outlive this op's launches, and its maximum is what the bound of dx is made from)
+        fold = not d.native and self.fold_ok(src)
+        dz = self._dz_buffer(x, fold)
+        if d.native:
+            tiles = self.lib.dsnt_conv_dgrad_strided_tiles(C.byref(c.g))
+        else:
+            bm = 128 if d.d6 else self.lib.dsnt_conv_fwd_bm(C.byref(d.gd))
+            tiles = (x.M + bm - 1) // bm
+        part = self.scratch('bnpart', tiles * 2 * x.C).view(-1)
+        bnb = self._bn_epilogue(x, src)
+        tl, dz_amax = None, None
+        if fold:
+            tl, dz_amax = BnTail(), self.amax_slot()
+            tl.amax = dz_amax.data_ptr()
+        if ap is not None:
+            assert d.d16 and d.d_stream and not d.native
+            name = 'dsnt_conv_dgrad_f16x3_stream_apply'
+            aps, applied = self._bn_apply(y, ap)
+            e = self.b(name, ap['dz'], aps, gy, d.wq16, self.dgrad_total, d.wbd, ap['bound'], dz, part, self._share(), d.gd, bnb, tl)
+            self._struct_bytes(name, 4 * y.buf.numel())
+            self.f16_uses.append((e, dict(kind='dgrad', name=c.name, w=d.wd, w_bound=d.wbd, g_bound=ap['bound'], g_apply=applied)))
+        else:
+            self._conv_dgrad_launch(c, d, dz, None, part, bnb, tl)
+        self._norm_backward(src, dz, reduced=(part, tiles), dz_amax=dz_amax)
 
-                    g_amax = y.grad_amax if (self.use_f16x3 and p.stride == 1) else None
-                    d16 = d6 and g_amax is not None and slot is not None and self.dgrad_planes16 is not None
-                    if d16:
-                        wq16 = self.dgrad_planes16[slot:slot + nw]
-                        wbd = self.dgrad_bounds[64 * slot_k:64 * slot_k + 64]
-                        # (the data gradient's filter is [Cin][3][3][Cout]: its "Cout" is this convolution's Cin)
-                        d_stream = self.stream_ok(p, gd, x.M, None)
-                        self._f16_dw_rows.append([wd.data_ptr(), wq16.data_ptr(), wbd.data_ptr(), nw, self.dgrad_total] +
-                                                 ([p.Cin, p.Cout] if d_stream else [0, 0]))
+    def _conv_residual_grads(self, c, gy, wl, defer_res):
+        """The gradients of c's residual inputs, last: gy is dead after c's own launches (the weight-gradient lane must have read
+        it before anyone accumulates into the donated buffer)."""
+        y = c.y
+        if c.res1 is not None or c.res2 is not None:
+            self.sync_bwd(wl, self.lane)
+        donated = False
+        for r in (c.res1, c.res2):
+            if r is None:
+                continue
+            if defer_res:
+                r.base, r.base_amax = gy, y.grad_amax
+            elif (donated and self.share_grads and r.grad is None and r.pending_apply is None and r.uses == 1 and
+                    not r.gives_away and not r.is_branch):
+                # the buffer went to the first residual input; this one has a single consumer, so its gradient is dL/dy
+                # and nothing else, and its producer only READS it (it gives no buffer away): shared, not copied.  Every
+                # later writer of the buffer comes after that reader in lane order, or waits for the lane that reads
+                # (`_wgrad_lane_reads` is keyed by the buffer)
+                r.grad, r.grad_amax, r.grad_shared = gy, y.grad_amax, True
+            else:
+                donated = self.grad_identity(r, gy, donate=not donated, g_amax=y.grad_amax) or donated
 
-                    def dgrad(out, res, part=None, bnb=None, tail=None):
-                        if native:
-                            self.b('dsnt_conv_dgrad_strided', gy, wd, out, res, part, g, bnb, tail)
-                        elif d16:
-                            e = self.b('dsnt_conv_fwd_f16x3_stream' if d_stream else 'dsnt_conv_fwd_f16x3_ex', gsrc, wq16,
-                                       self.dgrad_total, wbd, g_amax, None, out, None,
-                                       None, 2 if ((d_stream or p.R == 1) and self.lane != 0 and self.conv_share) else 0, res, None, part, gd, bnb, tail)
-                            self.f16_uses.append((e, dict(kind='dgrad', name=name, g=gsrc, g_bound=g_amax, w=wd, w_bound=wbd)))
-                        elif d6:
-                            self.b('dsnt_conv_fwd_bf16x6_ex', gsrc, wq, wq_stride, None, out, None, None, 0, res, None,
-                                   part, gd, bnb, tail)
-                        else:
-                            self.b('dsnt_conv_fwd_ex', gsrc, wd, None, out, None, None, 0, res, None, part, gd, bnb, tail)
-                    if normed:
-                        # the ReLU mask and the two per-channel sums of the BatchNorm backward ride in the
-                        # data-gradient epilogue; only finalise + apply remain as separate launches
-                        # (fold: the 1x1 convolution that produced x forms this BatchNorm's dx in its own backward — dz then has
-                        # to outlive this op's launches, and its maximum is what the bound of dx is made from)
-                        fold = not native and self.fold_ok(src)
-                        dz = self.empty(x.M * x.C) if fold else self.scratch('da', x.M * x.C).view(-1)[:x.M * x.C]
-                        if native:
-                            tiles = self.lib.dsnt_conv_dgrad_strided_tiles(C.byref(g))
-                        else:
-                            bm = 128 if d6 else self.lib.dsnt_conv_fwd_bm(C.byref(gd))
-                            tiles = (x.M + bm - 1) // bm
-                        part = self.scratch('bnpart', tiles * 2 * x.C).view(-1)
-                        bnb = BnBwdEpilogue(_lib.ptr(x.buf), _lib.ptr(src.scale), _lib.ptr(src.shift),
-                                            _lib.ptr(src.mean), _lib.ptr(src.invstd), 1 if src.relu else 0)
-                        tl, dz_amax = None, None
-                        if fold:
-                            tl, dz_amax = BnTail(), self.amax_slot()
-                            tl.amax = dz_amax.data_ptr()
-                        if fold3:
-                            assert d16 and d_stream and not native
-                            n2 = ap['n']
-                            aps = BnBwdApply(_lib.ptr(y.buf), _lib.ptr(n2.scale), _lib.ptr(n2.mean), _lib.ptr(n2.invstd), _lib.ptr(ap['coef']))
-                            shr = 2 if (self.lane != 0 and self.conv_share) else 0
-                            e = self.b('dsnt_conv_dgrad_f16x3_stream_apply', ap['dz'], aps, gy, wq16, self.dgrad_total, wbd, ap['bound'],
-                                       dz, part, shr, gd, bnb, tl)
-                            nb = 4 * y.buf.numel()          # (the tensor named inside the struct)
-                            self.bytes_bwd += nb
-                            self.bytes_by_name['dsnt_conv_dgrad_f16x3_stream_apply'] = self.bytes_by_name.get('dsnt_conv_dgrad_f16x3_stream_apply', 0) + nb
-                            self.f16_uses.append((e, dict(kind='dgrad', name=name, w=wd, w_bound=wbd, g_bound=ap['bound'],
-                                                          g_apply=dict(dz=ap['dz'], y=y.buf, scale=n2.scale, mean=n2.mean,
-                                                                       invstd=n2.invstd, coef=ap['coef']))))
-                        else:
-                            dgrad(dz, None, part, bnb, tl)
-                        self._norm_backward(src, dz, reduced=(part, tiles), dz_amax=dz_amax)
-                    else:
-                        # (d6: the large-tile kernels; their epilogue can leave max|written gradient| as the next bound)
-                        buf, acc = self.grad_target(x, amax=(bool(d6) or bool(native)) and self.raw_f16, base_ok=True)
-                        base = self.take_base()         # (x's gradient continues one it does not own: the residual operand)
-                        tl = None
-                        if x.grad_amax is not None:
-                            tl = BnTail()
-                            tl.amax = x.grad_amax.data_ptr()
-                        dgrad(buf, base if base is not None else (buf if acc else None), tail=tl)
-
-                if fold3:
-                    emit_dgrad()
-                    wl, defer_res = emit_wgrad()
-                else:
-                    wl, defer_res = emit_wgrad()
-                    emit_dgrad()
-            # identity branches last: gy is dead after the launches above (the weight-gradient lane
-            # must have read it before anyone accumulates into the donated buffer)
-            if res1 is not None or res2 is not None:
-                self.sync_bwd(wl, cur)
-            donated = False
-            for r in (res1, res2):
-                if r is not None and defer_res:
-                    r.base, r.base_amax = gy, (y.grad_amax if self.amax_all else None)
-                    continue
-                if r is not None:
-                    if (donated and self.share_grads and r.grad is None and r.pending_apply is None and r.uses == 1 and
-                            not r.gives_away and not r.is_branch):
-                        # the buffer went to the first residual input; this one has a single consumer, so its gradient is dL/dy
-                        # and nothing else, and its producer only READS it (it gives no buffer away): shared, not copied.  Every
-                        # later writer of the buffer comes after that reader in lane order, or waits for the lane that reads
-                        # (`_wgrad_lane_reads` is keyed by the buffer)
-                        r.grad = gy
-                        r.grad_amax = y.grad_amax if self.amax_all else None
-                        r.grad_shared = True
-                        continue
-                    donated = self.grad_identity(r, gy, donate=not donated, g_amax=y.grad_amax) or donated
-
-        self.on_backward(backward)
-        return y
+    def _f_with_stats(self, name, y, tensors, dims):
+        """Emit the element-wise forward launch `name` that writes y — as `name`_stats where the same pass also leaves what y's
+        consumers need: training, the batch statistics of y (the BatchNorm that reads it next), plus the bound of its raw
+        consumers if y is large enough for fp16x3; eval and large, that bound alone (no statistics in eval mode)."""
+        part = None
+        if self.training:
+            tiles = (y.M + 127) // 128
+            part = self.empty(tiles, 2, y.C)
+            y.stats = (part, tiles)
+        if self.use_f16x3 and y.M >= self.bf16x6_min_rows:
+            y.amax_tail = BnTail()
+        if part is None and y.amax_tail is None:
+            self.f(name, *tensors, *dims)
+        else:
+            self.f(name + '_stats', *tensors, part, *dims, y.amax_tail)
 
     def bn_act(self, x, bn, relu=True, name=''):
         """Materialised y = relu?(bn(x)) (the stem: hourglass.py:157-159)."""
@@ -1387,20 +1414,9 @@ class Tape:
         self.materialize(n)
         y = self.act(x.N, x.H, x.W, x.C, name)
         x.uses += 1
-        big = self.use_f16x3 and y.M >= self.bf16x6_min_rows
-        if self.training and self.fuse_op_stats:
-            # the statistics of y (the first Bottleneck's BatchNorm reads it next) and the bound of its raw consumer
-            # (that Bottleneck's skip projection) ride in the same pass
-            tiles = (y.M + 127) // 128
-            part = self.empty(tiles, 2, x.C)
-            y.amax_tail = BnTail() if big else None
-            self.f('dsnt_bn_act_fwd_stats', x.buf, n.scale, n.shift, 1 if n.relu else 0, y.buf, part, x.M, x.C, y.amax_tail)
-            y.stats = (part, tiles)
-        elif not self.training and big:
-            y.amax_tail = BnTail()
-            self.f('dsnt_bn_act_fwd_stats', x.buf, n.scale, n.shift, 1 if n.relu else 0, y.buf, None, x.M, x.C, y.amax_tail)
-        else:
-            self.f('dsnt_bn_act_fwd', x.buf, n.scale, n.shift, 1 if n.relu else 0, y.buf, x.M, x.C)
+        # the statistics of y (the first Bottleneck's BatchNorm reads it next) and the bound of its raw consumer
+        # (that Bottleneck's skip projection) ride in the same pass
+        self._f_with_stats('dsnt_bn_act_fwd', y, (x.buf, n.scale, n.shift, 1 if n.relu else 0, y.buf), (x.M, x.C))
         if self.record:
             def backward():
                 self._norm_backward(n, y.grad)
@@ -1411,18 +1427,8 @@ class Tape:
         y = self.act(x.N, x.H // 2, x.W // 2, x.C, name)
         x.uses += 1
         idx = self.empty(x.N, x.H // 2, x.W // 2, x.C, dtype=torch.uint8)
-        if self.training and self.fuse_op_stats:
-            # the consumer is a BatchNorm (hourglass.py:33): its batch statistics ride in the same pass
-            tiles = (y.M + 127) // 128
-            part = self.empty(tiles, 2, x.C)
-            y.amax_tail = BnTail() if (self.use_f16x3 and y.M >= self.bf16x6_min_rows) else None
-            self.f('dsnt_maxpool2_fwd_stats', x.buf, y.buf, idx, part, x.N, x.H, x.W, x.C, y.amax_tail)
-            y.stats = (part, tiles)
-        elif not self.training and self.use_f16x3 and y.M >= self.bf16x6_min_rows:
-            y.amax_tail = BnTail()        # no statistics in eval mode, but the next convolution's operand bound
-            self.f('dsnt_maxpool2_fwd_stats', x.buf, y.buf, idx, None, x.N, x.H, x.W, x.C, y.amax_tail)
-        else:
-            self.f('dsnt_maxpool2_fwd', x.buf, y.buf, idx, x.N, x.H, x.W, x.C)
+        # the consumer is a BatchNorm (hourglass.py:33): its batch statistics ride in the same pass
+        self._f_with_stats('dsnt_maxpool2_fwd', y, (x.buf, y.buf, idx), (x.N, x.H, x.W, x.C))
         if self.record:
             def backward():
                 add, x.pending_add = x.pending_add, None
@@ -1493,17 +1499,7 @@ class Tape:
         up.uses += 1
         low.uses += 1
         out.gives_away = True                   # dL/d out's buffer becomes dL/d up in backward
-        if self.training and self.fuse_op_stats:
-            tiles = (out.M + 127) // 128
-            part = self.empty(tiles, 2, up.C)
-            out.amax_tail = BnTail() if (self.use_f16x3 and out.M >= self.bf16x6_min_rows) else None
-            self.f('dsnt_upsample2_add_fwd_stats', up.buf, low.buf, out.buf, part, up.N, up.H, up.W, up.C, out.amax_tail)
-            out.stats = (part, tiles)
-        elif not self.training and self.use_f16x3 and out.M >= self.bf16x6_min_rows:
-            out.amax_tail = BnTail()
-            self.f('dsnt_upsample2_add_fwd_stats', up.buf, low.buf, out.buf, None, up.N, up.H, up.W, up.C, out.amax_tail)
-        else:
-            self.f('dsnt_upsample2_add_fwd', up.buf, low.buf, out.buf, up.N, up.H, up.W, up.C)
+        self._f_with_stats('dsnt_upsample2_add_fwd', out, (up.buf, low.buf, out.buf), (up.N, up.H, up.W, up.C))
         if self.record:
             point = self.wgrad_lane is not None and low.M <= self.release_rows
             self._release_total += point
@@ -1550,9 +1546,9 @@ class Tape:
         """The 7x7 / stride 2 / pad 3 convolution of a planar (<= 4 channel) input as a 4x4 / stride 1 / pad 1 convolution
         on its space-to-depth form (csrc/elementwise.hip: dsnt_s2d_input / dsnt_s2d_weights): K = 256 in 16-channel steps,
         so the stem runs on the split-precision matrix-core kernels like every other large convolution instead of the
-        fp32 MFMA (245 -> ~80 us at batch 32).  Returns None if it does not apply (the caller then uses `conv`)."""
+        fp32 MFMA (245 -> ~80 us at batch 32; -0.08 ms a step).  Returns None if it does not apply (the caller then uses `conv`)."""
         got = self._planar_src.get(id(x))
-        if (got is None or not self.use_f16x3 or not self.stem_s2d_on or p.R != 7 or p.S != 7 or p.stride != 2 or p.pad != 3
+        if (got is None or not self.use_f16x3 or p.R != 7 or p.S != 7 or p.stride != 2 or p.pad != 3
                 or p.dil != 1 or x.C != 4 or x.H % 2 or x.W % 2 or x.N * (x.H // 2) * (x.W // 2) < self.bf16x6_min_rows):
             return None
         src, entry = got

@@ -468,7 +468,7 @@ class Hourglass(TapeModule):
         g = self.hg[n - 1]
         # the full-resolution skip branch is independent of the whole low-resolution recursion:
         # trace it on the side lane so its few large kernels overlap the many small ones
-        if t.record and t.use_lanes and t.fuse_join:
+        if t.record and t.use_lanes:        # (the branch gradient joined inside the pool's backward: -0.15 ms)
             # Training: the branch is traced LAST, so that its backward is emitted first and its gradient exists when
             # the pool's backward is emitted — the main lane then waits for the side lane, takes the branch's gradient
             # buffer over as x's and the pool's backward ACCUMULATES into it (no separate x.grad += branch.grad pass:

@@ -3,6 +3,8 @@ runs, with the device check of `_lib.ptr` bypassed): the SCHEDULE the measuremen
 which lane carries what, where lanes wait for each other, which launches were fused away."""
 import ctypes as C
 import collections
+import importlib.util
+import os
 
 import pytest
 import torch
@@ -265,3 +267,30 @@ def test_persistent_stage_runs_of_the_recorded_lists(tape):
             assert lib.dsnt_list_size(h) == size and lib.dsnt_list_stages(h, None) == 0
         finally:
             lib.dsnt_list_destroy(h)
+
+
+def test_schedule_dump_is_canonical_and_sees_a_moved_launch(monkeypatch_module):
+    """tools/schedule_dump.py, the check that a change to the engine left every schedule as it was: two fresh traces of one program
+    (different addresses throughout) give the same text, every pointer on the lists lies in an allocation the dump knows, and one
+    backward launch moved to another lane changes the text."""
+    from dsnt import _lib
+    import dsnt.engine as E
+    import dsnt.model  # noqa: F401  (every module that binds `ptr` by name is imported BEFORE the patch)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('schedule_dump', os.path.join(root, 'tools', 'schedule_dump.py'))
+    sd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(sd)
+    monkeypatch_module.setattr(_lib, 'ptr', sd.cpu_ptr)
+    monkeypatch_module.setattr(E._lib, 'ptr', sd.cpu_ptr)
+    texts = []
+    for _ in range(2):
+        tape, extra = sd.trace('hg1', True, (2, 3, 128, 128))
+        text, unresolved = sd.dump(tape, extra)
+        assert unresolved == 0
+        texts.append(text)
+    assert texts[0] == texts[1] and len(texts[0].splitlines()) > len(tape.fwd) + len(tape.bwd)
+    i = next(i for i, e in enumerate(tape.bwd) if e[0] is not None and e[2].startswith('dsnt_conv'))
+    fn, args, name, lane = tape.bwd[i]
+    tape.bwd[i] = (fn, args, name, lane + 1)
+    moved, unresolved = sd.dump(tape, extra)
+    assert unresolved == 0 and moved != texts[0]
