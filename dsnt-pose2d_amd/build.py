@@ -3,6 +3,7 @@
 Cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
 repo snapshot.  Usage: python dsnt-pose2d_amd/build.py [--force]
 """
+import glob
 import os
 import subprocess
 import sys
@@ -13,10 +14,10 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libdsnt_hip.so')
 # the general convolution units: built without the SLP vectoriser whatever DSNT_SLP says (see build())
 NO_SLP = ('conv_f32.hip', 'conv_split6.hip', 'conv_wgrad.hip', 'conv_prep.hip')
-# (longest compiles first: four run at a time)
+# (longest compiles first: four run at a time; the short element-wise units last)
 SOURCES = ['api.cpp', 'conv3s.hip', 'head.hip', 'gemm1.hip', 'conv_split6.hip', 'conv_f32.hip', 'wgrad3.hip', 'bwd1.hip',
-           'fwd1.hip', 'conv_wgrad.hip', 'elementwise.hip', 'wgrad1.hip', 'augment.hip', 'conv_prep.hip', 'stem4.hip', 'debug.hip',
-           'heatmap.hip', 'dgrad_up.hip', 'render.hip']
+           'fwd1.hip', 'conv_wgrad.hip', 'wgrad1.hip', 'augment.hip', 'conv_prep.hip', 'stem4.hip',
+           'heatmap.hip', 'dgrad_up.hip', 'render.hip', 'bn.hip', 'resample.hip', 'flat.hip', 'optim.hip', 'pckh.hip']
 FLAGS = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wno-unused-value',
          '-Wno-unused-result']
 # kernel experiments: extra compiler flags and another output name (load it with DSNT_HIP_LIB=<path>), e.g.
@@ -32,9 +33,7 @@ def _newer(a, b):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    deps = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'bn_pro.h'), os.path.join(CSRC, 'conv_split.h'), os.path.join(CSRC, 'conv_epilogue.h'),
-            os.path.join(CSRC, 'wgrad3.h'), os.path.join(CSRC, 'gemm1.h'), os.path.join(CSRC, 'conv3s.h'), os.path.join(CSRC, 'bwd1.h'), os.path.join(CSRC, 'fwd1.h'), os.path.join(CSRC, 'stem4.h'), os.path.join(CSRC, 'stage.h'), os.path.join(CSRC, 'ew_bodies.h'), os.path.join(CSRC, 'flipmerge.h'),
-            os.path.join(HERE, '..', 'include', 'dsnt_hip.h'), os.path.join(HERE, '..', 'include', 'dsnt_hip_debug.h')]
+    deps = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + sorted(glob.glob(os.path.join(HERE, '..', 'include', '*.h')))
     objs, jobs = [], []
     bdir = 'build' if not os.environ.get('DSNT_LIB_NAME') else 'build_' + os.path.splitext(os.environ['DSNT_LIB_NAME'])[0]
     os.makedirs(os.path.join(CSRC, bdir), exist_ok=True)

@@ -5,7 +5,6 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/dsnt_hip.h"
-#include "../../include/dsnt_hip_debug.h"
 
 #define DSNT_WAVE 64
 
@@ -28,6 +27,11 @@ dsnt_list* dsnt_recording(void);
     } while (0)
 
 static inline bool dsnt_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// Workgroups of a grid-stride launch over n items: enough to cover them once, at most 4096.
+static inline int flat_grid(long n, int block) {
+    long g = (n + block - 1) / block;
+    return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
 
 // Per-DEVICE host caches (one process may drive several devices; entry points may be called from several threads — autograd's
 // backward thread).  dsnt_device_id(): the current device, clamped to the cache size.  dsnt_device_cus(): its CU count.

@@ -501,8 +501,6 @@ static void launch_fwd6(const ConvP& p, bool pro, hipStream_t st) {
 #ifndef FWD6_BN64_ROWS_DEFAULT
 #define FWD6_BN64_ROWS_DEFAULT 8192
 #endif
-static bool g_force_gemm6 = false;      // debug/bench: route 3x3 convolutions through the implicit-GEMM kernel
-extern "C" int dsnt_debug_force_gemm6(int on) { g_force_gemm6 = on != 0; return DSNT_OK; }
 
 static int conv_fwd6_impl(const float* x, const void* w_planes, int64_t plane_stride, const float* bias, float* y,
                           const float* in_scale, const float* in_shift, int in_relu,
@@ -540,12 +538,12 @@ static int conv_fwd6_impl(const float* x, const void* w_planes, int64_t plane_st
             dsnt_gemm1_launch(p, ntw, in_scale != nullptr, st, share_chip);
             DSNT_CHECK_LAUNCH("dsnt_conv_fwd_f16x3");
         }
-        if (conv3x3_halo_ok(g) && !g_force_gemm6) {
+        if (conv3x3_halo_ok(g)) {
             if (BN == 128) launch_conv3x3_6<2, true>(p, in_scale != nullptr, st);
             else launch_conv3x3_6<1, true>(p, in_scale != nullptr, st);
         } else if (BN == 128) launch_fwd6<2, 2, 2, 2, true>(p, in_scale != nullptr, st);
         else launch_fwd6<2, 2, 2, 1, true>(p, in_scale != nullptr, st);
-    } else if (conv3x3_halo_ok(g) && !g_force_gemm6) {
+    } else if (conv3x3_halo_ok(g)) {
         if (BN == 128) launch_conv3x3_6<2>(p, in_scale != nullptr, st);
         else launch_conv3x3_6<1>(p, in_scale != nullptr, st);
     } else if (BN == 128) launch_fwd6<2, 2, 2, 2>(p, in_scale != nullptr, st);
@@ -634,5 +632,5 @@ extern "C" int dsnt_conv_f16x3_route(const dsnt_conv_geom* g, int wgrad) {
     p.a_bound = &one; p.w_bound = &one; p.wq = reinterpret_cast<const unsigned short*>(&one);
     conv_geom_fill(p, g);
     if (dsnt_gemm1_cfg(p) > 0) return 1;
-    return conv3x3_halo_ok(g) && !g_force_gemm6 ? 2 : 0;
+    return conv3x3_halo_ok(g) ? 2 : 0;
 }

@@ -1,11 +1,18 @@
 // Bodies of the small NHWC kernels that can also run inside a persistent stage (stage.h): device functions of a VIRTUAL workgroup
-// index, so that the stand-alone launch (elementwise.hip) and the stage's loop (conv_f32.hip) execute the same instructions.  Each is
+// index, so that the stand-alone launch (bn.hip, resample.hip) and the stage's loop (conv_f32.hip) execute the same instructions.  Each is
 // written for 256 live threads; in a 512-thread stage workgroup the upper half skips the work and keeps the barriers.
 #pragma once
 #include "common.h"
 #include "bn_pro.h"
 
 #define TILE_ROWS 128
+// Thread mapping of the tile kernels (tile_reduce_kernel in bn.hip, tile_op_stats_body below), host side, shared so that
+// their sums stay bit-identical to each other: a workgroup covers `cgs` float4 column groups x (256 / cgs) row lanes of one 128-row tile.  Large tensors: all columns in one
+// workgroup (up to 256 groups per pass).  Small ones (fewer than 256 tiles — the low-resolution hourglass levels, where
+// a 4..64-workgroup launch is pure latency): 16 column groups per workgroup, the rest of the columns on gridDim.y, so a
+// thread walks 8 rows instead of 32 and the launch has 4x (C = 256) the workgroups.
+static inline int tile_cgs(long tiles, int C4) { return tiles < 256 && C4 > 16 && C4 % 16 == 0 ? 16 : (C4 < 256 ? C4 : 256); }
+static inline unsigned tile_grid_y(long tiles, int C4) { const int c = tile_cgs(tiles, C4); return c == 16 && C4 > 16 ? C4 / 16 : 1; }
 
 struct TileOpP {
     const float* a; const float* b; float* y; unsigned char* idx; float* partial;

@@ -976,12 +976,14 @@ extern "C" int dsnt_expect_bwd(const float* gcoords, float* ghm, int64_t rows, i
     DSNT_CHECK_LAUNCH("dsnt_expect_bwd");
 }
 
+static inline float gauss_k(float sigma) { return (float)(-0.5 * (1.0 / (double)sigma) * (1.0 / (double)sigma)); }
+
 extern "C" int dsnt_make_gauss(const float* coords, float* out, int64_t rows, int h, int w, float sigma,
                                void* stream) {
     DSNT_REQUIRE(coords && out, DSNT_ERR_ARG, "dsnt_make_gauss: null tensor");
     DSNT_REQUIRE(sigma > 0.f, DSNT_ERR_ARG, "dsnt_make_gauss: sigma must be positive");
     if (int e = check_rows("dsnt_make_gauss", rows, h, w)) return e;
-    const float k = (float)(-0.5 * (1.0 / (double)sigma) * (1.0 / (double)sigma));
+    const float k = gauss_k(sigma);
     DSNT_LAUNCH(make_gauss_kernel, dim3((int)rows), dim3(HB), 0, (hipStream_t)stream, coords, out, h, w, k);
     DSNT_CHECK_LAUNCH("dsnt_make_gauss");
 }
@@ -991,13 +993,11 @@ extern "C" int dsnt_make_gauss_bwd(const float* coords, const float* g_out, floa
     DSNT_REQUIRE(coords && g_out && g_coords, DSNT_ERR_ARG, "dsnt_make_gauss_bwd: null tensor");
     DSNT_REQUIRE(sigma > 0.f, DSNT_ERR_ARG, "dsnt_make_gauss_bwd: sigma must be positive");
     if (int e = check_rows("dsnt_make_gauss_bwd", rows, h, w)) return e;
-    const float k = (float)(-0.5 * (1.0 / (double)sigma) * (1.0 / (double)sigma));
+    const float k = gauss_k(sigma);
     DSNT_LAUNCH(make_gauss_bwd_kernel, dim3((int)rows), dim3(HB), 0, (hipStream_t)stream, coords, g_out,
                        g_coords, h, w, k);
     DSNT_CHECK_LAUNCH("dsnt_make_gauss_bwd");
 }
-
-static inline float gauss_k(float sigma) { return (float)(-0.5 * (1.0 / (double)sigma) * (1.0 / (double)sigma)); }
 
 extern "C" int dsnt_reg_fwd(const float* hm, const float* target, float* per_row, int64_t rows, int h, int w,
                             float sigma, int kind, void* stream) {

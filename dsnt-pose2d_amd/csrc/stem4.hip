@@ -1,5 +1,5 @@
 // The stem of the hourglass (hourglass.py:157 `conv1`: 7x7 / stride 2 / pad 3 on the 3-channel image) in the form the engine runs
-// it: a 4x4 / stride 1 / pad 1 convolution of the 16-channel space-to-depth image (csrc/elementwise.hip: dsnt_s2d_input), 64 output
+// it: a 4x4 / stride 1 / pad 1 convolution of the 16-channel space-to-depth image (csrc/flat.hip: dsnt_s2d_input), 64 output
 // channels, fp16x3 split: forward (stem4_fwd_kernel) and weight gradient (stem4_wgrad_kernel, below); the stem needs no data gradient.
 //
 // Why a kernel of its own: K = 256 is sixteen taps of ONE 16-channel chunk and N = 64, i.e. 168 MB of traffic against 17 GFLOP —

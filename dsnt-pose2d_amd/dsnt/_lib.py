@@ -172,14 +172,6 @@ SIGNATURES = {
     'dsnt_epoch_indices': [L, C.c_uint64, C.c_uint64, L, L, I, P, P],
     'dsnt_crop_affine': [P, L, P, P, L, P, P, I, I, P, P, P],
     'dsnt_render_pose': [P, I, P, P, I, I, I, I, P, I, I, P, L, P, F, P, P, I, P, P, I, F, F, P, P],
-    'dsnt_debug_mfma_peak': [P, I, I, I, I, P],
-    'dsnt_debug_coexec': [P, I, I, I, P],
-    'dsnt_debug_bf16_peak': [P, I, I, I, I, P],
-    'dsnt_debug_starve': [P, P, I, I, I, I, P],
-    'dsnt_debug_grid_barrier': [P, I, I, I, P, P],
-    'dsnt_debug_grid_barrier2': [P, I, I, I, P, P],
-    'dsnt_debug_empty': [I, I, P, P],
-    'dsnt_debug_force_gemm6': [I],
 }
 # entry points without the status/stream convention
 PLAIN = {

@@ -1544,7 +1544,7 @@ class Tape:
 
     def stem_s2d(self, x, p, name='stem'):
         """The 7x7 / stride 2 / pad 3 convolution of a planar (<= 4 channel) input as a 4x4 / stride 1 / pad 1 convolution
-        on its space-to-depth form (csrc/elementwise.hip: dsnt_s2d_input / dsnt_s2d_weights): K = 256 in 16-channel steps,
+        on its space-to-depth form (csrc/flat.hip: dsnt_s2d_input / dsnt_s2d_weights): K = 256 in 16-channel steps,
         so the stem runs on the split-precision matrix-core kernels like every other large convolution instead of the
         fp32 MFMA (245 -> ~80 us at batch 32; -0.08 ms a step).  Returns None if it does not apply (the caller then uses `conv`)."""
         got = self._planar_src.get(id(x))

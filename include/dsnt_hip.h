@@ -10,9 +10,7 @@
  * Conventions
  *  - plain pointers + sizes; every pointer is DEVICE memory owned by the caller
  *    (PyTorch's allocator); the library allocates nothing and the product entry points
- *    declared here keep no state except a thread-local error string (the calibration
- *    probes and debug switches live in dsnt_hip_debug.h, are not part of this ABI and are the
- *    only code with process-wide switches);
+ *    declared here keep no state except a thread-local error string;
  *  - all arithmetic is fp32; activations are NHWC ([N][H][W][C], C innermost);
  *    conv weights are OHWI ([Cout][R][S][Cin]); heat-maps for the DSNT head are
  *    planar rows ([rows = N*J][H*W]);

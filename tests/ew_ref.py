@@ -1,4 +1,4 @@
-"""The element-wise kernels of csrc/elementwise.hip and csrc/ew_bodies.h restated in numpy fp64, for
+"""The element-wise kernels of csrc/bn.hip, resample.hip, flat.hip, optim.hip and csrc/ew_bodies.h restated in numpy fp64, for
 tests/test_ew_ref_cpu.py (which pins this file to the torch CPU operators) and tests/test_elementwise_edges_gpu.py
 (which holds the HIP kernels to it).  No device code: everything here takes and returns numpy arrays on the host.
 
@@ -19,18 +19,18 @@ def gamma(k):
 
 # ---------------------------------------------------------------- host-side launch arithmetic (mirrors)
 def flat_grid(n, block=256):
-    """csrc/elementwise.hip `flat_grid()`: workgroups of a flat launch, capped at 4096."""
+    """csrc/common.h `flat_grid()`: workgroups of a flat launch, capped at 4096."""
     g = (n + block - 1) // block
     return 1 if g < 1 else (4096 if g > 4096 else g)
 
 
 def tile_cgs(tiles, C4):
-    """csrc/elementwise.hip `tile_cgs()`: float4 column groups a tile workgroup covers per pass."""
+    """csrc/ew_bodies.h `tile_cgs()`: float4 column groups a tile workgroup covers per pass."""
     return 16 if (tiles < 256 and C4 > 16 and C4 % 16 == 0) else (C4 if C4 < 256 else 256)
 
 
 def tile_grid_y(tiles, C4):
-    """csrc/elementwise.hip `tile_grid_y()`."""
+    """csrc/ew_bodies.h `tile_grid_y()`."""
     c = tile_cgs(tiles, C4)
     return C4 // 16 if (c == 16 and C4 > 16) else 1
 

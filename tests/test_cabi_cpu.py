@@ -7,8 +7,10 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = [os.path.join(ROOT, 'include', 'dsnt_hip.h'),          # the product ABI
-           os.path.join(ROOT, 'include', 'dsnt_hip_debug.h')]    # calibration probes and debug switches (tools/ only)
+HEADERS = [os.path.join(ROOT, 'include', 'dsnt_hip.h')]          # the product ABI
+# the calibration probes and the debug switch the library once carried beside the ABI: gone, and not to come back unnoticed
+RETIRED_PROBES = ['dsnt_debug_mfma_peak', 'dsnt_debug_coexec', 'dsnt_debug_bf16_peak', 'dsnt_debug_starve',
+                  'dsnt_debug_grid_barrier', 'dsnt_debug_grid_barrier2', 'dsnt_debug_empty', 'dsnt_debug_force_gemm6']
 
 
 def _declared(headers=HEADERS):
@@ -32,6 +34,65 @@ def test_library_exports_every_declared_symbol():
     assert lib.dsnt_version() >= 100
     # the product header declares no diagnostics, and nothing in the product package binds one at import time
     assert not [n for n in _declared(HEADERS[:1]) if n.startswith('dsnt_debug')]
+    for n in RETIRED_PROBES:
+        assert not hasattr(lib, n), 'libdsnt_hip.so still exports ' + n
+
+
+def _prototypes(headers=HEADERS):
+    """name -> (return type, [argument types]) of every prototype, as C type strings without the parameter names."""
+    protos = {}
+    for h in headers:
+        text = re.sub(r'/\*.*?\*/', '', open(h).read(), flags=re.S)
+        text = re.sub(r'//[^\n]*', '', text)
+        text = re.sub(r'^\s*#[^\n]*', '', text, flags=re.M)
+        for ret, name, args in re.findall(r'([A-Za-z_][\w\s]*?[\s\*]+)(dsnt_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', text):
+            types = []
+            for a in args.split(','):
+                a = ' '.join(a.split())
+                if a in ('', 'void'):
+                    continue
+                types.append(re.sub(r'\s*\b[A-Za-z_]\w*$', '', a).replace(' *', '*'))    # drop the parameter's name
+            assert name not in protos, name + ' declared twice'
+            protos[name] = (' '.join(ret.split()).replace(' *', '*'), types)
+    return protos
+
+
+def _ctypes_ok(ctype, bound, _lib):
+    scalars = {'int': C.c_int, 'int64_t': C.c_int64, 'float': C.c_float, 'double': C.c_double,
+               'uint64_t': C.c_uint64, 'uint32_t': C.c_uint32}
+    structs = {'const dsnt_conv_geom*': _lib.GP, 'dsnt_bn_bwd_epilogue*': _lib.BP, 'dsnt_bn_prologue*': _lib.PP,
+               'dsnt_out_bounds*': _lib.TP, 'dsnt_bn_bwd_apply*': _lib.AP}
+    if ctype in scalars:
+        return bound is scalars[ctype]
+    for k, v in structs.items():
+        if ctype in (k, 'const ' + k):
+            return bound is v
+    if ctype.endswith('*'):
+        return bound in (C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p))
+    return False
+
+
+def test_ctypes_tables_match_the_header_argument_by_argument():
+    """A ctypes row of the wrong width or length is silent undefined behaviour: every prototype of include/dsnt_hip.h is parsed
+    and held against _lib.SIGNATURES (status return, trailing `void* stream` included) / _lib.PLAIN (return type too)."""
+    from dsnt import _lib
+    protos = _prototypes()
+    bound = set(_lib.SIGNATURES) | set(_lib.PLAIN)
+    assert len(protos) == len(bound), (sorted(bound - set(protos)), sorted(set(protos) - bound))    # nothing the regex cannot read
+    assert set(protos) == bound
+    returns = {'int': C.c_int, 'int64_t': C.c_int64, 'const char*': C.c_char_p, 'void': None}
+    for name, (ret, types) in sorted(protos.items()):
+        if name in _lib.SIGNATURES:
+            assert ret == 'int', (name, ret)
+            args = _lib.SIGNATURES[name]
+        else:
+            res, args = _lib.PLAIN[name]
+            want = returns[ret] if ret in returns else C.c_void_p
+            assert ret in returns or ret.endswith('*'), (name, ret)
+            assert res is want, (name, ret, res)
+        assert len(args) == len(types), (name, types, args)
+        for i, (t, b) in enumerate(zip(types, args)):
+            assert _ctypes_ok(t, b, _lib), '%s: argument %d is `%s` in the header, %r in dsnt._lib' % (name, i, t, b)
 
 
 def test_argument_validation_without_gpu():

@@ -1,5 +1,5 @@
-"""The element-wise HIP kernels (csrc/elementwise.hip, csrc/ew_bodies.h) against tests/ew_ref.py (numpy fp64), through the
-C ABI, at the sizes and inputs where the rest of the suite does not go: past one grid stride of the flat launches (a),
+"""The element-wise HIP kernels (csrc/bn.hip, resample.hip, flat.hip, optim.hip, ew_bodies.h) against tests/ew_ref.py (numpy
+fp64), through the C ABI, at the sizes and inputs where the rest of the suite does not go: past one grid stride of the flat launches (a),
 all three code paths of the BatchNorm backward apply (b), every thread mapping of the tile reductions (c), pools on
 tied, NaN and -inf windows (d), the optimisers and the non-finite guard element by element (e).
 
@@ -7,7 +7,7 @@ Bars.  Where a kernel selects or copies (pools, masks, skipped elements, fill, l
 EQUAL — compared as bits where a -0.0 or a NaN can occur.  Where it computes, the bar is the a-priori fp32 rounding bound of
 its expression against the fp64 value of the same fp32 inputs, element by element: gamma(k) * (sum of the absolute values of
 the terms), k the rounded operations, stated where each bar is formed (ew_ref.py returns them).  build.py compiles
-elementwise.hip with `-O3 -fno-slp-vectorize` and no fast-math flag; for HIP the compiler's default is correctly rounded fp32
+these units with `-O3 -fno-slp-vectorize` and no fast-math flag; for HIP the compiler's default is correctly rounded fp32
 division and sqrtf (-fhip-fp32-correctly-rounded-divide-sqrt), so neither adds to k; fp contraction (the default) only
 removes roundings.  tests/test_ew_ref_cpu.py shows that torch's own fp32 CPU kernels meet the same bars, so none is
 widened.  No bar comes from a kernel's output.

@@ -1,5 +1,5 @@
 """The `fc` output strategy (`fc2_fwd_kernel` / `fc2_bwd_kernel`, csrc/head.hip) and the PCKh hit test (`pckh_kernel`,
-csrc/elementwise.hip) called directly, against fp64 restatements.
+csrc/pckh.hip) called directly, against fp64 restatements.
 
 fc: `out = hm @ W.T + b` per (image, joint) row, weights at nn.Linear's scale (uniform in +-1/sqrt(hw)), heat-maps from a
 softmax.  Bar: 2e-5 of the largest entry of each fp64 result (the gradient bar of tests/test_head_gpu.py).  `gw` is a

@@ -1,4 +1,4 @@
-"""The PCKh histogram (`pckh_hist_kernel`, csrc/elementwise.hip, through `dsnt_pckh_hist`) and `dsnt.evaluator.PCKhCurve`
+"""The PCKh histogram (`pckh_hist_kernel`, csrc/pckh.hip, through `dsnt_pckh_hist`) and `dsnt.evaluator.PCKhCurve`
 against a numpy fp64 restatement.
 
 The table is integer, so it must equal the restatement exactly: every case first checks on the CPU that no distance lies

@@ -1,5 +1,5 @@
 """Sensitivity of tests/test_elementwise_edges_gpu.py: build libdsnt_hip.so from a scratch copy of csrc/ that carries ONE
-change in elementwise.hip or ew_bodies.h, outside the tree, and print its path.  The module run against it must FAIL:
+change in resample.hip (a, c), optim.hip (e, f), bn.hip (g) or ew_bodies.h (b, d), outside the tree, and print its path.  The module run against it must FAIL:
 
     python3 tools/mutate_elementwise.py a|b|c|d|e|f|g <empty scratch directory>          # build (no GPU needed)
     DSNT_HIP_LIB=<printed path> python3 -m pytest -m gpu tests/test_elementwise_edges_gpu.py
@@ -29,13 +29,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'dsnt-pose2d_amd', 'csrc')
 MUTATIONS = {
-    'a': ('elementwise.hip', 'if (V.x > m.x || V.x != V.x) { m.x = V.x; k.x = P; }', 'if (V.x >= m.x || V.x != V.x) { m.x = V.x; k.x = P; }'),
+    'a': ('resample.hip', 'if (V.x > m.x || V.x != V.x) { m.x = V.x; k.x = P; }', 'if (V.x >= m.x || V.x != V.x) { m.x = V.x; k.x = P; }'),
     'b': ('ew_bodies.h', 'if (V.x > v.x || V.x != V.x) { v.x = V.x; k.x = P; }', 'if (V.x >= v.x || V.x != V.x) { v.x = V.x; k.x = P; }'),
-    'c': ('elementwise.hip', 'if (v.x > m.x || v.x != v.x) { m.x = v.x; k.x = p; }', 'if (v.x >= m.x || v.x != v.x) { m.x = v.x; k.x = p; }'),
+    'c': ('resample.hip', 'if (v.x > m.x || v.x != v.x) { m.x = v.x; k.x = p; }', 'if (v.x >= m.x || v.x != v.x) { m.x = v.x; k.x = p; }'),
     'd': ('ew_bodies.h', 'o1 = bn_apply_one(g1, x1, v, relu);', 'o1 = bn_apply_one(g1, x1, v, 0);'),
-    'e': ('elementwise.hip', '        if (wd != 0.f) gi = fmaf(wd, pi, gi);\n        const float s = alpha * sq[i]', '        const float s = alpha * sq[i]'),
-    'f': ('elementwise.hip', 'momentum * buf[i] + gi', 'momentum * gi + buf[i]'),
-    'g': ('elementwise.hip', 'for (int j = 0; j < rpar; ++j)', 'for (int j = 0; j < rpar - 1; ++j)'),
+    'e': ('optim.hip', '        if (wd != 0.f) gi = fmaf(wd, pi, gi);\n        const float s = alpha * sq[i]', '        const float s = alpha * sq[i]'),
+    'f': ('optim.hip', 'momentum * buf[i] + gi', 'momentum * gi + buf[i]'),
+    'g': ('bn.hip', 'for (int j = 0; j < rpar; ++j)', 'for (int j = 0; j < rpar - 1; ++j)'),
 }
 
 
