@@ -1,10 +1,10 @@
-// dsnt_flip_merge_head (head.hip: entry point and the dsnt strategy; heatmap.hip: the gauss strategy): the flip-merged
+// dsnt_flip_merge_head (head_fwd.hip: entry point and the dsnt strategy; heatmap.hip: the gauss strategy): the flip-merged
 // logits of a paired batch, computed where they are read instead of being materialised.
 //
 // logits [2B][J][h][w], rows B..2B-1 the mirrored inputs.  The merged row of (sample b, joint j) is
 //   m[y][x] = (L[b][j][y][x] + L[B + b][perm[j]][y][w - 1 - x]) / 2
 // in fp32, the reference's `(hm1 + hm2) / 2` of inference.py:41-46 (the division by 2 is exact: the same value as
-// ATen's).  A FlipSrc stands in for the `const float*` a row is read from: Row<> (head.hip) and the arg-max decode
+// ATen's).  A FlipSrc stands in for the `const float*` a row is read from: Row<> (head_row.h) and the arg-max decode
 // (heatmap.hip) take either.
 #pragma once
 #include "common.h"
@@ -54,7 +54,7 @@ __device__ __forceinline__ void flip_backproject(float cx, float cy, const doubl
 
 // ---- per-joint statistics of a heat-map row (dsnt_heatmap_stats, dsnt_flip_merge_head_stats)
 // For one row (sample b, joint j) with the post-activation map p[y][x], h x w, and the DSNT grid X = (2x + 1)/w - 1,
-// Y = (2y + 1)/h - 1 (Grid2, head.hip):
+// Y = (2y + 1)/h - 1 (Grid2, head_row.h):
 //   peak, peak_index   max p and the first index i = y w + x that holds it (decode_row's rule); NaN is never the peak
 //   mass               sum p (1 for softmax; not for the other preactivations at eps, nor for gauss)
 //   mean = (mx, my)    (sum X p, sum Y p): for the dsnt strategy the coordinates, bit for bit

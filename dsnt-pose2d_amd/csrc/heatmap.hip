@@ -5,16 +5,12 @@
 // /root/reference/src/dsnt/model.py:147-156, 247-258.  HBM-bound, one 256-thread workgroup per
 // (image, joint) row of H*W floats; the 7x7 target bump is evaluated in-register, never materialised
 // for the loss.
-#include "common.h"
-#include "flipmerge.h"
-#include <math.h>
+#include "head_row.h"   // HB, check_rows, gauss_k; common.h and flipmerge.h
 
 // The reference's coordinate arithmetic is a chain of separately rounded fp32 tensor ops (add_, mul_, add_);
 // hipcc contracts a*b+c into one FMA by default (and HIP's __fmul_rn / __fadd_rn are plain operators), which
 // moves results by an ulp and can move a rounded pixel.  This file is compiled with -ffp-contract=off
 // (build.py; HIP's default -ffp-contract=fast ignores `#pragma clang fp contract`).
-
-#define HB 256
 
 // Centre of the target bump of a row: util.py:133-146 — pixel = (c + 1) * (W/2) - 0.5 in fp32, three separately
 // rounded operations (no FMA contraction), then Python round() = round-half-even; draw_gaussian (:70-126) with
@@ -236,19 +232,17 @@ int flip_merge_decode_launch(const float* logits, int B, int J, int h, int w, co
 }
 
 static int check_rows_hm(const char* who, int64_t rows, int h, int w, float sigma) {
-    DSNT_REQUIRE(rows > 0 && rows < (1LL << 31), DSNT_ERR_SHAPE, "%s: rows=%lld out of range", who, (long long)rows);
-    DSNT_REQUIRE(h > 0 && w > 0 && (long)h * w < (1L << 24), DSNT_ERR_SHAPE, "%s: bad map size %dx%d", who, h, w);
+    if (int e = check_rows(who, rows, h, w)) return e;
     DSNT_REQUIRE(sigma > 0.f, DSNT_ERR_ARG, "%s: sigma must be positive", who);
     return DSNT_OK;
 }
-static inline float bump_k(float sigma) { return (float)(-0.5 * (1.0 / (double)sigma) * (1.0 / (double)sigma)); }
 
 extern "C" int dsnt_encode_heatmaps(const float* target, float* out, int64_t rows, int h, int w, float sigma,
                                     void* stream) {
     DSNT_REQUIRE(target && out, DSNT_ERR_ARG, "dsnt_encode_heatmaps: null tensor");
     if (int e = check_rows_hm("dsnt_encode_heatmaps", rows, h, w, sigma)) return e;
     DSNT_LAUNCH(encode_heatmaps_kernel, dim3((unsigned)rows), dim3(HB), 0, (hipStream_t)stream, target, out,
-                       h, w, bump_k(sigma));
+                       h, w, gauss_k(sigma));
     DSNT_CHECK_LAUNCH("dsnt_encode_heatmaps");
 }
 
@@ -257,7 +251,7 @@ extern "C" int dsnt_heatmap_mse_fwd(const float* hm, const float* target, float*
     DSNT_REQUIRE(hm && target && per_row, DSNT_ERR_ARG, "dsnt_heatmap_mse_fwd: null tensor");
     if (int e = check_rows_hm("dsnt_heatmap_mse_fwd", rows, h, w, sigma)) return e;
     DSNT_LAUNCH(heatmap_mse_fwd_kernel, dim3((unsigned)rows), dim3(HB), 0, (hipStream_t)stream, hm, target,
-                       per_row, h, w, bump_k(sigma));
+                       per_row, h, w, gauss_k(sigma));
     DSNT_CHECK_LAUNCH("dsnt_heatmap_mse_fwd");
 }
 
@@ -267,7 +261,7 @@ extern "C" int dsnt_heatmap_mse_bwd(const float* hm, const float* target, const 
     if (int e = check_rows_hm("dsnt_heatmap_mse_bwd", rows, h, w, sigma)) return e;
     const float coef = (float)(2.0 / ((double)rows * h * w));
     DSNT_LAUNCH(heatmap_mse_bwd_kernel, dim3((unsigned)rows), dim3(HB), 0, (hipStream_t)stream, hm, target,
-                       gscale, dhm, h, w, bump_k(sigma), coef);
+                       gscale, dhm, h, w, gauss_k(sigma), coef);
     DSNT_CHECK_LAUNCH("dsnt_heatmap_mse_bwd");
 }
 

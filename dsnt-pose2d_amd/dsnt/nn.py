@@ -5,8 +5,8 @@ Every public name, positional/keyword argument and default of
 `make_gauss`, `kl_reg_loss`, `js_reg_loss`, `mse_reg_loss`, `variance_reg_loss`, ...), so
 `train.py` / `infer.py` style callers import it unchanged.  Underneath, each op is a
 `torch.autograd.Function` that enqueues hand-written HIP kernels from libdsnt_hip.so on the
-current stream (csrc/head.hip).  Tensors must be fp32 and resident on the HIP device: there is
-no CPU fallback, by design.
+current stream (csrc/head_ops.hip, head_loss.hip, head_fwd.hip).  Tensors must be fp32 and
+resident on the HIP device: there is no CPU fallback, by design.
 """
 import math
 

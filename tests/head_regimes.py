@@ -29,7 +29,7 @@ from dsnt_oracle import nn as onn, model as omodel
 
 REGIMES = ('diffuse', 'peaked', 'edge', 'onehot', 'bimodal', 'offset', 'straddle')
 REGS = ('none', 'js', 'kl', 'mse', 'var')
-# shape -> why it is in the matrix (the dispatch of dsnt_head_fwd / dsnt_head_loss_grad in csrc/head.hip)
+# shape -> why it is in the matrix (the dispatch of dsnt_head_fwd / dsnt_head_loss_grad in csrc/head_fwd.hip, head_loss.hip)
 SHAPES = ((64, 64), (64, 48), (28, 28), (16, 16),   # VEC == 4 and w % 4 == 0: the fast JS form
           (14, 14),                                   # hw % 4 == 0, w % 4 != 0: VEC == 4 with the per-slot JS path
           (7, 7), (5, 5),                             # VEC == 1
@@ -227,7 +227,7 @@ def census_applies(h, w):
 
 
 def census(p32, target, h, w, sigma):
-    """Which JS branch each 256-pixel granule of each row takes in head_loss_grad_kernel (csrc/head.hip, the block
+    """Which JS branch each 256-pixel granule of each row takes in head_loss_grad_kernel (csrc/head_loss.hip, the block
     `if (VEC == 4 && (w & 3) == 0)` under `if (kind == 0 && tab)`).
 
     Mirrors, in fp32 numpy:

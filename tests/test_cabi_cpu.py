@@ -122,6 +122,98 @@ def test_argument_validation_without_gpu():
     assert lib.dsnt_conv_fwd_bm(C.byref(g)) in (32, 128)
 
 
+def _head_refusals():
+    """(entry point, arguments without the stream, return code, dsnt_last_error()) of calls the DSNT head's wrappers refuse
+    before they touch a device; X is a non-null pointer that is never followed."""
+    X, N, big = C.c_void_p(4096), None, 4096            # big x big = 2^24 pixels
+    perm3 = C.cast((C.c_int * 3)(0, 2, 1), C.c_void_p)
+    twice = C.cast((C.c_int * 3)(0, 0, 1), C.c_void_p)
+    perm33 = C.cast((C.c_int * 33)(*range(33)), C.c_void_p)
+    rows = []
+
+    def add(name, args, rc, text):
+        rows.append((name, args, rc, (name + ': ' + text).encode()))
+
+    def shapes(name, ptrs, tail=(), first=False):
+        """rows = 0 and h * w = 2^24 through check_rows; hw-only entry points (first=True) see the map as 1 x hw"""
+        hw_ok, hw_big = ((64,), (1 << 24,)) if first else ((8, 8), (big, big))
+        add(name, ptrs + (0,) + hw_ok + tail, 1, 'rows=0 out of range')
+        add(name, ptrs + (4,) + hw_big + tail, 1, 'bad map size %dx%d' % ((1, 1 << 24) if first else (big, big)))
+
+    add('dsnt_preact_fwd', (N, X, 4, 64, 0, 0., 1e-6), 3, 'null tensor')
+    add('dsnt_preact_fwd', (X, X, 4, 64, 5, 0., 1e-6), 3, 'unknown mode 5')
+    shapes('dsnt_preact_fwd', (X, X), (0, 0., 1e-6), first=True)
+    add('dsnt_preact_bwd', (X, N, X, X, 4, 64, 0, 0., 1e-6), 3, 'null tensor')
+    add('dsnt_preact_bwd', (N, X, X, X, 4, 64, 2, 0., 1e-6), 3, 'null tensor')       # modes 2..4 read x
+    add('dsnt_preact_bwd', (X, X, X, X, 4, 64, 5, 0., 1e-6), 3, 'unknown mode 5')
+    shapes('dsnt_preact_bwd', (N, X, X, X), (0, 0., 1e-6), first=True)
+    for name, n in (('dsnt_expect_fwd', 2), ('dsnt_expect_bwd', 2), ('dsnt_head_fwd', 3)):
+        add(name, (X,) * (n - 1) + (N, 4, 8, 8), 3, 'null tensor')
+        shapes(name, (X,) * n)
+    add('dsnt_heatmap_stats', (X, 4, 8, 8, X, N), 3, 'null tensor')
+    add('dsnt_heatmap_stats', (X, 0, 8, 8, X, X), 1, 'rows=0 out of range')
+    add('dsnt_heatmap_stats', (X, 4, big, big, X, X), 1, 'bad map size 4096x4096')
+    for name, n in (('dsnt_make_gauss', 2), ('dsnt_make_gauss_bwd', 3)):
+        add(name, (N,) + (X,) * (n - 1) + (4, 8, 8, 1.), 3, 'null tensor')
+        add(name, (X,) * n + (4, 8, 8, 0.), 3, 'sigma must be positive')
+        shapes(name, (X,) * n, (1.,))
+    for name, n in (('dsnt_reg_fwd', 3), ('dsnt_reg_bwd', 4), ('dsnt_reg_bwd_mu', 4)):
+        add(name, (X, N) + (X,) * (n - 2) + (4, 8, 8, 1., 0), 3, 'null tensor')          # kinds 0..2 read the target
+        shapes(name, (X,) * n, (1., 0))
+    add('dsnt_reg_fwd', (X, X, X, 4, 8, 8, 1., 4), 3, 'unknown kind 4')
+    add('dsnt_reg_bwd', (X, X, X, X, 4, 8, 8, 1., 4), 3, 'unknown kind 4')
+    add('dsnt_reg_bwd_mu', (X, X, X, X, 4, 8, 8, 1., 3), 3, 'kind 3 has no target Gaussian')
+    for name, n, tail in (('dsnt_head_loss_rows', 5, (1., 0)), ('dsnt_head_bwd', 7, (1., 0)),
+                          ('dsnt_head_loss_grad', 8, (1., 0, 1.))):
+        add(name, (N,) + (X,) * (n - 1) + (4, 8, 8) + tail, 3, 'null tensor')
+        add(name, (X,) * n + (4, 8, 8, 1., 4) + tail[2:], 3, 'unknown regulariser 4')
+        shapes(name, (X,) * n, tail)
+    add('dsnt_head_loss_grad', (X,) * 8 + (4, 1, 4097, 1., 0, 1.), 1,
+        'heat-maps of up to 4096 pixels (got 1x4097); use dsnt_head_loss_rows + dsnt_head_bwd for larger ones')
+    for name, ptrs, tail in (('dsnt_euclid_fwd', 3, (2,)), ('dsnt_euclid_bwd', 5, (2,)), ('dsnt_masked_avg_fwd', 3, ()),
+                             ('dsnt_masked_avg_bwd', 4, ()), ('dsnt_fc2_fwd', 4, (64,)), ('dsnt_fc2_bwd', 6, (64,)),
+                             ('dsnt_mask_denom', 2, ())):
+        add(name, (X,) * ptrs + (0,) + tail, 3, 'bad argument')                          # n = 0 / rows = 0
+    add('dsnt_euclid_fwd', (X, X, N, 4, 2), 3, 'bad argument')
+    add('dsnt_euclid_bwd', (X, X, X, X, N, 4, 2), 3, 'bad argument')
+    add('dsnt_masked_avg_fwd', (N, X, X, 4), 3, 'bad argument')
+    add('dsnt_masked_avg_bwd', (N, X, X, X, 4), 3, 'bad argument')
+    add('dsnt_fc2_fwd', (X, N, X, X, 4, 64), 3, 'bad argument')
+    add('dsnt_fc2_bwd', (X, X, X, X, N, X, 4, 64), 3, 'bad argument')
+    add('dsnt_mask_denom', (X, N, 4), 3, 'bad argument')
+    add('dsnt_head_loss_reduce', (X, X, X, N, 1., X, X, 4), 3, 'bad argument')
+    add('dsnt_head_loss_reduce', (X, X, X, X, 1., X, X, 0), 3, 'bad argument')
+    add('dsnt_scale_by_scalar', (X, N, 4), 3, 'null pointer or n <= 0')
+    add('dsnt_scale_by_scalar', (X, X, 0), 3, 'null pointer or n <= 0')
+    for name, extra in (('dsnt_flip_merge_head', ()), ('dsnt_flip_merge_head_stats', (X, X, X))):
+        def flip(B=2, J=3, h=8, w=8, perm=perm3, strategy=0, preact=0, logits=X, extra=extra):
+            return (logits, B, J, h, w, perm, strategy, preact, 0., 1e-6, X, X, X, X, X) + extra
+        add(name, flip(logits=N), 3, 'null pointer')
+        add(name, flip(strategy=2), 3, 'unknown strategy 2')
+        add(name, flip(preact=5), 3, 'unknown preact mode 5')
+        add(name, flip(J=33, perm=perm33), 1, 'J=33 outside 1..32')
+        add(name, flip(B=0), 1, 'B=0 out of range')
+        add(name, flip(h=big, w=big), 1, 'bad map size 4096x4096')
+        add(name, flip(perm=twice), 3, 'perm is not a permutation of 0..2 (perm[1] = 0)')
+    add('dsnt_flip_merge_head_stats', flip(extra=(X, N, X)), 3, 'null pointer')
+    return rows
+
+
+def test_head_wrappers_refuse_bad_arguments_without_gpu():
+    """Return code and exact dsnt_last_error() of every DSNT head entry point (head_ops.hip, head_loss.hip, head_fwd.hip) on
+    arguments it refuses: null tensors, rows = 0, h * w = 2^24, unknown modes, kinds, regularisers and strategies,
+    sigma = 0, rows too long for the fused loss, J = 33 and a non-permutation.  Nothing here reaches a device."""
+    from dsnt import _lib
+    lib = _lib.load()
+    table = _head_refusals()
+    moved = [n for n in _lib.SIGNATURES if re.match(
+        r'dsnt_(preact|expect|make_gauss|euclid|masked_avg|fc2|reg|head|mask_denom|scale_by_scalar|flip_merge_head|heatmap_stats)', n)]
+    assert len(moved) == 25 and set(moved) == {row[0] for row in table}
+    for name, args, rc, text in table:
+        got = getattr(lib, name)(*args, None)
+        assert (got, lib.dsnt_last_error()) == (rc, text), (name, args)
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     import dsnt.nn as dn

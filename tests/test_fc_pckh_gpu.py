@@ -1,4 +1,4 @@
-"""The `fc` output strategy (`fc2_fwd_kernel` / `fc2_bwd_kernel`, csrc/head.hip) and the PCKh hit test (`pckh_kernel`,
+"""The `fc` output strategy (`fc2_fwd_kernel` / `fc2_bwd_kernel`, csrc/head_ops.hip) and the PCKh hit test (`pckh_kernel`,
 csrc/pckh.hip) called directly, against fp64 restatements.
 
 fc: `out = hm @ W.T + b` per (image, joint) row, weights at nn.Linear's scale (uniform in +-1/sqrt(hw)), heat-maps from a

@@ -20,7 +20,7 @@ the edge regime on the two wide maps, which sets K_ref; each cell fp32 oracle / 
   Value errors stay below 0.1 of their bounds everywhere (coords, heat-maps, dist, reg_row, loss).  On the wide maps
   dist is down to 1.3e-3.  4096 rows: worst |row sum| = 73.5 x 2^-24 S_r, 0.033 of the tighter bound of that test.
 
-SENSITIVITY (a scratch copy of head.hip with one change, built into a library outside the tree, one run each through
+SENSITIVITY (a scratch copy of head_loss.hip with one change, built into a library outside the tree, one run each through
 tools/mutate_head.py; nothing of it is committed):
   (a) `far` 1e-30f -> 1e-12f: NOT caught, 167 passed, worst ratio / bound 0.29 as without the change.  It cannot be
       caught in fp32: where the shortcut now fires wrongly, d reg / d p is off by (1/2) ln(1 + q / p) and

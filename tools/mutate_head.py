@@ -1,5 +1,6 @@
-"""Sensitivity of tests/test_head_regimes_gpu.py: build libdsnt_hip.so from a scratch copy of csrc/ whose head.hip carries ONE
-arithmetic change, outside the tree, and print its path.  The regime tests run against it must FAIL:
+"""Sensitivity of tests/test_head_regimes_gpu.py: build libdsnt_hip.so from a scratch copy of csrc/ whose head_loss.hip
+carries ONE arithmetic change in head_loss_grad_kernel, outside the tree, and print its path.  The regime tests run
+against it must FAIL:
 
     python3 tools/mutate_head.py a|b|c <empty scratch directory>          # build (no GPU needed)
     DSNT_HIP_LIB=<printed path> python3 -m pytest -m gpu tests/test_head_regimes_gpu.py
@@ -32,11 +33,11 @@ def main(which, out):
     inc = os.path.join(out, 'include')
     src = os.path.join(out, 'dsnt-pose2d_amd', 'csrc')
     shutil.copytree(os.path.join(ROOT, 'include'), inc)
-    # csrc/build/ (the objects of the in-tree build) is copied with its file times, so build.py compiles head.hip alone;
+    # csrc/build/ (the objects of the in-tree build) is copied with its file times, so build.py compiles head_loss.hip alone;
     # only the build_<name>/ directories of experiment libraries and the libraries themselves stay behind
     shutil.copytree(CSRC, src, ignore=shutil.ignore_patterns('build_*', '*.so'))
     shutil.copy(os.path.join(ROOT, 'dsnt-pose2d_amd', 'build.py'), os.path.join(out, 'dsnt-pose2d_amd', 'build.py'))
-    path = os.path.join(src, 'head.hip')
+    path = os.path.join(src, 'head_loss.hip')
     text = open(path).read()
     assert text.count(old) == 1, 'mutation %s: pattern found %d times' % (which, text.count(old))
     open(path, 'w').write(text.replace(old, new))
