@@ -1,10 +1,11 @@
-// The PCKh evaluators (evaluator.py:66, train.py:243-258): the hit test at one threshold and the one-launch histogram
-// behind the PCKh curve, both on one fp64 distance expression.
+// The PCKh evaluators (evaluator.py:66, train.py:243-258): the hit test at one threshold, the one-launch histogram
+// behind the PCKh curve and the misprediction field of bin/investigate.py, all on one fp64 distance expression.
 #include "common.h"
 
 // ---------------------------------------------------------------- PCKh hits
 // Distance of joint i (of image n) between the back-projected prediction and target, in head lengths: one expression for
-// pckh_kernel and pckh_hist_kernel, so that the curve at a threshold holds the very hits of the single-threshold kernel.
+// pckh_kernel, pckh_hist_kernel and error_field_kernel, so that the curve at a threshold holds the very hits of the
+// single-threshold kernel and the field's misses are exactly its non-hits.
 __device__ __forceinline__ double pckh_distance(const float* __restrict__ pred, const float* __restrict__ target,
                                                 const double* __restrict__ m, const double* __restrict__ b,
                                                 const double* __restrict__ head, long i, long n) {
@@ -106,4 +107,151 @@ extern "C" int dsnt_pckh_hist(const float* pred, const float* target, const doub
     DSNT_LAUNCH(pckh_hist_kernel, dim3(grid), dim3(DSNT_PCKH_HIST_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
                 mask, head, thr, T, table, dist, B, J, use_lds);
     DSNT_CHECK_LAUNCH("dsnt_pckh_hist");
+}
+
+// Misprediction field (bin/investigate.py:62-99; include/dsnt_hip.h: dsnt_error_field): per joint, a bins x bins grid over
+// the target's location holding how many joints there were, how many missed, and the summed offset of the misses.  The
+// sums are fp64 adds, whose result depends on their order, so there are no atomics: workgroup j owns joint j, and lane l
+// owns the cells l, l + BLOCK, ... of that joint in all five planes.  The samples are walked in chunks of BLOCK: lane i
+// writes the record of sample n0 + i to LDS, then every wave walks the records in ascending n and each lane takes those
+// of its own cells, which is the sequential loop over n bit for bit, however the set is cut into calls.
+static_assert(DSNT_ERROR_FIELD_BLOCK % 64 == 0 && DSNT_ERROR_FIELD_BLOCK >= 64, "whole waves");
+constexpr int EF_CELLS = DSNT_ERROR_FIELD_MAX_BINS * DSNT_ERROR_FIELD_MAX_BINS;
+constexpr int EF_OWN = (EF_CELLS + DSNT_ERROR_FIELD_BLOCK - 1) / DSNT_ERROR_FIELD_BLOCK;      // cells per lane at most
+static_assert(EF_CELLS <= (1 << 16), "a record holds its cell in 16 bits");
+constexpr int EF_MISS = 1 << 16, EF_FINITE = 1 << 17;                                         // record: cell | flags, or -1
+struct error_field_edges { double e[DSNT_ERROR_FIELD_MAX_BINS + 1]; };                        // padded with +inf behind bins
+static_assert(DSNT_ERROR_FIELD_MAX_BINS % 8 == 0, "error_field_cell reads the edges eight at a time");
+// Cell [by][bx] of a target inside the frame.  Along an axis: the number of edges e[1..bins] that are <= t, capped at
+// bins - 1, which is e[k] <= t < e[k + 1] with the last edge closed.  t is finite and the padding is +inf, so the padding
+// never counts; the index is uniform, so eight edges are one scalar load of the kernel argument, as in pckh_hist_kernel.
+__device__ __forceinline__ int error_field_cell(const error_field_edges& edges, double tx, double ty, int bins) {
+    int kx = 0, ky = 0;
+    for (int q = 0; q < bins; q += 8) {
+#pragma unroll
+        for (int u = 1; u <= 8; ++u) {
+            const double e = edges.e[q + u];
+            kx += (e <= tx) ? 1 : 0;
+            ky += (e <= ty) ? 1 : 0;
+        }
+    }
+    return min(ky, bins - 1) * bins + min(kx, bins - 1);
+}
+__global__ __launch_bounds__(DSNT_ERROR_FIELD_BLOCK)
+void error_field_kernel(const float* __restrict__ pred, const float* __restrict__ target, const double* __restrict__ m,
+                        const double* __restrict__ b, const float* __restrict__ mask, const double* __restrict__ head,
+                        float thr, const error_field_edges edges, double hi, int bins, long long* counts, double* sums,
+                        int B, int J) {
+    __shared__ int rec[DSNT_ERROR_FIELD_BLOCK];
+    __shared__ double rdx[DSNT_ERROR_FIELD_BLOCK], rdy[DSNT_ERROR_FIELD_BLOCK];
+    constexpr int BLOCK = DSNT_ERROR_FIELD_BLOCK;
+    const int j = blockIdx.x, tid = threadIdx.x, cells = bins * bins;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const size_t plane = (size_t)J * cells;                    // one plane of either table
+    const size_t base = (size_t)j * cells;
+    const double lo = edges.e[0];
+    unsigned total[EF_OWN], miss[EF_OWN], finite[EF_OWN];      // this call's counts: fewer than 2^31 samples
+    double sx[EF_OWN], sy[EF_OWN];                             // the table's own value, then + dx in ascending n
+#pragma unroll
+    for (int q = 0; q < EF_OWN; ++q) {
+        const int c = tid + q * BLOCK;
+        total[q] = miss[q] = finite[q] = 0u;
+        sx[q] = c < cells ? sums[base + c] : 0.0;
+        sy[q] = c < cells ? sums[plane + base + c] : 0.0;
+    }
+    for (long n0 = 0; n0 < B; n0 += BLOCK) {
+        const long n = n0 + tid;
+        int r = -1;                                            // records past B read as "no cell"
+        double dx = 0.0, dy = 0.0;
+        if (n < B) {
+            const long i = n * J + j;
+            const double tx = target[2 * i], ty = target[2 * i + 1];
+            // mask == 1 and the target inside the closed frame (investigate.py:73-74); a NaN target fails the comparison
+            if (mask[i] == 1.f && lo <= tx && tx <= hi && lo <= ty && ty <= hi) {
+                r = error_field_cell(edges, tx, ty, bins);
+                const double d = pckh_distance(pred, target, m, b, head, i, n);
+                if (!(d <= (double)thr)) {                     // NaN and inf distances are misses, as in dsnt_pckh
+                    r |= EF_MISS;
+                    dx = (double)pred[2 * i] - tx;
+                    dy = (double)pred[2 * i + 1] - ty;
+                    if (dx - dx == 0.0 && dy - dy == 0.0) r |= EF_FINITE;      // both finite
+                }
+            }
+        }
+        rec[tid] = r;
+        rdx[tid] = dx;
+        rdy[tid] = dy;
+        __syncthreads();
+        if (wave * 64 < cells) {                               // (a wave whose lanes own no cell has nothing to scan for)
+            const int len = B - n0 < BLOCK ? (int)(B - n0) : BLOCK;
+            for (int s0 = 0; s0 < len; s0 += 64) {
+                // 64 records, one per lane, and a ballot of those whose cell belongs to a lane of this wave; its bits are
+                // walked in ascending order, which is ascending n.  A record comes out of its lane as a scalar, so the
+                // branches on it are taken by the whole wave and only the owner's compare is per lane.
+                const int rv = rec[s0 + lane];
+                const double rx = rdx[s0 + lane], ry = rdy[s0 + lane];
+                unsigned long long todo = __ballot(rv >= 0 && (((rv & 0xffff) % BLOCK) >> 6) == wave);
+                while (todo) {
+                    const int k = __ffsll((long long)todo) - 1;
+                    todo &= todo - 1;
+                    const int v = __builtin_amdgcn_readlane(rv, k);
+                    const int c = v & 0xffff, slot = c / BLOCK;
+                    const bool mine = tid == c % BLOCK;
+                    double ax = 0.0, ay = 0.0;
+                    if (v & EF_FINITE) {
+                        ax = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(rx), k),
+                                              __builtin_amdgcn_readlane(__double2loint(rx), k));
+                        ay = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ry), k),
+                                              __builtin_amdgcn_readlane(__double2loint(ry), k));
+                    }
+#pragma unroll
+                    for (int q = 0; q < EF_OWN; ++q) {
+                        if (slot != q) continue;
+                        total[q] += mine ? 1u : 0u;
+                        miss[q] += (mine && (v & EF_MISS)) ? 1u : 0u;
+                        if (v & EF_FINITE) {
+                            finite[q] += mine ? 1u : 0u;
+                            if (mine) {
+                                sx[q] += ax;
+                                sy[q] += ay;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < EF_OWN; ++q) {
+        const int c = tid + q * BLOCK;
+        if (c < cells) {
+            counts[base + c] += (long long)total[q];
+            counts[plane + base + c] += (long long)miss[q];
+            counts[2 * plane + base + c] += (long long)finite[q];
+            sums[base + c] = sx[q];
+            sums[plane + base + c] = sy[q];
+        }
+    }
+}
+extern "C" int dsnt_error_field(const float* pred, const float* target, const double* m, const double* b,
+                                const float* mask, const double* head, float threshold, const double* edges, int bins,
+                                int64_t* counts, double* sums, int B, int J, void* stream) {
+    DSNT_REQUIRE(pred && target && m && b && mask && head && edges && counts && sums && B > 0 && J > 0,
+                 DSNT_ERR_ARG, "dsnt_error_field: bad argument");
+    DSNT_REQUIRE(bins >= 1 && bins <= DSNT_ERROR_FIELD_MAX_BINS, DSNT_ERR_ARG, "dsnt_error_field: bins=%d outside 1..%d",
+                 bins, DSNT_ERROR_FIELD_MAX_BINS);
+    error_field_edges e;
+    for (int k = 0; k <= DSNT_ERROR_FIELD_MAX_BINS; ++k) e.e[k] = (double)INFINITY;
+    for (int k = 0; k <= bins; ++k) {
+        const double t = edges[k];
+        DSNT_REQUIRE(t - t == 0.0, DSNT_ERR_ARG, "dsnt_error_field: edge %d is not finite", k);
+        DSNT_REQUIRE(k == 0 || t > edges[k - 1], DSNT_ERR_ARG,
+                     "dsnt_error_field: edges must be strictly ascending (index %d)", k);
+        e.e[k] = t;
+    }
+    const double hi = e.e[bins];
+    DSNT_LAUNCH(error_field_kernel, dim3(J), dim3(DSNT_ERROR_FIELD_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
+                mask, head, threshold, e, hi, bins, (long long*)counts, sums, B, J);
+    DSNT_CHECK_LAUNCH("dsnt_error_field");
 }

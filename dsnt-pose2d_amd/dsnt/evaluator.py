@@ -9,6 +9,9 @@ Meter values are accumulated as device tensors and only read when `.value()` is 
 `PCKhCurve` answers every threshold at once: one launch per batch adds into a device-resident histogram of the
 normalised distance per joint (`dsnt_pckh_hist`), and PCKh at each threshold, for each joint and group,
 is a cumulative sum of that table taken when the user asks.
+
+`ErrorField` is the reference's `bin/investigate.py` on the device: where in the frame joints are missed and which way
+(`dsnt_error_field`), again one launch per batch into device-resident tables.
 """
 import ctypes
 
@@ -293,3 +296,164 @@ class PCKhCurve:
             counts = counts.cuda()
         dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
         self._take(counts)
+
+
+class ErrorField:
+    """Where in the frame joints miss PCKh@`threshold`, and in which direction (reference `bin/investigate.py`).
+
+    The normalised ground-truth location of every valid joint inside [-1, 1]^2 falls into one cell of a `bins` x `bins`
+    grid (cells `[by, bx]`; `e_k <= t < e_{k+1}`, the last edge closed, as `scipy.stats.binned_statistic_dd` bins).  Per
+    joint and cell the tables hold how many joints there were, how many missed (exactly the joints `PCKhEvaluator` gives
+    no hit), how many of the misses had a finite offset, and the fp64 sums of those offsets (prediction - truth,
+    normalised coordinates).  `name` below is a joint name, a group name or a joint index; groups sum their joints in
+    ascending index.
+
+    One owner per cell adds a batch's samples in ascending order, so tables fed by `add_normalized` alone are
+    bit-identical however the set was cut into batches.  `merge` and `all_reduce` add fp64 sums on the host, in the
+    order in which they are called: the last bits of `mean_offset` then depend on that order (the counts never do)."""
+
+    JOINT_NAMES = PCKhEvaluator.JOINT_NAMES
+    JOINT_GROUPS = PCKhEvaluator.JOINT_GROUPS
+    MAX_BINS = 32                         # DSNT_ERROR_FIELD_MAX_BINS
+
+    def __init__(self, bins=8, threshold=0.5, n_joints=16, joint_names=None, joint_groups=None):
+        self.bins, self.n_joints, self.threshold = int(bins), int(n_joints), float(threshold)
+        if not 1 <= self.bins <= self.MAX_BINS:
+            raise ValueError('between 1 and %d bins, got %d' % (self.MAX_BINS, self.bins))
+        if self.n_joints < 1:
+            raise ValueError('n_joints must be positive')
+        if joint_names is None and self.n_joints == len(self.JOINT_NAMES):
+            joint_names = self.JOINT_NAMES
+            if joint_groups is None:
+                joint_groups = self.JOINT_GROUPS
+        self.joint_names = list(joint_names) if joint_names is not None else []
+        if self.joint_names and len(self.joint_names) != self.n_joints:
+            raise ValueError('%d joint names for %d joints' % (len(self.joint_names), self.n_joints))
+        groups = {g: sorted(self.joint_names.index(n) for n in names) for g, names in (joint_groups or {}).items()}
+        groups.setdefault('all', list(range(self.n_joints)))
+        self.groups = groups
+        self.edges = np.linspace(-1, 1, self.bins + 1)
+        self.centres = 0.5 * self.edges[1:] + 0.5 * self.edges[:-1]
+        self._edges_arg = (ctypes.c_double * (self.bins + 1))(*self.edges)    # host array, passed by value to the kernel
+        shape = (self.n_joints, self.bins, self.bins)
+        self._tables = {}                 # device -> (int64 [3, J, bins, bins], f64 [2, J, bins, bins]), the kernel adds
+        self._host = (torch.zeros((3,) + shape, dtype=torch.int64),           # merged, loaded and reduced state
+                      torch.zeros((2,) + shape, dtype=torch.float64))
+
+    # ------------------------------------------------------------------ adding batches
+    def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b):
+        """Add a batch given in normalised coords (back-projected in fp64 as in `PCKhEvaluator.add_normalized` for the
+        hit test; binned and subtracted as given): one kernel, no reduction and no host synchronisation."""
+        B, J = norm_pred.shape[0], norm_pred.shape[1]
+        if J != self.n_joints:
+            raise ValueError('%d joints, the tables have %d' % (J, self.n_joints))
+        dev = norm_pred.device
+        pred = norm_pred.detach().to(torch.float32).contiguous()
+        target = norm_target.detach().to(device=dev, dtype=torch.float32).contiguous()
+        m = transform_m.to(device=dev, dtype=torch.float64).contiguous()
+        b = transform_b.to(device=dev, dtype=torch.float64).reshape(B, 2).contiguous()
+        mask = joint_mask.to(device=dev, dtype=torch.float32).contiguous()
+        head = head_lengths.to(device=dev, dtype=torch.float64).contiguous()
+        tables = self._tables.get(dev)
+        if tables is None:
+            tables = self._tables[dev] = tuple(torch.zeros_like(t, device=dev) for t in self._host)
+        call('dsnt_error_field', ptr(pred), ptr(target), ptr(m), ptr(b), ptr(mask), ptr(head), self.threshold,
+             self._edges_arg, self.bins, ptr(tables[0]), ptr(tables[1]), B, J)
+
+    def reset(self):
+        for tables in list(self._tables.values()) + [self._host]:
+            for t in tables:
+                t.zero_()
+
+    # ------------------------------------------------------------------ reading results
+    def tables(self):
+        """(counts int64 [3, J, bins, bins]: total, miss, miss with a finite offset; sums f64 [2, J, bins, bins]: of dx
+        and of dy) on the host."""
+        counts, sums = self._host[0].clone(), self._host[1].clone()
+        for c, s in self._tables.values():
+            counts += c.cpu()
+            sums += s.cpu()
+        return counts, sums
+
+    _rows = PCKhCurve._rows
+
+    def _plane(self, table, name):
+        """One plane [J, bins, bins] summed over the joints of `name`, in ascending index."""
+        rows = self._rows(name)
+        out = table[rows[0]].clone()
+        for j in rows[1:]:
+            out += table[j]
+        return out.numpy()
+
+    def totals(self, name='all'):
+        """Valid joints whose target lay in each cell, int64 [bins, bins]."""
+        return self._plane(self.tables()[0][0], name)
+
+    def misses(self, name='all'):
+        """Those of them that missed, int64 [bins, bins]."""
+        return self._plane(self.tables()[0][1], name)
+
+    def miss_rate(self, name='all'):
+        """misses / totals, f64 [bins, bins]; 0 where there were no joints."""
+        counts = self.tables()[0]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.nan_to_num(self._plane(counts[1], name) / self._plane(counts[0], name))
+
+    def mean_offset(self, name='all'):
+        """Mean (dx, dy) of the misses of each cell, f64 [bins, bins, 2]; NaN where no miss had a finite offset."""
+        counts, sums = self.tables()
+        n = self._plane(counts[2], name)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.stack((self._plane(sums[0], name) / n, self._plane(sums[1], name) / n), axis=-1)
+
+    def quiver(self, name='all'):
+        """`(X, Y, U, V, C)` for `ax.quiver`: cell centres, mean offsets and miss rates as flat arrays, sorted by
+        ascending miss rate so that the worst cells are drawn last."""
+        X, Y = np.meshgrid(self.centres, self.centres)
+        C, field = self.miss_rate(name), self.mean_offset(name)
+        at = np.unravel_index(np.argsort(C.flatten()), C.shape)
+        return X[at], Y[at], field[..., 0][at], field[..., 1][at], C[at]
+
+    # ------------------------------------------------------------------ combining and saving
+    def _take(self, counts, sums):
+        """Make the two host tables the whole state."""
+        for tables in self._tables.values():
+            for t in tables:
+                t.zero_()
+        self._host = (counts.to(device='cpu', dtype=torch.int64).clone(), sums.to(device='cpu', dtype=torch.float64).clone())
+
+    def merge(self, other):
+        """Add `other`'s tables to this one's (fp64 sums added on the host: see the class docstring)."""
+        if (other.n_joints, other.bins, other.threshold) != (self.n_joints, self.bins, self.threshold):
+            raise ValueError('merge needs the same joints, bins and threshold')
+        counts, sums = other.tables()
+        self._host[0].add_(counts)
+        self._host[1].add_(sums)
+
+    def state_dict(self):
+        counts, sums = self.tables()
+        return {'bins': self.bins, 'threshold': self.threshold, 'counts': counts, 'sums': sums}
+
+    def load_state_dict(self, state):
+        counts, sums = state['counts'], state['sums']
+        shape = (self.n_joints, self.bins, self.bins)
+        if int(state['bins']) != self.bins or float(state['threshold']) != self.threshold:
+            raise ValueError('state of %d bins at threshold %g, this field has %d at %g'
+                             % (state['bins'], state['threshold'], self.bins, self.threshold))
+        if tuple(counts.shape) != (3,) + shape or tuple(sums.shape) != (2,) + shape:
+            raise ValueError('tables of shape %s and %s for %d joints and %d bins'
+                             % (tuple(counts.shape), tuple(sums.shape), self.n_joints, self.bins))
+        self._take(counts, sums)
+
+    def all_reduce(self, group=None):
+        """Sum the tables over the ranks of a `torch.distributed` group; nothing to do in a single process.  The fp64
+        sums are reduced in the backend's order (see the class docstring)."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        counts, sums = self.tables()
+        if dist.get_backend(group) == 'nccl':
+            counts, sums = counts.cuda(), sums.cuda()
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+        self._take(counts, sums)

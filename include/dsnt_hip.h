@@ -761,6 +761,30 @@ int dsnt_pckh(const float* pred, const float* target, const double* m, const dou
 int dsnt_pckh_hist(const float* pred, const float* target, const double* m, const double* b,
                    const float* mask, const double* head, const double* thresholds, int T,
                    unsigned long long* table, double* dist, int B, int J, void* stream);
+/* bin/investigate.py:62-99, the misprediction field: one launch ADDS a batch to a bins x bins grid per joint over the
+ * normalised location of the TARGET, holding how many joints lay in each cell, how many of them missed, and the summed
+ * offset of the misses.  pred, target, m, b, mask, head and threshold are dsnt_pckh's, d is its distance (same fp64
+ * expression), and a joint is a miss here exactly when dsnt_pckh gives it no hit: !(d <= threshold), so a NaN or inf d
+ * (zero head length, non-finite prediction) is a miss.
+ * A joint counts only if mask == 1 and edges[0] <= tx <= edges[bins] and likewise ty (tx, ty: the fp32 target widened to
+ * fp64; a NaN target fails the comparison).  Its cell along an axis is the number of edges[1..bins] that are <= t, capped
+ * at bins - 1: e_k <= t < e_{k+1} with the last edge closed, which is scipy.stats.binned_statistic_dd(range=...).  Then
+ * total[j][cy][cx] += 1; on a miss, miss += 1 and, with dx = (double)px - tx and dy likewise, if both are finite:
+ * miss_finite += 1, sum_x += dx, sum_y += dy (a non-finite prediction is counted and kept out of the sums).
+ * edges: HOST double[bins + 1], 1 <= bins <= DSNT_ERROR_FIELD_MAX_BINS, finite and strictly ascending, the same for x
+ * and y, passed by value to the kernel (DSNT_ERR_ARG otherwise, nothing launched).  counts: device i64
+ * [3][J][bins][bins], planes total, miss, miss_finite, cells [by][bx]; sums: device f64 [2][J][bins][bins], planes sum
+ * of dx and of dy.  The kernel only adds to both; the caller zeroes.
+ * No atomics: the grid is J workgroups of DSNT_ERROR_FIELD_BLOCK threads, workgroup j owns joint j and lane l of it owns
+ * the cells l, l + DSNT_ERROR_FIELD_BLOCK, ...; the lane loads the sums' current values, adds its samples in ascending n
+ * and stores.  The tables are therefore bit-identical to a sequential loop over n, and the same whether a set arrives as
+ * one batch or as several.  dsnt_version() >= 124. */
+#define DSNT_ERROR_FIELD_MAX_BINS 32
+#define DSNT_ERROR_FIELD_BLOCK 256
+int dsnt_error_field(const float* pred, const float* target, const double* m, const double* b,
+                     const float* mask, const double* head, float threshold,
+                     const double* edges, int bins, int64_t* counts, double* sums,
+                     int B, int J, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation
  * data.py:118-226 (MPIIDataset.__getitem__, use_aug) batched on the device; semantics in csrc/augment.hip.
