@@ -210,7 +210,9 @@ __global__ void __launch_bounds__(AUG_NT) augment_kernel(const uint8_t* __restri
             for (int ch = 0; ch < 3; ++ch) gain[ch] = gain_p[3 * b + ch];
         }
         const double cd = (double)R * (double)scale;
-        const int c = cd >= 1.0 && cd <= 8.0 * R ? (int)cd : (cd > 1.0 ? 8 * R : 1);    // (the binding refuses these)
+        // scale is a device value the binding cannot check without a host sync, so the clamp is the contract: R * scale
+        // below 1 or NaN gives a crop side of 1, above 8R a side of 8R (tests/test_augment_edges_gpu.py)
+        const int c = cd >= 1.0 && cd <= 8.0 * R ? (int)cd : (cd > 1.0 ? 8 * R : 1);
         sc.c_side = c;
         sc.off = (int)rint((double)(R - c) / 2.0);
         sc.hflip = hflip != 0;

@@ -106,7 +106,8 @@ class DeviceAugment:
     the same (seed, step) gives the same batch and nothing is carried between calls; `params` (a dict with those four
     tensors on the device) overrides the draw.  Without `use_aug`: the identity (scale 1, no rotation, no flip,
     gain 1).  `train` masks joints that leave the crop (`|coord| >= 1`), as the reference does for the train subset.
-    Values of given `params` are not checked on the host (that would synchronise): scale must lie in (1/R, 8].
+    Values of given `params` are not checked on the host (that would synchronise): the kernel clamps the crop side
+    `int(R * scale)` into `[1, 8R]` (1 below the range or at NaN, 8R above it).
     Everything is enqueued on the current stream; nothing synchronises with the host.
 
     `flip_pair=True` (flip test-time augmentation, `inference.predict(..., paired=True)`): the same launch also

@@ -21,7 +21,8 @@ Pillow version: generated with Pillow 12.2; the reference pins Pillow 4.2.1.  Bo
 bilinear value to uint8; the goldens follow 12.2 (the only version here).
 
 The expected image is stored as the uint8 crop Pillow produces (steps 1-3, exact); `to_input` turns it into the
-expected model input (steps 4-5, torch CPU ops), which keeps the file small.
+expected model input (steps 4-5, torch CPU ops), which keeps the file small.  `to_input` and the keypoint maths live in
+tests/augment_ref.py, the restatement the tests share; only the Pillow side (`pil_crop`) is kept here.
 
 Sources are blocky PCG64 images (32 x 32 blocks of uniform uint8 noise plus an 8-column stripe of a 1-pixel 0/255
 checker), so the file stays small while the block edges and the stripe exercise the bilinear taps and the truncation.
@@ -31,14 +32,14 @@ import sys
 import zlib
 
 import numpy as np
-import torch
-import torch.nn.functional as Fn
 from PIL import Image
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(ROOT, 'dsnt-pose2d_amd')]
+sys.path[:0] = [os.path.join(ROOT, 'dsnt-pose2d_amd'), os.path.join(ROOT, 'tests')]
 
+import augment_ref  # noqa: E402
+from augment_ref import to_input  # noqa: E402,F401  (steps 4-6; tests/test_augment_gpu.py takes it from here)
 from dsnt.inference import HFLIP_INDICES  # noqa: E402  (no HIP needed to import it)
 
 R = 384
@@ -93,6 +94,7 @@ def keypoints(name, m):
 
 def pil_crop(src, scale, rot, hflip):
     """Steps 1-3 with Pillow: the uint8 crop [c, c, 3] the reference's ToTensor receives."""
+    R = src.shape[0]
     img = Image.fromarray(src)
     if hflip:
         img = img.transpose(Image.Transpose.FLIP_LEFT_RIGHT)
@@ -103,46 +105,14 @@ def pil_crop(src, scale, rot, hflip):
     return np.asarray(img.crop((off, off, off + c, off + c))).copy()
 
 
-def to_input(crop, gain, S, mean=MEAN, std=STD):
-    """Steps 4-5 with torch CPU ops on the uint8 crop: the model input [3, S, S] f32."""
-    x = torch.from_numpy(np.ascontiguousarray(crop)).permute(2, 0, 1).contiguous().float().div(255)
-    for ch in range(3):
-        x[ch].mul_(float(gain[ch])).clamp_(0, 1)
-    out = Fn.adaptive_avg_pool2d(x, S)
-    for ch in range(3):
-        out[ch].sub_(float(mean[ch])).div_(float(std[ch]))
-    return out.numpy()
-
-
 def transform_image(src, scale, rot, hflip, gain, S, mean=MEAN, std=STD):
     """Steps 1-5: the model input [3, S, S] f32."""
-    return to_input(pil_crop(src, scale, rot, hflip), gain, S, mean, std)
-
-
-def aug_matrix(scale, rot, hflip):
-    t = np.eye(3)
-    if hflip:
-        t = np.array([[-1.0, 0, 0], [0, 1, 0], [0, 0, 1]]) @ t
-    a = np.radians(rot)
-    return np.array([[np.cos(a) / scale, np.sin(a) / scale, 0], [-np.sin(a) / scale, np.cos(a) / scale, 0],
-                     [0, 0, 1]]) @ t
+    return augment_ref.to_input(pil_crop(src, scale, rot, hflip), gain, S, mean, std)
 
 
 def transform_keypoints(kp, matrix, kmask, scale, rot, hflip, train=True):
-    """data.py:150-196 in fp64: (part_coords f64 [J,2], part_mask [J], trans_m [2,2], trans_b [1,2])."""
-    t = aug_matrix(scale, rot, hflip)
-    pc = (np.concatenate([kp, np.ones((len(kp), 1))], 1) @ matrix.T)[:, :2]
-    pc = (np.concatenate([pc, np.ones((len(pc), 1))], 1) @ t.T)[:, :2]
-    pm = kmask.astype(np.float64)
-    if hflip:
-        idx = HFLIP_INDICES.numpy()
-        pc2, pm2 = pc.copy(), pm.copy()
-        pc2[idx], pm2[idx] = pc, pm            # scatter_(0, idx, src): out[idx[i]] = src[i]
-        pc, pm = pc2, pm2
-    if train:
-        pm = pm * np.all(np.abs(pc) < 1, -1)
-    s = np.linalg.inv(matrix) @ np.linalg.inv(t)
-    return pc, pm, s[0:2, 0:2].copy(), s[0:2, 2].reshape(1, 2).copy()
+    """data.py:150-196 in fp64 with the MPII flip table: (part_coords f64 [J,2], part_mask [J], trans_m, trans_b)."""
+    return augment_ref.keypoints(kp, matrix, kmask, scale, rot, hflip, HFLIP_INDICES.numpy(), train)
 
 
 def make():

@@ -1,6 +1,7 @@
 """CPU checks of the training augmentation (dsnt.data.DeviceAugment, csrc/augment.hip): the golden file regenerates
-bit for bit, its keypoint maths agrees with the reference's torch formulation, the sampling rule the kernel implements
-reproduces Pillow's rotation exactly, and the new entry points are exported and validate their arguments."""
+bit for bit, its keypoint maths agrees with the reference's torch formulation, the restatement the GPU tests compare
+with (tests/augment_ref.py) reproduces Pillow's flip, rotation and centre crop exactly and draws what the kernel's
+header states, and the new entry points are exported and validate their arguments."""
 import ctypes as C
 import importlib.util
 import math
@@ -9,6 +10,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+import augment_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEN = os.path.join(ROOT, 'tests', 'golden', 'make_augment_golden.py')
@@ -87,31 +90,6 @@ def test_golden_covers_the_issue_cases():
     assert any(float(g[n + '.gain'].max()) * 255 > 255 * 1.5 for n in names)
 
 
-def _kernel_rotate(img, rot):
-    """The sampling rule csrc/augment.hip implements (step 2 of its header), restated in numpy."""
-    R = img.shape[0]
-    deg = rot % 360.0
-    ang = -math.radians(deg)
-    a, b = round(math.cos(ang), 15), round(math.sin(ang), 15)
-    c = a * -(R / 2) + b * -(R / 2) + 0.0 + R / 2
-    f = -b * -(R / 2) + a * -(R / 2) + 0.0 + R / 2
-    ys, xs = np.mgrid[0:R, 0:R].astype(np.float64)
-    xin = a * (xs + 0.5) + b * (ys + 0.5) + c
-    yin = -b * (xs + 0.5) + a * (ys + 0.5) + f
-    inside = (xin >= 0) & (xin < R) & (yin >= 0) & (yin < R)
-    xin, yin = xin - 0.5, yin - 0.5
-    x0, y0 = np.floor(xin), np.floor(yin)
-    dx, dy = (xin - x0)[..., None], (yin - y0)[..., None]
-    x0, y0 = x0.astype(int), y0.astype(int)
-    cl = lambda v: np.clip(v, 0, R - 1)
-    im = img.astype(np.float64)
-    v1 = im[cl(y0), cl(x0)] + (im[cl(y0), cl(x0 + 1)] - im[cl(y0), cl(x0)]) * dx
-    has2 = ((y0 + 1 >= 0) & (y0 + 1 < R))[..., None]
-    v2 = np.where(has2, im[cl(y0 + 1), cl(x0)] + (im[cl(y0 + 1), cl(x0 + 1)] - im[cl(y0 + 1), cl(x0)]) * dx, v1)
-    v = (v1 + (v2 - v1) * dy).astype(np.int64)            # truncation
-    return np.where(inside[..., None], v, 0).astype(np.uint8)
-
-
 @pytest.mark.parametrize('R', [40, 41, 384])
 def test_kernel_sampling_rule_is_pillows_rotation(R):
     from PIL import Image
@@ -119,7 +97,108 @@ def test_kernel_sampling_rule_is_pillows_rotation(R):
     img = r.integers(0, 256, (R, R, 3), dtype=np.uint8)
     for rot in (7.5, -7.5, 30.0, -30.0, 60.0, -59.9, 0.3, 359.0):
         want = np.asarray(Image.fromarray(img).rotate(rot, Image.Resampling.BILINEAR))
-        assert np.array_equal(_kernel_rotate(img, rot), want), (R, rot)
+        assert np.array_equal(augment_ref.rotate(img, rot), want), (R, rot)
+
+GRID_R = (5, 8, 9, 33, 40, 41, 97)
+GRID_ROT = (90.0, 180.0, 270.0, -90.0, 360.0, 720.5, 1e-6, -1e-6, 60.0, -60.0, 45.0, 0.3, 359.0,
+            float(np.float32(-59.9)), float(np.float32(12.345)), -0.0)
+GRID_SCALE = (2 ** -0.5, 0.75, 1.0, 1.3, 2 ** 0.5)
+
+
+@pytest.mark.parametrize('R', GRID_R)
+def test_restated_crop_is_pillows_flip_rotate_crop(R):
+    """augment_ref.crop against Image.transpose / rotate(BILINEAR) / crop on noise (every pixel differs from its
+    neighbours), bit for bit: right angles (Pillow's transpose shortcut), whole turns, -0.0, tiny angles, odd and even
+    R, c < R and c > R.  R = 5 adds c == 1."""
+    pil_crop = _gen().pil_crop
+    r = np.random.default_rng(1000 + R)
+    src = r.integers(0, 256, (R, R, 3), dtype=np.uint8)
+    scales = GRID_SCALE + ((0.3,) if R == 5 else ())
+    for hflip in (0, 1):
+        for rot in GRID_ROT:
+            for scale in scales:
+                scale = float(np.float32(scale))              # the kernel's parameters are fp32
+                got, want = augment_ref.crop(src, scale, rot, hflip), pil_crop(src, scale, rot, hflip)
+                assert got.shape == want.shape and np.array_equal(got, want), (R, rot, scale, hflip)
+    if R == 5:
+        assert augment_ref.crop(src, float(np.float32(0.3)), 7.5, 1).shape == (1, 1, 3)
+
+
+def test_restated_crop_clamps_like_the_kernel():
+    src = np.random.default_rng(5).integers(0, 256, (5, 5, 3), dtype=np.uint8)
+    for scale in (0.0, -1.0, 0.19, float('nan')):
+        assert np.array_equal(augment_ref.crop(src, scale, 0.0, 0), src[2:3, 2:3]), scale      # c = 1, offset 2
+    for scale in (100.0, 8.01, float('inf')):
+        big = augment_ref.crop(src, scale, 0.0, 0)
+        assert big.shape == (40, 40, 3) and np.array_equal(big[18:23, 18:23], src)              # offset round(-17.5) = -18
+        assert int(big.sum()) == int(src.sum())
+    assert augment_ref.crop(src, 8.0, 0.0, 0).shape == (40, 40, 3) and augment_ref.crop(src, 0.2, 0.0, 0).shape == (1, 1, 3)
+
+
+def test_restated_keypoints_match_the_reference_formulation():
+    from dsnt.inference import HFLIP_INDICES
+    g = _golden()
+    for n in g['names']:
+        p = str(n) + '.'
+        for train in (True, False):
+            args = (g[p + 'keypoints'], g[p + 'matrix'], g[p + 'keypoint_mask'], float(g[p + 'scale']),
+                    float(g[p + 'rot']), int(g[p + 'hflip']))
+            want = _reference_keypoints(*args, train=train)
+            got = augment_ref.keypoints(*args, HFLIP_INDICES.numpy(), train)
+            for a, w in zip(got, want):
+                assert a.shape == w.shape, (n, train)
+            for a, w in ((got[0], want[0]), (got[2], want[2]), (got[3], want[3])):
+                assert np.abs(a - w).max() <= 1e-12 * max(1.0, np.abs(w).max()), (n, train)
+            assert np.array_equal(got[1], want[1]), (n, train)
+
+
+def _draws_differ(a, b):
+    return any(not np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def test_restated_draw_is_a_function_of_every_counter_and_key_word():
+    sample = np.arange(64)
+    seed, step = 0x0123456789ABCDEF, 0x00000003_00000007
+    base = augment_ref.draw(seed, step, sample)
+    again = augment_ref.draw(seed, step, sample)
+    assert [x.dtype for x in base] == [np.float32, np.float32, np.uint8, np.float32]
+    assert [x.shape for x in base] == [(64,), (64,), (64,), (64, 3)]
+    assert all(np.array_equal(x, y) for x, y in zip(base, again))
+    one = augment_ref.draw(seed, step, 5)                              # a scalar sample word: that row of the batch
+    assert all(np.array_equal(np.asarray(x), y[5]) for x, y in zip(one, base))
+    assert _draws_differ(base, augment_ref.draw(seed, step, sample + 64))
+    assert _draws_differ(base, augment_ref.draw(seed, step ^ 1, sample))                  # step, low word
+    assert _draws_differ(base, augment_ref.draw(seed, step ^ (1 << 32), sample))          # step, high word
+    assert _draws_differ(base, augment_ref.draw(seed ^ 1, step, sample))                  # seed, low word
+    assert _draws_differ(base, augment_ref.draw(seed ^ (1 << 63), step, sample))          # seed, high word
+    # the sample word is 32 bits wide, as the kernel's is
+    assert all(np.array_equal(x, y) for x, y in zip(base, augment_ref.draw(seed, step, sample + 2 ** 32)))
+    # the three gains are three words of one Philox output, not one word reused
+    assert not np.array_equal(base[3][:, 0], base[3][:, 1]) and not np.array_equal(base[3][:, 1], base[3][:, 2])
+
+
+def test_restated_draw_respects_the_clip_bounds_exactly():
+    scale, rot, hflip, gain = augment_ref.draw(99, 3, np.arange(1 << 16))
+    lo, hi = np.float32(2 ** -0.5), np.float32(2 ** 0.5)
+    assert scale.min() == lo and scale.max() == hi                     # 4.6 % of the samples sit on each pair of bounds
+    assert 0.03 < (scale == lo).mean() + (scale == hi).mean() < 0.06
+    assert rot.min() == -60 and rot.max() == 60
+    assert 0.3 < (rot != 0).mean() < 0.5 and 0.4 < hflip.mean() < 0.6 and set(np.unique(hflip)) == {0, 1}
+    assert gain.astype(np.float64).min() > 0.6 and gain.max() <= np.float32(1.4)
+    # the ends of the word range: unit() is (0, 1], so the rotation threshold .4 and the flip threshold .5 are inclusive
+    w = lambda *v: [np.array([x], np.uint64) for x in v]
+    u = lambda t: int(t * 16777216 - 1) << 8                            # the smallest word with unit(word) == t
+    assert augment_ref.unit(0) == 2.0 ** -24 and augment_ref.unit(0xFFFFFFFF) == 1.0
+    assert augment_ref.unit(u(0.5)) == 0.5 and augment_ref.unit(u(0.5) + 256) > 0.5
+    s, r, h, gn = augment_ref.draw_from_words(w(0, 0, 0, u(0.5)), w(0, 0xFFFFFFFF, 0, 0), w(0, 0xFFFFFFFF, 0x80000000, 0))
+    assert s[0] == hi and r[0] == 60 and h[0] == 1                      # sqrt(-2 ln 2^-24) cos(2 pi 2^-24) = 5.77: clipped
+    assert gn[0, 0] == np.float32(0.6 + 0.8 * 2.0 ** -24) and gn[0, 1] == np.float32(1.4) and float(gn[0, 0]) > 0.6
+    s, r, h, gn = augment_ref.draw_from_words(w(0xFFFFFFFF, 0, 0xFFFFFFFF, u(0.5) + 256), w(0, 0, 0, 0), w(0, 0, 0, 0))
+    assert s[0] == 1 and r[0] == 0 and h[0] == 0                        # ln 1 = 0: scale 2^0; unit 1 > .4: no rotation
+    t4 = (int(0.4 * 16777216) - 1) << 8                                 # the largest word with unit(word) <= .4
+    assert augment_ref.unit(t4) <= 0.4 < augment_ref.unit(t4 + 256)
+    assert augment_ref.draw_from_words(w(0, 0, t4, 0), w(0, 0, 0, 0), w(0, 0, 0, 0))[1][0] == 60
+    assert augment_ref.draw_from_words(w(0, 0, t4 + 256, 0), w(0, 0, 0, 0), w(0, 0, 0, 0))[1][0] == 0
 
 
 def test_augment_symbols_exported_and_validated_without_gpu():
