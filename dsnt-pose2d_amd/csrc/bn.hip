@@ -214,8 +214,10 @@ extern "C" int dsnt_bn_bwd_finalize_bound(const float* partial, int ntiles, int6
                                           float* bound_out, void* stream) {
     DSNT_REQUIRE(partial && coef && scale && dz_amax && bound_out && ntiles > 0 && C > 0 && M > 0, DSNT_ERR_ARG,
                  "dsnt_bn_bwd_finalize_bound: bad argument");
+    // a frozen BatchNorm has no folded apply (dx = scale dz needs no bound of the coefficients): the flag is refused, not read as bit 0
+    DSNT_REQUIRE(!(accumulate & DSNT_BN_FROZEN), DSNT_ERR_ARG, "dsnt_bn_bwd_finalize_bound: DSNT_BN_FROZEN has no bound form");
     const BnFinP q{partial, ntiles, 1.0 / (double)M, 1.0, C, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 1, dgamma, dbeta, coef, nullptr,
-                   accumulate, BnBoundP{scale, dz_amax, sqrtf((float)M), reinterpret_cast<unsigned*>(bound_out)}};
+                   accumulate & 1, BnBoundP{scale, dz_amax, sqrtf((float)M), reinterpret_cast<unsigned*>(bound_out)}};
     DSNT_LAUNCH_OP(DSNT_ST_FIN_BWD, bn_finalize_kernel<1>, dim3((C + 15) / 16), dim3(FIN_T), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_bn_bwd_finalize_bound");
 }

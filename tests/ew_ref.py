@@ -1,11 +1,14 @@
 """The element-wise kernels of csrc/bn.hip, resample.hip, flat.hip, optim.hip and csrc/ew_bodies.h restated in numpy fp64, for
-tests/test_ew_ref_cpu.py (which pins this file to the torch CPU operators) and tests/test_elementwise_edges_gpu.py
-(which holds the HIP kernels to it).  No device code: everything here takes and returns numpy arrays on the host.
+tests/test_ew_ref_cpu.py (which pins this file to the torch CPU operators), tests/test_elementwise_edges_gpu.py and
+tests/test_bn_finalize_gpu.py (which hold the HIP kernels to it).  No device code: everything here takes and returns numpy arrays on the host.
 
 Layouts are the kernels': NHWC activations, [M][C] rows for the BatchNorm pieces, flat vectors for the optimisers.
 Inputs are the kernels' fp32 inputs taken to fp64; where a kernel's result is a selection (pool maximum, ReLU mask,
 skipped element) the selection rule is spelled out, where it is arithmetic the fp64 value comes with the a-priori
 fp32 rounding bound of the kernel's expression (`U` = 2^-24, `gamma(k)` = k U / (1 - k U): k rounded operations)."""
+import math
+from fractions import Fraction
+
 import numpy as np
 
 U = 2.0 ** -24
@@ -141,23 +144,24 @@ def tie_share(x, pool):
 
 
 # ---------------------------------------------------------------- BatchNorm: tile sums
-def _by_tile(t, M, C):
-    tiles = (M + TILE_ROWS - 1) // TILE_ROWS
-    pad = np.zeros((tiles * TILE_ROWS, C), dtype=np.float64)
+def _by_tile(t, M, C, rows=TILE_ROWS):
+    tiles = (M + rows - 1) // rows
+    pad = np.zeros((tiles * rows, C), dtype=np.float64)
     pad[:M] = t
-    return pad.reshape(tiles, TILE_ROWS, C)
+    return pad.reshape(tiles, rows, C)
 
 
-def tile_sums_of(t1, t2, M, C):
-    """Per 128-row tile and channel, in fp64: (sum t1, sum t2, sum |t1|, sum |t2|), each [tiles][C]."""
-    a, b = _by_tile(t1, M, C), _by_tile(t2, M, C)
+def tile_sums_of(t1, t2, M, C, rows=TILE_ROWS):
+    """Per 128-row tile and channel, in fp64: (sum t1, sum t2, sum |t1|, sum |t2|), each [tiles][C].  (`rows`: another tile
+    height, for hand-made partials of many tiles from a small x.)"""
+    a, b = _by_tile(t1, M, C, rows), _by_tile(t2, M, C, rows)
     return a.sum(1), b.sum(1), np.abs(a).sum(1), np.abs(b).sum(1)
 
 
-def tile_sums(x, M, C):
+def tile_sums(x, M, C, rows=TILE_ROWS):
     """dsnt_bn_stats: (sum x, sum x^2, sum |x|, sum x^2) per tile and channel from the fp32 `x` [M][C]."""
     x = np.asarray(x, dtype=np.float64).reshape(M, C)
-    return tile_sums_of(x, x * x, M, C)
+    return tile_sums_of(x, x * x, M, C, rows)
 
 
 def relu_mask(x, scale, shift):
@@ -364,3 +368,236 @@ def bn_vectors(x, gamma, beta, eps=1e-5):
     sc = (gamma * is_).astype(np.float32)
     sh = (beta - mu * sc).astype(np.float32)
     return mu, is_, sc, sh
+
+
+# ---------------------------------------------------------------- BatchNorm: the finalise step (partial[tiles][2][C] -> vectors)
+U64 = 2.0 ** -53
+BN_FROZEN = 2              # include/dsnt_hip.h: DSNT_BN_FROZEN
+
+
+def gamma64(k):
+    return k * U64 / (1.0 - k * U64)
+
+
+def half_ulp32(v):
+    """Half an fp32 unit in the last place of the binade `v` lies in (subnormal spacing, 2^-149, below 2^-126 and at 0)."""
+    v = np.abs(np.asarray(v, dtype=np.float64))
+    e = np.where(v == 0, -125, np.frexp(v)[1])                  # frexp(0) says exponent 0: zero belongs to the subnormal binade
+    return 0.5 * np.ldexp(1.0, np.maximum(e - 24, -149))
+
+
+def exact_tile_sums(partial):
+    """(S0, S1, A0, A1) per channel from partial[tiles][2][C]: the tile sums added EXACTLY (math.fsum: the correctly rounded
+    fp64 value of the real sum, whatever the order) and the sums of their absolute values."""
+    p = np.asarray(partial, dtype=np.float64)
+    assert p.ndim == 3 and p.shape[1] == 2
+    S = np.array([[math.fsum(p[:, k, c].tolist()) for c in range(p.shape[2])] for k in range(2)])
+    A = np.array([[math.fsum(np.abs(p[:, k, c]).tolist()) for c in range(p.shape[2])] for k in range(2)])
+    return S[0], S[1], A[0], A[1]
+
+
+def combine_f32(partial):
+    """What a left-to-right fp32 combine of the tile sums gives (the mistake the `cancelling` partials exist to show):
+    (S0, S1) as fp64 views of fp32 accumulators."""
+    p = np.asarray(partial, dtype=np.float32)
+    acc = np.zeros((2, p.shape[2]), dtype=np.float32)
+    for t in range(p.shape[0]):
+        acc = acc + p[t]                      # fp32 + fp32, rounded once per addition
+    return acc[0].astype(np.float64), acc[1].astype(np.float64)
+
+
+def _is(var, eps):
+    return 1.0 / np.sqrt(var + eps)
+
+
+def bn_finalize(partial, M, gamma, beta, running_mean, running_var, momentum, eps, training, sum_err=None, sums=None):
+    """dsnt_bn_finalize / bn_pro_forward in fp64 from the exact tile sums.  `momentum`, `eps`: taken as the fp32 values the
+    ABI receives.  gamma / beta / running_* may be None (the ABI's NULL).  training = 0: the statistics are the running
+    pair, `partial` is not read.  Returns a dict of fp64 vectors; every `bar_*` bounds |device fp32 value - reference|.
+
+    With u = 2^-53, T tiles, A_k = sum |partial_k|:
+      e_k  = gamma64(T) A_k            the kernels' fp64 combine, any order (`sum_err` = (e0, e1) replaces it: the error the
+                                       tile sums themselves carry, for an end-to-end bar)
+      dm   = e0 / M + 2u |mean|        mean = S0 * fl(1 / M): two roundings
+      dv   = e1 / M + 2 |mean| dm + dm^2 + 4u (|S1| / M + mean^2)      var = S1 invM - mean^2, clamped at 0 as the kernels do
+      invstd = fl32(1 / sqrt(var + eps)): half an fp32 ulp + max |is(var +- dv) - is(var)|, lower end clamped at 0 (is() is
+               monotone: the interval's image, no first-order expansion)
+      mean:  half an fp32 ulp + dm
+      running_mean / running_var = (1 - m) old + m new (unbias): half an fp32 ulp + m dm / m unbias dv
+    scale and shift are one and two fp32 operations on the device's OWN mean and invstd: scale_bits() / shift_ok().
+    `sums`: (exact_tile_sums(partial), tiles) computed before, for several calls on the same partials."""
+    m, eps = _f32(momentum), _f32(eps)
+    out = {}
+    if training:
+        (S0, S1, A0, A1), T = sums if sums is not None else (exact_tile_sums(partial), np.asarray(partial).shape[0])
+        e0, e1 = (gamma64(T) * A0, gamma64(T) * A1) if sum_err is None else sum_err
+        mean = S0 / M
+        raw = S1 / M - mean * mean
+        var = np.maximum(raw, 0.0)
+        dm = e0 / M + 2 * U64 * np.abs(mean)
+        dv = e1 / M + 2 * np.abs(mean) * dm + dm * dm + 4 * U64 * (np.abs(S1) / M + mean * mean)
+        out.update(S0=S0, S1=S1, A0=A0, A1=A1, var_raw=raw)
+    else:
+        mean = np.asarray(running_mean, dtype=np.float64)
+        var = np.asarray(running_var, dtype=np.float64)
+        dm, dv = np.zeros_like(mean), np.zeros_like(var)
+    is_ = _is(var, eps)
+    with np.errstate(divide='ignore'):
+        spread = np.maximum(np.abs(_is(var + dv, eps) - is_), np.abs(_is(np.maximum(var - dv, 0.0), eps) - is_))
+    out.update(mean=mean, var=var, invstd=is_, dm=dm, dv=dv, bar_mean=half_ulp32(mean) + dm, bar_invstd=half_ulp32(is_) + spread,
+               bar_invstd_spread=spread)
+    if training and running_mean is not None:
+        unbias = M / (M - 1.0) if M > 1 else 1.0
+        rm = (1.0 - m) * np.asarray(running_mean, dtype=np.float64) + m * mean
+        rv = (1.0 - m) * np.asarray(running_var, dtype=np.float64) + m * var * unbias
+        out.update(running_mean=rm, running_var=rv, bar_running_mean=half_ulp32(rm) + m * dm,
+                   bar_running_var=half_ulp32(rv) + m * unbias * dv)
+    return out
+
+
+def scale_bits(gamma, invstd_got):
+    """scale = fl32(gamma * invstd) on the device's own invstd — one fp32 multiply, nothing to contract; invstd itself
+    when gamma is NULL.  Compare as bits."""
+    is_ = np.asarray(invstd_got, dtype=np.float32)
+    return is_.copy() if gamma is None else np.asarray(gamma, dtype=np.float32) * is_
+
+
+def shift_ok(beta, mean_got, scale_got, shift_got):
+    """shift = beta - mean * scale on the device's own fp32 mean and scale: the compiler may contract, so either
+    fl32(beta - fl32(mean scale)) or the fused fl32(beta - mean scale).  The fused value is decided exactly (rationals:
+    the product of two fp32 numbers needs 48 bits, the difference more than fp64 may hold).  Returns a bool per channel;
+    zeros compare equal whatever their sign."""
+    mu, sc, got = (np.asarray(v, dtype=np.float32) for v in (mean_got, scale_got, shift_got))
+    b = np.zeros_like(mu) if beta is None else np.asarray(beta, dtype=np.float32)
+    ok = got == b - mu * sc                                    # numpy fp32: two roundings
+    for c in np.flatnonzero(~ok):
+        g = got[c]
+        if not np.isfinite(g):
+            continue
+        E = Fraction(float(b[c])) - Fraction(float(mu[c])) * Fraction(float(sc[c]))
+        d = abs(E - Fraction(float(g)))
+        lo, hi = (abs(E - Fraction(float(np.nextafter(g, np.float32(s))))) for s in (-np.inf, np.inf))
+        even = (int(np.asarray(g).view(np.uint32)) & 1) == 0
+        ok[c] = d <= lo and d <= hi and (even or (d < lo and d < hi))
+    return ok
+
+
+def bn_bwd_finalize(partial, M, flags, dgamma0, dbeta0, scale=None, dz_amax=None, sums=None):
+    """dsnt_bn_bwd_finalize(_bound) / bn_pro_backward in fp64 from the exact tile sums (S0 = sum dz, S1 = sum dz xhat).
+    `flags`: bit 0 = add to dgamma0 / dbeta0 (the fp32 vectors the launch finds; None = the ABI's NULL: nothing written),
+    BN_FROZEN = both coefficient rows are zero, dgamma / dbeta as without it.  Bars (e_k as in bn_finalize):
+      coef[k] = fl32(S_k fl(1 / M)):  half an fp32 ulp + e_k / M + 2u |S_k / M|        (frozen: exactly zero)
+      dgamma = fl32(S1), dbeta = fl32(S0):  half an ulp + e_k; accumulated: one more fp32 addition — half an ulp of the sum.
+    With `scale` and `dz_amax` (64 slots) the dict holds `bound(coef_got)`: per slot s the fp64 value of
+      max over 16-channel blocks vb = s (mod 64), channels c of the block:  |scale_c| (max dz_amax + |coef0_c| + |coef1_c| sqrtf(M))
+    on the device's own coef [2][C] (0 for a slot no block maps to), and `bar_bound_rel` = gamma(5): four fp32 operations
+    (product, two sums, product; the rounded sqrtf(M) is an input), one spare.  `sums`: as in bn_finalize."""
+    (S0, S1, A0, A1), T = sums if sums is not None else (exact_tile_sums(partial), np.asarray(partial).shape[0])
+    e0, e1 = gamma64(T) * A0, gamma64(T) * A1
+    frozen, acc = bool(flags & BN_FROZEN), bool(flags & 1)
+    c0, c1 = (np.zeros_like(S0), np.zeros_like(S1)) if frozen else (S0 / M, S1 / M)
+    out = {'S0': S0, 'S1': S1, 'coef': np.stack([c0, c1]),
+           'bar_coef': np.zeros((2, S0.size)) if frozen else np.stack([half_ulp32(c0) + e0 / M + 2 * U64 * np.abs(c0),
+                                                                        half_ulp32(c1) + e1 / M + 2 * U64 * np.abs(c1)])}
+    for name, S, e, old in (('dgamma', S1, e1, dgamma0), ('dbeta', S0, e0, dbeta0)):
+        if old is None:
+            out[name] = None
+            continue
+        bar = half_ulp32(S) + e
+        want = S
+        if acc:
+            want = S + np.asarray(old, dtype=np.float64)
+            bar = bar + half_ulp32(want)
+        out[name], out['bar_' + name] = want, bar
+    if scale is not None:
+        sc, dzmax = np.abs(np.asarray(scale, dtype=np.float64)), float(np.max(np.asarray(dz_amax, dtype=np.float64)))
+        sqrtM = float(np.sqrt(np.float32(M)))              # sqrtf((float)M): correctly rounded on both sides
+        C = S0.size
+
+        def bound(coef_got):
+            cg = np.abs(np.asarray(coef_got, dtype=np.float64)).reshape(2, C)
+            per = sc * (dzmax + cg[0] + cg[1] * sqrtM)
+            slots = np.zeros(64)
+            for vb in range((C + 15) // 16):
+                slots[vb & 63] = max(slots[vb & 63], per[vb * 16:vb * 16 + 16].max())
+            return slots
+        out['bound'], out['bar_bound_rel'] = bound, gamma(5)
+    return out
+
+
+def pro_mapping(C, NT):
+    """bn_pro_sums<NT>'s index arithmetic (csrc/bn_pro.h): the 2C-wide row of partial[tiles][2][C] goes through the workgroup
+    in chunks of NT columns; per chunk (nc columns, L = NT // nc tile lanes, idle = NT - nc L threads without a lane).
+    Returns the list of (nc, L, idle), one per chunk."""
+    ncol, out = 2 * C, []
+    for cb in range(0, ncol, NT):
+        nc = min(ncol - cb, NT)
+        L = NT // nc
+        out.append((nc, L, NT - nc * L))
+    return out
+
+
+def pro_reads(tiles, C, NT):
+    """How often bn_pro_sums<NT> reads each element of partial[tiles][2C] — must be once, nothing beyond `tiles` —, and per
+    chunk the largest number of trips of its 16-deep load batch any lane takes.  Mirrors the kernel's loops thread by thread."""
+    ncol = 2 * C
+    cnt = np.zeros((tiles, ncol), dtype=np.int64)
+    trips = []
+    for cb in range(0, ncol, NT):
+        nc = min(ncol - cb, NT)
+        L = NT // nc
+        most = 0
+        for tid in range(NT):
+            col, lane = tid % nc, tid // nc
+            if lane >= L:
+                continue
+            n = 0
+            for r0 in range(lane, tiles, 16 * L):
+                n += 1
+                for u in range(16):
+                    r = r0 + u * L
+                    if r < tiles:
+                        cnt[r, cb + col] += 1
+            most = max(most, n)
+        trips.append(most)
+    return cnt, trips
+
+
+# ---------------------------------------------------------------- BatchNorm: hand-made tile sums for the finalise tests
+def partial_producer(T, C, seed, rows=TILE_ROWS, offset=0.0):
+    """Tile sums as a producer leaves them: fl32 of tile_sums() of a bn_case x (+ `offset`), `rows` rows per tile, the last
+    tile ragged.  Returns (partial [T][2][C] fp32, M, x)."""
+    M = T * rows - (rows // 3 if T > 1 or rows > 1 else 0)
+    x = bn_case(M, C, seed)[0]
+    if offset:
+        x = (x / np.float32(1.7) + np.float32(offset)).astype(np.float32)       # spread ~1 around `offset`
+    s1, s2, _, _ = tile_sums(x, M, C, rows)
+    return np.stack([s1, s2], 1).astype(np.float32), M, x
+
+
+def partial_cancelling(T, C, seed, M=None):
+    """Integer-valued tile sums that tell an fp64 combine from an fp32 one: both rows alternate +2^26, a small odd integer,
+    -2^26, a small odd integer, ..., as many +2^26 as -2^26.  Every partial sum of any subset is an integer below 2^53: exact
+    in fp64 in ANY order.  In fp32 a small term vanishes beside 2^26 (ulp 8): row 0 holds 1 or 3, so a left-to-right fp32
+    combine loses EVERY small term up to the last -2^26 (all errors of one sign: they cannot cancel); row 1 holds odd
+    values below 256, so that var > 0.  T >= 4.
+    Returns (partial, M), M = 128 T - 37 unless given (the finalise step only divides by it)."""
+    assert T >= 4
+    r = np.random.default_rng(seed)
+    p = np.empty((T, 2, C), dtype=np.float64)
+    p[:, 0] = 2 * r.integers(0, 2, (T, C)) + 1
+    p[:, 1] = 2 * r.integers(0, 128, (T, C)) + 1
+    big = np.arange(0, T, 2)
+    big = big[:len(big) // 2 * 2]                                 # even tiles, an even number of them
+    for i, t in enumerate(big):
+        p[t, :, :] = (1.0 if i % 2 == 0 else -1.0) * 2.0 ** 26
+    return p.astype(np.float32), (128 * T - 37 if M is None else M)
+
+
+def partial_constant(T, C, values, rows=TILE_ROWS):
+    """Tile sums of channels with x = v everywhere (channel c: values[c % len(values)]), full tiles of `rows` (a power of two)
+    rows: rows v and rows v^2, exact in fp32 for v of at most 12 significant bits.  Returns (partial, M, v per channel)."""
+    v = np.array([values[c % len(values)] for c in range(C)], dtype=np.float64)
+    p = np.empty((T, 2, C), dtype=np.float64)
+    p[:, 0], p[:, 1] = rows * v, rows * v * v
+    return p.astype(np.float32), T * rows, v

@@ -226,3 +226,109 @@ def test_launch_mirrors():
     assert R.tile_cgs(8, 48) == 16 and R.tile_grid_y(8, 48) == 3 and R.tile_cgs(2, 258) == 256 and R.tile_grid_y(2, 258) == 1
     assert R.apply_is_fixed(163841, 64) == (True, 4096) and R.apply_is_fixed(2561, 128, pro=True) == (True, 128)
     assert not R.apply_is_fixed(350, 48)[0] and not R.apply_is_fixed(60003, 80)[0]
+
+
+# ---------------------------------------------------------------- the BatchNorm finalise oracle
+def _finalize_case(M, C, seed):
+    x, gamma, beta, da = R.bn_case(M, C, seed)
+    s1, s2, _, _ = R.tile_sums(x, M, C)
+    return x, gamma, beta, da, np.stack([s1, s2], 1)             # partial [tiles][2][C], fp64: the sums unrounded
+
+
+@pytest.mark.parametrize('M,C', [(1, 8), (37, 20), (4133, 64)])
+def test_bn_finalize_oracle_equals_batch_norm(M, C):
+    """R.bn_finalize fed with R.tile_sums(x) == F.batch_norm(x.double(), training=True): the output through scale / shift and
+    both running statistics after two calls (two inputs) with momentum 0.1 — two fp64 programs, 1e-12 relative.  momentum and
+    eps are handed to torch as the fp32 values the ABI carries.  torch refuses one value per channel in training mode, so
+    at M = 1 the reference is the definition: mean = x, var = 0 (unbias = 1), y = beta."""
+    mom, eps = _h(0.1), _h(1e-5)
+    rm, rv = np.linspace(-1, 1, C), np.linspace(0.5, 2, C)
+    rmt, rvt = torch.from_numpy(rm.copy()), torch.from_numpy(rv.copy())
+    for call in range(2):
+        x, gamma, beta, _, part = _finalize_case(M, C, seed=M + C + call)
+        o = R.bn_finalize(part, M, gamma, beta, rm, rv, 0.1, 1e-5, 1)
+        scale = gamma.astype(np.float64) * o['invstd']
+        y = x.astype(np.float64) * scale + (beta.astype(np.float64) - o['mean'] * scale)
+        if M > 1:
+            yt = F.batch_norm(torch.from_numpy(x).double(), rmt, rvt, torch.from_numpy(gamma).double(),
+                              torch.from_numpy(beta).double(), True, mom, eps).numpy()
+        else:
+            yt = np.broadcast_to(beta.astype(np.float64), (1, C))
+            rmt = (1 - mom) * rmt + mom * torch.from_numpy(x[0]).double()
+            rvt = (1 - mom) * rvt
+        assert np.abs(y - yt).max() <= 1e-12 * max(1.0, np.abs(yt).max())
+        rm, rv = o['running_mean'], o['running_var']
+        assert np.abs(rm - rmt.numpy()).max() <= 1e-12 * np.abs(rmt.numpy()).max()
+        assert np.abs(rv - rvt.numpy()).max() <= 1e-12 * np.abs(rvt.numpy()).max()
+        assert (o['bar_mean'] > 0).all() and (o['bar_invstd'] > 0).all()
+    # eval mode: the running pair is the statistic, nothing moves
+    e = R.bn_finalize(None, M, gamma, beta, rm, rv, 0.1, 1e-5, 0)
+    assert np.array_equal(e['mean'], rm) and np.abs(e['invstd'] - 1 / np.sqrt(rv + eps)).max() <= 1e-15 * e['invstd'].max()
+    assert 'running_mean' not in e and not e['dm'].any() and not e['bar_invstd_spread'].any()
+
+
+@pytest.mark.parametrize('M,C', [(1, 8), (37, 20), (4133, 64)])
+def test_bn_bwd_finalize_oracle_equals_autograd(M, C):
+    """R.bn_bwd_finalize == autograd's dgamma / dbeta, and its two coefficients are the ones with which R.bn_apply reproduces
+    x.grad (1e-12 relative; M = 1 by the definition: xhat = 0, dx = 0, dgamma = 0, dbeta = da).  Accumulation adds the old
+    vectors; DSNT_BN_FROZEN zeroes the coefficients and nothing else."""
+    x, gamma, beta, da, part = _finalize_case(M, C, seed=3 * M + C)
+    f = R.bn_finalize(part, M, gamma, beta, None, None, 0.1, 1e-5, 1)
+    d1, d2, _, _ = R.bn_bwd_tile_sums(da, x, f['mean'], f['invstd'], M, C)
+    bpart = np.stack([d1, d2], 1)
+    old_g, old_b = np.full(C, 0.25, np.float32), np.full(C, -0.5, np.float32)
+    o = R.bn_bwd_finalize(bpart, M, 0, old_g, old_b)
+    scale = gamma.astype(np.float64) * f['invstd']
+    dx, _, _ = R.bn_apply(da, x, scale, beta - f['mean'] * scale, f['mean'], f['invstd'], o['coef'], 0)
+    if M > 1:
+        xt = torch.from_numpy(x).double().requires_grad_()
+        gt, bt = torch.from_numpy(gamma).double().requires_grad_(), torch.from_numpy(beta).double().requires_grad_()
+        F.batch_norm(xt, None, None, gt, bt, True, _h(0.1), _h(1e-5)).backward(torch.from_numpy(da).double())
+        want_dx, want_dg, want_db = xt.grad.numpy(), gt.grad.numpy(), bt.grad.numpy()
+    else:
+        want_dx, want_dg, want_db = np.zeros((1, C)), np.zeros(C), da[0].astype(np.float64)
+    ref = max(1.0, np.abs(want_dx).max())
+    assert np.abs(dx - want_dx).max() <= 1e-12 * ref * max(1.0, float(f['invstd'].max()))
+    assert np.abs(o['dgamma'] - want_dg).max() <= 1e-12 * max(1.0, np.abs(want_dg).max())
+    assert np.abs(o['dbeta'] - want_db).max() <= 1e-12 * max(1.0, np.abs(want_db).max())
+    a = R.bn_bwd_finalize(bpart, M, 1, old_g, old_b)
+    assert np.array_equal(a['dgamma'], o['dgamma'] + 0.25) and np.array_equal(a['dbeta'], o['dbeta'] - 0.5)
+    assert np.array_equal(a['coef'], o['coef']) and (a['bar_dgamma'] > o['bar_dgamma']).all()
+    z = R.bn_bwd_finalize(bpart, M, R.BN_FROZEN | 1, old_g, None)
+    assert not z['coef'].any() and not z['bar_coef'].any() and np.array_equal(z['dgamma'], a['dgamma']) and z['dbeta'] is None
+
+
+def test_finalize_bars_admit_a_plain_fp64_combine_and_refuse_an_fp32_one():
+    """The bars are no tighter than a left-to-right fp64 evaluation of the kernels' expressions achieves (numpy, another
+    order than math.fsum), on producer, offset and cancelling partials; and on the cancelling partials a left-to-right fp32
+    combine misses the mean bar by more than 10x."""
+    for part, M in (R.partial_producer(65, 20, 1)[:2], R.partial_producer(257, 8, 2, rows=4, offset=300.0)[:2], R.partial_cancelling(1027, 20, 3)):
+        o = R.bn_finalize(part, M, None, None, None, None, 0.1, 1e-5, 1)
+        s = np.zeros((2, part.shape[2]))
+        for t in range(part.shape[0]):
+            s += part[t].astype(np.float64)
+        mean = s[0] * (1.0 / M)
+        var = np.maximum(s[1] * (1.0 / M) - mean * mean, 0.0)
+        is_ = (1.0 / np.sqrt(var + float(np.float32(1e-5)))).astype(np.float32)
+        assert (np.abs(mean.astype(np.float32).astype(np.float64) - o['mean']) <= o['bar_mean']).all()
+        assert (np.abs(is_.astype(np.float64) - o['invstd']) <= o['bar_invstd']).all()
+    f0, _ = R.combine_f32(part)
+    assert (np.abs(f0 / M - o['mean']) >= 10 * o['bar_mean']).all()
+
+
+def test_half_ulp32():
+    """Half an fp32 ulp of the binade: powers of two open their binade, zero and the subnormals share the spacing 2^-149."""
+    v = np.array([1.0, 1.5, 2.0, 0.75, -300.0, 2.0 ** -126, 2.0 ** -130, 0.0, -0.0])
+    want = np.array([2.0 ** -24, 2.0 ** -24, 2.0 ** -23, 2.0 ** -25, 2.0 ** -16, 2.0 ** -150, 2.0 ** -150, 2.0 ** -150, 2.0 ** -150])
+    assert np.array_equal(R.half_ulp32(v), want)
+    for x in (1.0, 1.5, 0.75, 300.0):
+        assert R.half_ulp32(x) == 0.5 * float(np.spacing(np.float32(x)))
+
+
+def test_prologue_mapping_mirror():
+    """R.pro_mapping / R.pro_reads as the GPU module's premise table uses them: every element read once at every shape."""
+    assert R.pro_mapping(20, 256) == [(40, 6, 16)] and R.pro_mapping(160, 256) == [(256, 1, 0), (64, 4, 0)]
+    assert R.pro_mapping(160, 512) == [(320, 1, 192)] and R.pro_mapping(256, 256) == [(256, 1, 0)] * 2
+    for C_, NT, tiles, want in ((20, 256, 97, [2]), (160, 256, 65, [5, 2]), (4, 512, 1025, [2]), (256, 512, 17, [2]), (64, 256, 1, [1])):
+        cnt, trips = R.pro_reads(tiles, C_, NT)
+        assert (cnt == 1).all() and trips == want
