@@ -20,12 +20,14 @@ the fused optimiser and the RCCL all-reduce operate on).
 """
 import ctypes as C
 import os
-import struct
 
 import torch
 
 from . import _lib
 from ._lib import ConvGeom, BnBwdEpilogue, BnTail, BnPrologue, BnBwdApply
+from .bounds import Bounds
+from .launchlist import Lanes, LaunchList
+from .wgrad_queue import WgradQueue
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -58,6 +60,11 @@ class Act:
     @property
     def M(self):
         return self.N * self.H * self.W
+
+    @property
+    def untouched(self):
+        """No gradient has reached this activation in any form: it can still start as another's `base`."""
+        return self._grad is None and self.base is None and self.pending_apply is None and self.pending_add is None
 
     @property
     def grad(self):
@@ -114,7 +121,7 @@ class _Dgrad:
 
 
 class Tape:
-    def __init__(self, device, training, record=None):
+    def __init__(self, device, training, record=None, want_input_grad=False):
         self.device = device
         # `training` is the BatchNorm mode (batch statistics vs running statistics, nn.Module.train / eval); `record` says
         # whether a backward list is built.  They differ for a backward through an EVAL-mode forward (frozen BatchNorm
@@ -122,48 +129,28 @@ class Tape:
         # program runs on the bound-free kernels: bf16x6, none of the fp16x3-only fused kernels
         self.training = training
         self.record = training if record is None else bool(record)
-        self.fwd = []           # (cfunc, args)
-        self.bwd = []
+        self.want_input_grad = want_input_grad      # d loss / d image is asked for: the stem keeps its data gradient
         self._bwd_emitters = []
         self._scratch = {}
         self._keep = []         # keeps ctypes structs / tensors alive
         self.lib = _lib.load()
         self.nbytes = 0
-        self.bytes_fwd, self.bytes_bwd, self.bytes_by_name, self._ws_ptrs = 0, 0, {}, set()
         self._read_switches()
+        # the two launch lists (dsnt.launchlist), replayed from C: recorded once into the library, then issued by ONE call per segment
+        stage = (device, self.stage_min_run, self.stage_max_vgrid, self.stage_grid) if (self.stage and device.type == 'cuda') else None
+        lanes = Lanes(self.use_lanes, self.n_lanes)
+        self.fwd, self.bwd = (LaunchList(self.lib, lanes, self._keep, stage) for _ in range(2))
+        self.bounds = Bounds(self)          # fp16x3 operand bounds and the per-step preparation (dsnt.bounds)
+        self.wgrads = WgradQueue(self)      # weight gradients held back, grouped and reduced per bucket (dsnt.wgrad_queue)
         self.lane = 0           # the lane being traced onto
-        self.side_stream, self.wgrad_stream, self.more_streams = None, None, ()
-        self.stage_census = []      # (stage launches, recorded launches inside) per compiled list
-        self._f16_w_stream = {}
         self.cur_bucket = 0         # parameter bucket of the layers being traced (mark_bucket)
-        self._wgrad_lane_reads = set()
-        self._writer_base = None
         self._ident = None
-        self._release_total, self._release_left, self._held = 0, 0, []
         self.acts = []          # every activation in creation order (debugging / introspection)
-        self.dgrad_slots = []   # (conv params, dst offset) of every conv whose data gradient is needed
-        self.dgrad_total, self.dgrad_f32, self.dgrad_planes = 0, None, None
         self.param_arena = None  # flat fp32 parameter arena (set by the Program) for the one-launch pack
-        self._pending_reduce = []   # table rows of the slabs written since the last flush
-        self._pending_group = []    # (descriptor bytes, workgroups) since the last flush
-        self._f16_w_rows, self._f16_w_seen = [], set()
-        self._f16_bn_rows = []
-        self._eval_bn_rows = []     # eval mode: every BatchNorm's vectors come from ONE table-driven launch per forward
-        # backward bounds, zeroed at the start of every backward: they follow the gradient through every writer that can report
-        # one (apply, axpy, pool / upsample backward) and through donations
-        self._amax_buf, self._amax_used = None, 0
-        self._planar_src, self._prep_exempt, self._post_reduce = {}, set(), []
-        self._famax_buf, self._famax_used, self._famax_of, self._famax_bn_of = None, 0, {}, {}   # forward activations: zeroed at the start of every forward
-        self._f16_dw_rows = []      # fp16x3 planes of the re-packed data-gradient weights
-        self._dgrad_pack = None     # arguments of the one re-packing launch (set by finish, emitted by emit_f16_prep)
-        self.dgrad_planes16, self.dgrad_bounds = None, None
+        self._planar_src = {}
         # every fp16x3 launch with the tensors behind its operands and bounds: (list entry, {...}) — lets a test walk a
         # step launch by launch and hold each bound against the operand it must dominate (tests/test_bounds_gpu.py)
         self.f16_uses = []
-        self._pending_group_uses = []
-        # replay from C (dsnt_list_*): a launch list is recorded once into the library and then issued by ONE call per
-        # segment instead of one ctypes call per launch (`_run`)
-        self._clists = {}
 
     def _read_switches(self):
         """The switches and thresholds of the schedule: product defaults, each with the environment variable that overrides it
@@ -253,6 +240,7 @@ class Tape:
         self.use_f16x3 = self.use_bf16x6 and os.environ.get('DSNT_SPLIT', 'f16x3') == 'f16x3'
         if self.record and not self.training:
             self.use_f16x3 = False      # (its backward operand bounds come from BATCH statistics: |xhat| <= sqrt(M))
+        self.no_relu = bool(os.environ.get('DSNT_DEBUG_NO_RELU'))   # smooth network for exact gradient checks
 
     # ------------------------------------------------------------------ buffers
     def empty(self, *shape, dtype=torch.float32):
@@ -273,150 +261,16 @@ class Tape:
             self._scratch[key] = t
         return t
 
-    def f16_weights(self, p, wq16=None, wsrc=None, wb=None, stream=False):
-        """Register conv weights (default: the arena's forward layout) for the per-step fp16x3 preparation.
-        stream: the planes of a 3x3 filter in the K-step order of dsnt_conv_fwd_f16x3_stream (csrc/conv3s.hip)."""
-        wq16 = p.wq16 if wq16 is None else wq16
-        key = wq16.data_ptr()
-        if key not in self._f16_w_seen:
-            self._f16_w_seen.add(key)
-            wsrc = p.w if wsrc is None else wsrc
-            wb = p.wb if wb is None else wb
-            n = wsrc.numel()
-            assert n % 4 == 0
-            self._f16_w_rows.append([wsrc.data_ptr(), wq16.data_ptr(), wb.data_ptr(), n, p.wq_stride] +
-                                    ([p.Cout, p.Cin] if stream else [0, 0]))
-            self._f16_w_stream[key] = stream
-        assert self._f16_w_stream.get(key, False) == stream, 'one weight tensor, two plane layouts'
+    def upload(self, rows, dtype=torch.int64):
+        """A table of a table-driven launch, on the device and kept alive."""
+        t = torch.tensor(rows, dtype=dtype).to(self.device)
+        self._keep.append(t)
+        return t
 
     def stream_ok(self, p, g, rows, res2):
         """A 3x3 convolution the symmetric persistent kernel runs (weights in stream order): at most one residual."""
         return (self.conv3s and p.R == 3 and p.S == 3 and res2 is None and
                 bool(self.lib.dsnt_conv_fwd_stream_ok(C.byref(g))))
-
-    def f16_bn_bound(self, n):
-        """Device scalar >= |relu?(bn(x))| of the train-mode BatchNorm seen through Normed n."""
-        if n.abound is None:
-            n.abound = self.empty(64)            # a bound = 64 slots (DSNT_BOUND_SLOTS)
-            bits = struct.unpack('<I', struct.pack('<f', float(n.x.M) ** 0.5))[0]
-            self._f16_bn_rows.append([n.bn.gamma.data_ptr(), n.bn.beta.data_ptr(), n.abound.data_ptr(), n.bn.C, bits])
-        return n.abound
-
-    def amax_slot(self):
-        if self._amax_buf is None:
-            self._amax_buf = self.empty(64 * 4096)
-        assert self._amax_used + 64 <= self._amax_buf.numel(), 'backward bound slots exhausted'
-        self._amax_used += 64
-        return self._amax_buf[self._amax_used - 64:self._amax_used]
-
-    def operand_amax(self, x):
-        """Bound slot for activation x used as a RAW fp16x3 operand (no BatchNorm in between: skip projections, `lin`
-        convolutions): the launch that produced x is asked — through its dsnt_out_bounds, read at launch time — to leave
-        max|x| there (-0.24 ms against bf16x6 for those convolutions).  None if the producer cannot."""
-        t = x.amax_tail
-        if t is None or not self.use_f16x3:
-            return None
-        slot = self._famax_of.get(id(t))
-        if slot is None:
-            slot = self._famax_slot()
-            t.amax = slot.data_ptr()
-            self._famax_of[id(t)] = slot
-            self._keep.append(t)
-        return slot
-
-    def _famax_slot(self):
-        if self._famax_buf is None:
-            self._famax_buf = self.empty(64 * 2048)      # hg8 with every level on fp16x3 claims ~800 slots
-        assert self._famax_used + 64 <= self._famax_buf.numel(), 'forward bound slots exhausted'
-        self._famax_used += 64
-        return self._famax_buf[self._famax_used - 64:self._famax_used]
-
-    def operand_amax_bn(self, n):
-        """Eval mode: bound slot for relu?(bn(x)) as an fp16x3 operand.  The BatchNorm vectors come from running
-        statistics (one dsnt_bn_eval_prep launch at the head of the forward), so the launch that produces x can form
-        the operand itself and leave its exact maximum (dsnt_out_bounds.amax_bn).  One BatchNorm per producer; None if
-        the producer cannot or is already taken by another BatchNorm."""
-        t = n.x.amax_tail
-        if t is None or not self.use_f16x3 or self.training:
-            return None
-        got = self._famax_bn_of.get(id(t))
-        if got is not None:
-            return got[1] if got[0] is n else None
-        slot = self._famax_slot()
-        t.amax_bn, t.amax_scale, t.amax_shift = slot.data_ptr(), n.scale.data_ptr(), n.shift.data_ptr()
-        t.amax_relu = 1 if n.relu else 0
-        self._famax_bn_of[id(t)] = (n, slot)
-        self._keep.append(t)
-        return slot
-
-    def f16_bn_bound_bwd(self, n):
-        """The same bound for a backward consumer.  The forward list computes it every step (emit_f16_prep) only if
-        some forward conv asked for it before the list was closed; rows added later would be lost."""
-        assert n.abound is not None, 'fp16x3 backward needs the BN bound its forward conv registered'
-        return n.abound
-
-    # launches that read weight planes or operand bounds: the preparation must have finished before the first of them
-    _PREP_CONSUMERS = ('dsnt_conv_fwd_f16x3_ex', 'dsnt_conv_fwd_f16x3_stream', 'dsnt_conv1x1_fwd_f16x3', 'dsnt_stem4_fwd_f16x3',
-                       'dsnt_conv_fwd_bf16x6_ex', 'dsnt_conv_fwd_bf16x6')
-
-    def emit_f16_prep(self, pos, head=()):
-        """Insert the per-step preparation launches at position `pos` of the forward list: fp16x3 weight planes and BN
-        operand bounds, eval-mode BN vectors and — weights do not change between a forward and its backward — the
-        re-packed / split data-gradient weights.  `head` = entries already on the list at `pos` that belong to the
-        preparation (the bf16 split of the arena).  With lanes, all of it runs on the side lane beside the stem
-        convolution (which reads fp32 weights) and the main lane waits right before the first launch that needs it."""
-        # (eval mode: the BN vectors are needed at once, and there is nothing to hide the launches behind)
-        side = 1 if (self.use_lanes and self.training) else 0      # (beside the stem: -0.15 ms)
-        saved, self.fwd = self.fwd, []
-        saved_lane, self.lane = self.lane, side
-        for fn, args, name, _ in head:
-            self.fwd.append((fn, args, name, side))
-        if self._f16_w_rows:
-            t = torch.tensor(self._f16_w_rows, dtype=torch.int64).to(self.device)
-            self._keep.append(t)
-            self.f('dsnt_f16_prep_weights', t, len(self._f16_w_rows), 7)
-        if self._f16_bn_rows:
-            t = torch.tensor(self._f16_bn_rows, dtype=torch.int64).to(self.device)
-            self._keep.append(t)
-            self.f('dsnt_f16_prep_bn_bounds', t, len(self._f16_bn_rows))
-        if self._eval_bn_rows:
-            t = torch.tensor(self._eval_bn_rows, dtype=torch.int64).to(self.device)
-            self._keep.append(t)
-            self.f('dsnt_bn_eval_prep', t, len(self._eval_bn_rows))
-        fwd_half = len(self.fwd)                # everything from here on is read by the backward list only
-        if self._dgrad_pack is not None:
-            self.f('dsnt_conv_pack_dgrad_all', *self._dgrad_pack)
-        if self._f16_dw_rows:
-            t = torch.tensor(self._f16_dw_rows, dtype=torch.int64).to(self.device)
-            self._keep.append(t)
-            self.f('dsnt_f16_prep_weights', t, len(self._f16_dw_rows), 7)
-        self.lane = 0
-        if self._famax_used:
-            self.f('dsnt_fill_zero', self._famax_buf, self._famax_used)
-            self.fwd.insert(0, self.fwd.pop())      # main lane, first: every producer comes after it
-        self.lane = saved_lane
-        prep, self.fwd = self.fwd, saved
-        # (the fill_zero entry was moved to the front: the boundary index moves with it)
-        fwd_half = fwd_half + 1 if self._famax_used else fwd_half
-        relay = None
-        if side and self.prep_split and self.n_lanes > 3 and 0 < fwd_half < len(prep):
-            # the backward-only half keeps running on the side lane while the forward proceeds: an idle lane takes the dependency
-            # on the FIRST half here (a list entry records and waits at one position), the main lane waits for that lane below
-            relay = self.n_lanes - 1
-            prep.insert(fwd_half, (None, (side, relay, torch.cuda.Event()), 'sync', 0))
-        del self.fwd[pos:pos + len(head)]
-        self.fwd[pos:pos] = prep
-        if side and prep:
-            first = next((i for i in range(pos + len(prep), len(self.fwd))
-                          if self.fwd[i][0] is not None and self.fwd[i][2] in self._PREP_CONSUMERS
-                          and id(self.fwd[i]) not in self._prep_exempt), len(self.fwd))
-            if relay is not None:
-                # the relay lane is taken to be idle up to here: an op (or a wait) traced onto it before `first` would put the main
-                # lane behind that op without anyone noticing — refuse at trace time instead
-                for ent in self.fwd[pos + len(prep):first]:
-                    busy = ent[3] == relay if ent[0] is not None else (ent[2] == 'sync' and relay in ent[1][:2])
-                    assert not busy, 'prep relay lane %d is in use before the first prep consumer (%s)' % (relay, ent[2])
-            self.fwd.insert(first, (None, (side if relay is None else relay, 0, torch.cuda.Event()), 'sync', 0))
 
     def _use6(self, g):
         return (self.use_bf16x6 and g.N * g.Ho * g.Wo >= self.bf16x6_min_rows and
@@ -428,35 +282,25 @@ class Tape:
         return a
 
     # ------------------------------------------------------------------ emission helpers
-    def _emit(self, lst, name, *args):
-        fn = getattr(self.lib, name)
-        conv = []
-        for a in args:
-            if isinstance(a, torch.Tensor):
-                # algorithmic HBM bytes of the step (bench.py `step_bounds`): every tensor a launch names is read or
-                # written once by it; weight-gradient slabs (workspace, not algorithm) are left out
-                if a.data_ptr() not in self._ws_ptrs:
-                    nb = a.numel() * a.element_size()
-                    self.bytes_by_name[name] = self.bytes_by_name.get(name, 0) + nb
-                    if lst is self.fwd:
-                        self.bytes_fwd += nb
-                    else:
-                        self.bytes_bwd += nb
-                conv.append(_lib.ptr(a))
-            elif isinstance(a, (ConvGeom, BnBwdEpilogue, BnTail, BnPrologue, BnBwdApply)):
-                self._keep.append(a)
-                conv.append(C.byref(a))
-            else:
-                conv.append(a)
-        entry = (fn, tuple(conv), name, self.lane)
-        lst.append(entry)
-        return entry
-
     def f(self, name, *args):
-        return self._emit(self.fwd, name, *args)
+        return self.fwd.emit(self.lane, name, *args)
 
     def b(self, name, *args):
-        return self._emit(self.bwd, name, *args)
+        return self.bwd.emit(self.lane, name, *args)
+
+    def b_amax(self, name, *args, amax):
+        """`name`, or — the gradient it writes has a bound slot — `name`_amax, which leaves max|written| in that slot."""
+        return self.b(name, *args) if amax is None else self.b(name + '_amax', *args, amax)
+
+    bytes_fwd = property(lambda self: self.fwd.nbytes)
+    bytes_bwd = property(lambda self: self.bwd.nbytes)
+
+    @property
+    def bytes_by_name(self):
+        both = dict(self.fwd.bytes_by_name)
+        for name, nb in self.bwd.bytes_by_name.items():
+            both[name] = both.get(name, 0) + nb
+        return both
 
     def on_backward(self, fn):
         lane = self.lane
@@ -474,15 +318,14 @@ class Tape:
         """`dst` lane waits for everything emitted so far on `src`; mirrored in backward unless bwd=False."""
         if not self.use_lanes:
             return
-        self.fwd.append((None, (src, dst, torch.cuda.Event()), 'sync', 0))
+        self.fwd.sync(src, dst)
         if self.record and bwd:
-            self._bwd_emitters.append(
-                lambda: self.bwd.append((None, (dst, src, torch.cuda.Event()), 'sync', 0)))
+            self._bwd_emitters.append(lambda: self.bwd.sync(dst, src))
 
     def sync_bwd(self, src, dst):
         """Backward-list only: `dst` lane waits for what has been emitted on `src` so far."""
         if self.use_lanes and src != dst:
-            self.bwd.append((None, (src, dst, torch.cuda.Event()), 'sync', 0))
+            self.bwd.sync(src, dst)
 
     def branch(self, x, join=True):
         """Alias of activation x for a branch traced on the side lane: same buffer and statistics,
@@ -504,91 +347,22 @@ class Tape:
 
     def finish(self):
         """Emit the backward list (reverse order of the forward ops)."""
-        if self.dgrad_slots:
-            # one launch re-packs (tap-flipped, transposed) and bf16-splits every dgrad weight
-            total = (self.dgrad_total + 7) // 8 * 8
-            self.dgrad_f32 = self.empty(total)
-            self.dgrad_planes = self.empty(3 * total, dtype=torch.bfloat16)
-            rows = []
-            for p, dst in self.dgrad_slots:
-                src = (p.w.data_ptr() - self.param_arena.data_ptr()) // 4
-                rows.append([src, dst, p.Cout, p.R, p.S, p.Cin])
-            table = torch.tensor(rows, dtype=torch.int32).to(self.device)
-            self._keep.append(table)
-            # launched by the forward list's preparation (emit_f16_prep), off the backward's critical path
-            self._dgrad_pack = (table, len(rows), self.param_arena, self.dgrad_f32, self.dgrad_planes, total)
-            self.dgrad_total = total
-            if self.use_f16x3:
-                self.dgrad_planes16 = self.empty(2 * total, dtype=torch.float16)
-                self.dgrad_bounds = self.empty(64 * len(rows))
+        self.bounds.close_dgrad()
         prep_pos = len(self.bwd)
-        self._release_left = self._release_total
+        self.wgrads.begin_backward()
         for fn in reversed(self._bwd_emitters):
             fn()
         self._bwd_emitters = []
-        # fp16x3: zero the amax slots (the re-packed data-gradient weights are split by the forward list's preparation)
-        saved, self.bwd = self.bwd, []
-        if self._amax_used:
-            self.b('dsnt_fill_zero', self._amax_buf, self._amax_used)
-        prep, self.bwd = self.bwd, saved
-        self.bwd[prep_pos:prep_pos] = prep
-        if self._pending_reduce:          # convolutions outside every parameter bucket (stand-alone modules)
-            self.lane = self._flush_lane()
-            self.flush_wgrad()
-
-    def release_wgrads(self):
-        """Put the held-back weight-gradient launches on the backward list here."""
-        if self._held:
-            self.bwd.extend(self._held)
-            self._held = []
-
-    def _flush_lane(self):
-        """The lane that reduces a bucket's weight-gradient slabs, made to wait for every lane that wrote one.  With a
-        weight-gradient lane it is that lane — the main lane neither waits for the backlog of weight gradients nor
-        runs the reduction; without, the main lane."""
-        self.release_wgrads()
-        fl = self.wgrad_lane if self.wgrad_lane is not None else 0
-        for src in self.chain_lanes:
-            self.sync_bwd(src, fl)
-        return fl
-
-    def flush_wgrad(self):
-        """Emit the one-launch reduction of every weight-gradient slab written since the last flush."""
-        rows = self._pending_reduce
-        if not rows:
-            return
-        self._pending_reduce = []
-        if self._pending_group:
-            descs, self._pending_group = self._pending_group, []
-            blob = b''.join(d for d, _ in descs)
-            gtable = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.device)
-            self._keep.append(gtable)
-            blocks = (max(n for _, n in descs) + 7) // 8 * 8
-            e = self.b('dsnt_conv_wgrad_group', gtable, len(descs), blocks)
-            for u in self._pending_group_uses:
-                self.f16_uses.append((e, u))
-            self._pending_group_uses = []
-        table = torch.tensor(rows, dtype=torch.int64).to(self.device)
-        self._keep.append(table)
-        blocks = max((r[4] // 4 + (r[5] + 3) // 4 + 63) // 64 for r in rows)
-        self.b('dsnt_wgrad_reduce_all', table, len(rows), blocks)
-        for nm, args in self._post_reduce:          # gradients that are reduced in another layout than the parameter's
-            self.b(nm, *args)
-        self._post_reduce = []
+        self.bounds.emit_backward_zero(prep_pos)
+        if self.wgrads.pending:           # convolutions outside every parameter bucket (stand-alone modules)
+            self.wgrads.flush()
 
     def mark_bucket(self, k):
         """Forward position where parameter bucket k starts being used: in the (reversed) backward
         list the marker lands right after the last launch that writes bucket k's gradients."""
         self.cur_bucket = k
         if self.record:
-            def mark():
-                lane, self.lane = self.lane, self._flush_lane()
-                self.flush_wgrad()
-                # the marker carries the lane on which the bucket's gradients become complete: `run` calls the hook
-                # with that lane's stream current, so a collective started there orders itself after the reduction
-                self.bwd.append((None, k, 'bucket', self.lane))
-                self.lane = lane
-            self.on_backward(mark)
+            self.on_backward(lambda: self.wgrads.flush(bucket=k))
 
     def flush_point(self):
         """Forward position behind which (in backward: before which) the weight-gradient slabs written so far are reduced and the
@@ -598,132 +372,19 @@ class Tape:
         lane beside the next stage's launch-bound chain.  (On the hourglass the same cut inside the stem's bucket gains nothing:
         profiles/r05_ab_switches.txt box B.)"""
         if self.record and self.defer_reduce and self.flush_points:
-            def flush():
-                lane, self.lane = self.lane, self._flush_lane()
-                self.flush_wgrad()
-                self.lane = lane
-            self.on_backward(flush)
+            self.on_backward(self.wgrads.flush)
 
-    def _compile(self, lst):
-        """Record `lst` into a C launch list: (handle, bucket ids after each segment)."""
-        lib = self.lib
-        h = lib.dsnt_list_create()
-        if not h:
-            raise RuntimeError('dsnt_list_create failed')
-        marks = []
-        try:
-            if self.use_lanes:
-                for lane in range(1, self.n_lanes):
-                    self._rc(lib.dsnt_list_sync(h, 0, lane), 'dsnt_list_sync')
-            self._rc(lib.dsnt_list_begin(h), 'dsnt_list_begin')
-            try:
-                for fn, args, name, lane in lst:
-                    if fn is None:
-                        if name == 'sync':
-                            self._rc(lib.dsnt_list_sync(h, args[0], args[1]), 'dsnt_list_sync')
-                        else:
-                            marks.append((args, lane))
-                            lib.dsnt_list_mark(h)
-                        continue
-                    self._rc(fn(*args, C.c_void_p(lane)), name)          # recorded, not launched: `stream` = lane index
-            finally:
-                lib.dsnt_list_end()
-            if self.use_lanes:
-                for lane in range(1, self.n_lanes):
-                    self._rc(lib.dsnt_list_sync(h, lane, 0), 'dsnt_list_sync')
-            self._fuse_stages(h)
-        except Exception:
-            lib.dsnt_list_destroy(h)
-            raise
-        return h, marks
-
-    def _fuse_stages(self, h):
-        """Runs of small dependent launches of one lane (the 8 x 8 / 4 x 4 hourglass levels) -> persistent stage launches
-        (include/dsnt_hip.h: dsnt_list_fuse).  The tables and counters live in a tensor this tape owns."""
-        if not self.stage or self.device.type != 'cuda':
-            return
-        lib = self.lib
-        need = lib.dsnt_list_fuse_bytes(h, self.stage_min_run, self.stage_max_vgrid)
-        if need <= 0:
-            return
-        ws = torch.zeros((need + 63) // 64 * 64, dtype=torch.uint8, device=self.device)
-        self._keep.append(ws)
-        rc = lib.dsnt_list_fuse(h, C.c_void_p(ws.data_ptr()), ws.numel(), self.stage_min_run, self.stage_max_vgrid, self.stage_grid)
-        if rc < 0:
-            self._rc(rc, 'dsnt_list_fuse')
-        inside = C.c_int(0)
-        n = lib.dsnt_list_stages(h, C.byref(inside))
-        self.stage_census.append((n, inside.value))
+    stage_census = property(lambda self: self.fwd.stage_census + self.bwd.stage_census)
 
     def stage_errors(self):
         """Persistent stages of this tape's compiled lists whose barrier gave up (a workgroup never arrived) since they were
         built: 0 in a healthy process.  Synchronises the device (diagnostic / tests)."""
         torch.cuda.synchronize()
-        return sum(max(0, self.lib.dsnt_list_stage_errors(h)) for h, _ in self._clists.values())
-
-    def _rc(self, rc, name):
-        if rc != 0:
-            raise RuntimeError('%s failed (%d): %s' % (name, rc, self.lib.dsnt_last_error().decode()))
-
-    def __del__(self):
-        try:
-            for h, _ in self._clists.values():
-                self.lib.dsnt_list_destroy(h)
-        except Exception:
-            pass
+        return self.fwd.stage_errors() + self.bwd.stage_errors()
 
     def run(self, lst, bucket_hook=None, probe=None):
-        """Replay a launch list.  `probe(entry)` (diagnostics / tests) is called before every launch."""
-        main = torch.cuda.current_stream()
-        if self.use_lanes and self.side_stream is None:
-            # (stream priorities were tried — chain on high-priority streams, weight gradients on a normal one — and
-            # change nothing on this hardware)
-            self.side_stream = torch.cuda.Stream()
-            self.wgrad_stream = torch.cuda.Stream()
-            self.more_streams = tuple(torch.cuda.Stream() for _ in range(self.n_lanes - 3))
-        return self._run(lst, main, bucket_hook, probe)
-
-    def _run(self, lst, main, bucket_hook, probe):
-        streams = (main, self.side_stream, self.wgrad_stream) + self.more_streams
-        ptrs = tuple(st.cuda_stream if st is not None else 0 for st in streams)
-        if probe is None:
-            cl = self._clists.get(id(lst))
-            if cl is None:
-                cl = self._clists[id(lst)] = self._compile(lst)
-            h, marks = cl
-            arr = (C.c_void_p * len(ptrs))(*ptrs)
-            for seg in range(len(marks) + 1):
-                rc = self.lib.dsnt_list_replay(h, seg, arr, len(ptrs))
-                if rc != 0:
-                    torch.cuda.synchronize()
-                    self._rc(rc, 'dsnt_list_replay')
-                if seg < len(marks) and bucket_hook is not None:
-                    k, lane = marks[seg]
-                    with torch.cuda.stream(streams[lane]):
-                        bucket_hook(k)
-            return
-        for st in streams[1:] if self.use_lanes else ():
-            st.wait_stream(main)
-        for entry in lst:
-            fn, args, name, lane = entry
-            if fn is None:
-                if name == 'sync':
-                    src, dst, ev = args
-                    ev.record(streams[src])
-                    streams[dst].wait_event(ev)
-                elif bucket_hook is not None:
-                    with torch.cuda.stream(streams[lane]):
-                        bucket_hook(args)
-                continue
-            if probe is not None:
-                probe(entry)
-            rc = fn(*args, ptrs[lane])
-            if rc != 0:
-                torch.cuda.synchronize()
-                raise RuntimeError('%s failed (%d): %s' % (
-                    name, rc, _lib.load().dsnt_last_error().decode()))
-        for st in streams[1:] if self.use_lanes else ():
-            main.wait_stream(st)
+        """Replay one of the tape's lists.  `probe(entry)` (diagnostics / tests) is called before every launch."""
+        lst.replay(bucket_hook, probe)
 
     # ------------------------------------------------------------------ gradient plumbing
     def add_later(self, a, g, g_amax=None):
@@ -744,48 +405,40 @@ class Tape:
             self._ident = (torch.ones(n, device=self.device), torch.zeros(n, device=self.device))
         return self._ident
 
-    def take_base(self):
-        """After grad_target(..., base_ok=True): the tensor the writer has to add to its value (or None)."""
-        b, self._writer_base = self._writer_base, None
-        return b
-
-    def grad_target(self, a, amax=False, take_add=False, base_ok=False):
+    def grad_target(self, a, amax=False, take_add=False):
         """(buffer, accumulate flag) for a kernel about to write a's gradient.  `amax`: the kernel leaves max|written|
         in a.grad_amax (fp16x3 operand bound).  Every writer rewrites the whole tensor, so the slot stays a valid bound
         while all writers since its creation report into it; a writer that cannot invalidates it."""
+        buf, acc, base = self.grad_target_base(a, amax, take_add)
+        if base is not None:        # this writer cannot read the base itself: it finds a copy in place
+            self.b_amax('dsnt_axpy', base, buf, 1.0, 0, base.numel(), amax=a.grad_amax)
+            acc = 1
+        return buf, acc
+
+    def grad_target_base(self, a, amax=False, take_add=False):
+        """`grad_target` for a writer that can add a third tensor in its own pass: (buffer, accumulate flag, base).  base (or
+        None): a's gradient continues one it does not own — base + this writer's value go into the buffer, a NEW one."""
         if a.pending_apply is not None:          # a BatchNorm backward left to a's producer, and now a second contribution
             self.materialize_apply(a)
         if a.pending_add is not None and not take_add:
             self._flush_add(a)                   # this writer cannot add a second tensor in its pass: the separate launch after all
-        self._writer_base = None
         if a.base is not None:
-            # a's gradient continues one it does not own: base + this writer's value go into a NEW buffer.  A writer that can
-            # read the base itself (base_ok: `take_base`) does that in its own pass; any other finds a copy in place
-            base, base_amax, a.base, a.base_amax = a.base, a.base_amax, None, None
+            base, a.base, a.base_amax = a.base, None, None
             a._grad, a.grad_shared = self.empty(a.N, a.H, a.W, a.C), False
-            a.grad_amax = self.amax_slot() if (self.use_f16x3 and amax) else None
-            if base_ok:
-                self._writer_base = base
-                return a._grad, 0
-            if a.grad_amax is not None:
-                self.b('dsnt_axpy_amax', base, a._grad, 1.0, 0, base.numel(), a.grad_amax)
-            else:
-                self.b('dsnt_axpy', base, a._grad, 1.0, 0, base.numel())
-            return a._grad, 1
+            a.grad_amax = self.bounds.amax_slot() if (self.use_f16x3 and amax) else None
+            return a._grad, 0, base
         acc = 1
         if a.grad is None:
             a.grad = self.empty(a.N, a.H, a.W, a.C)
             acc = 0
-        elif a.grad.data_ptr() in self._wgrad_lane_reads:
-            self._wgrad_lane_reads.discard(a.grad.data_ptr())
-            self.release_wgrads()                            # a held-back launch that reads it must be on the list first
-            self.sync_bwd(self.wgrad_lane, self.lane)        # a weight gradient on its own lane still reads this buffer
+        else:
+            self.wgrads.before_write(a.grad)
         if self.use_f16x3 and amax:
             if a.grad_amax is None:
-                a.grad_amax = self.amax_slot()
+                a.grad_amax = self.bounds.amax_slot()
         else:
             a.grad_amax = None
-        return a.grad, acc
+        return a.grad, acc, None
 
     def grad_identity(self, a, g, donate, g_amax=None):
         """a.grad (+)= g.  With `donate`, g's buffer is handed over when a has no gradient yet
@@ -800,10 +453,7 @@ class Tape:
             a.grad_amax = g_amax
             return True
         buf, acc = self.grad_target(a, amax=True)
-        if a.grad_amax is not None:
-            self.b('dsnt_axpy_amax', g, buf, 1.0, acc, g.numel(), a.grad_amax)
-        else:
-            self.b('dsnt_axpy', g, buf, 1.0, acc, g.numel())
+        self.b_amax('dsnt_axpy', g, buf, 1.0, acc, g.numel(), amax=a.grad_amax)
         return False
 
     # ------------------------------------------------------------------ ops
@@ -823,7 +473,7 @@ class Tape:
 
     def norm(self, x, bn, relu=True):
         """BatchNorm bookkeeping for x under `bn`: finalise kernel -> scale/shift vectors."""
-        if os.environ.get('DSNT_DEBUG_NO_RELU'):   # smooth network for exact gradient checks
+        if self.no_relu:
             relu = False
         n = Normed()
         n.x, n.bn, n.relu = x, bn, relu
@@ -832,19 +482,13 @@ class Tape:
         n.pending = None
         n.lane = self.lane      # the lane whose launches write scale / shift: every consumer must run there (`check_lane`)
         if self.training:
-            part, tiles = self.ensure_stats(x)
-            if self.fuse_finalize and bn.C <= 256 and tiles * bn.C <= self.fuse_finalize_max:
-                # few tiles (the 8x8 / 4x4 levels): the launch that CONSUMES this BatchNorm finalises it in its prologue
-                # (`conv`); any other first reader materialises it with the usual launch (`materialize`)
-                n.pending = (part, tiles)
-            else:
-                self.f('dsnt_bn_finalize', part, tiles, x.M, bn.C, bn.gamma, bn.beta, bn.rmean, bn.rvar,
-                       bn.momentum, bn.eps, 1, n.mean, n.invstd, n.scale, n.shift)
+            n.pending = self.ensure_stats(x)
+            # few tiles (the 8x8 / 4x4 levels): the launch that CONSUMES this BatchNorm finalises it in its prologue
+            # (`conv`); any other first reader materialises it with the usual launch (`materialize`), as do many tiles here
+            if not (self.fuse_finalize and bn.C <= 256 and n.pending[1] * bn.C <= self.fuse_finalize_max):
+                self.materialize(n)
         else:
-            bits = struct.unpack('<I', struct.pack('<f', float(bn.eps)))[0]
-            self._eval_bn_rows.append([bn.gamma.data_ptr(), bn.beta.data_ptr(), bn.rmean.data_ptr(), bn.rvar.data_ptr(),
-                                       n.mean.data_ptr(), n.invstd.data_ptr(), n.scale.data_ptr(), n.shift.data_ptr(),
-                                       bn.C, bits])
+            self.bounds.eval_bn(n)
         return n
 
     def check_lane(self, n):
@@ -878,12 +522,8 @@ class Tape:
         ap, x.pending_apply = x.pending_apply, None
         n = ap['n']
         buf, acc = self.grad_target(x, amax=True)
-        if x.grad_amax is not None:
-            self.b('dsnt_bn_act_bwd_apply_amax', ap['dz'], x.buf, n.scale, n.shift, n.mean, n.invstd, ap['coef'], 0,
-                   buf, acc, x.M, n.bn.C, x.grad_amax)
-        else:
-            self.b('dsnt_bn_act_bwd_apply', ap['dz'], x.buf, n.scale, n.shift, n.mean, n.invstd, ap['coef'], 0,
-                   buf, acc, x.M, n.bn.C)
+        self.b_amax('dsnt_bn_act_bwd_apply', ap['dz'], x.buf, n.scale, n.shift, n.mean, n.invstd, ap['coef'], 0,
+                    buf, acc, x.M, n.bn.C, amax=x.grad_amax)
 
     def _norm_backward(self, n, da, reduced=None, finalised=False, dz_amax=None):
         """Given da = dL/d relu(bn(x)), accumulate dx into n.x.grad and dgamma/dbeta.  With
@@ -907,7 +547,7 @@ class Tape:
             acc_p = 1 if bn.uses > 0 else 0
             bn.uses += 1
             coef = self.empty(2 * bn.C)          # lives until the producer's backward
-            bound = self.amax_slot()
+            bound = self.bounds.amax_slot()
             self.b('dsnt_bn_bwd_finalize_bound', part, tiles, x.M, bn.C, bn.ggamma, bn.gbeta, acc_p, coef, n.scale,
                    dz_amax, bound)
             x.pending_apply = dict(dz=da, n=n, coef=coef, bound=bound, dz_amax=dz_amax)
@@ -922,8 +562,7 @@ class Tape:
             bn.uses += 1
             if not fused:
                 self.b('dsnt_bn_bwd_finalize', part, tiles, x.M, bn.C, bn.ggamma, bn.gbeta, acc_p | (2 if frozen else 0), coef)
-        buf, acc = self.grad_target(x, amax=True, base_ok=True)
-        base = self.take_base()         # x's gradient continues one it does not own: dx = base + value (`conv`, defer_res)
+        buf, acc, base = self.grad_target_base(x, amax=True)    # (base: dx = base + value, `conv`'s defer_res)
         if fused:
             # few tiles: the apply launch sums them itself in its prologue (coef) and writes dgamma / dbeta
             coef = self.empty(2 * bn.C)          # private: the launch writes it (a shared scratch could still be in use)
@@ -936,12 +575,9 @@ class Tape:
         elif base is not None:
             self.b('dsnt_bn_act_bwd_apply_base', da, x.buf, n.scale, n.shift, n.mean, n.invstd, coef, relu,
                    base, buf, x.M, bn.C, x.grad_amax)
-        elif x.grad_amax is not None:
-            self.b('dsnt_bn_act_bwd_apply_amax', da, x.buf, n.scale, n.shift, n.mean, n.invstd, coef, relu,
-                   buf, acc, x.M, bn.C, x.grad_amax)
         else:
-            self.b('dsnt_bn_act_bwd_apply', da, x.buf, n.scale, n.shift, n.mean, n.invstd, coef, relu,
-                   buf, acc, x.M, bn.C)
+            self.b_amax('dsnt_bn_act_bwd_apply', da, x.buf, n.scale, n.shift, n.mean, n.invstd, coef, relu,
+                        buf, acc, x.M, bn.C, amax=x.grad_amax)
 
     # ------------------------------------------------------------------ convolution
     def conv(self, src, p, res1=None, res2=None, want_stats=False, need_input_grad=True, name=''):
@@ -972,7 +608,7 @@ class Tape:
 
     def _operand_bound(self, c):
         """The bound slot of c's A operand as its producer leaves it (None if it cannot); the first call claims the producer's tail."""
-        return self.operand_amax_bn(c.src) if c.normed else self.operand_amax(c.x)
+        return self.bounds.operand_amax_bn(c.src) if c.normed else self.bounds.operand_amax(c.x)
 
     @staticmethod
     def _bn_epilogue(x, n):
@@ -992,15 +628,6 @@ class Tape:
         that produced x (`fold_ok`) — a buffer that outlives this op's launches."""
         n = x.M * x.C
         return self.empty(n) if private else self.scratch('da', n).view(-1)[:n]
-
-    def _reduce_row(self, ws, p, splits):
-        self._pending_reduce.append([ws.data_ptr(), p.gw.data_ptr(), p.gb.data_ptr() if p.gb is not None else 0,
-                                     splits, p.Cout * p.R * p.S * p.Cin, p.Cout, 0])
-
-    def _struct_bytes(self, name, nb):
-        """Algorithmic bytes of the tensors a backward launch names inside a struct (`_emit` counts the plain arguments)."""
-        self.bytes_bwd += nb
-        self.bytes_by_name[name] = self.bytes_by_name.get(name, 0) + nb
 
     def _conv_forward(self, c, want_stats):
         """Choose c's forward kernel — fwd1 / stem4 / stream or tiled fp16x3 / bf16x6 / fp32 with the BatchNorm finalised in its
@@ -1035,7 +662,7 @@ class Tape:
         r1 = c.res1.buf if c.res1 is not None else None
         r2 = res2.buf if res2 is not None else None
         if self.use_f16x3 and self.training and normed:
-            self.f16_bn_bound(src)              # also for the weight gradient of convs whose forward is not fp16x3
+            self.bounds.f16_bn_bound(src)       # also for the weight gradient of convs whose forward is not fp16x3
         # fp16x3 needs a bound of the A operand: train-mode BatchNorm parameters, or the producer's max|x| for a raw x
         if can16 and not early:
             x_amax = self._operand_bound(c)
@@ -1045,8 +672,8 @@ class Tape:
             self.materialize(src)
         if use16:
             st = self.stream_ok(p, g, y.M, res2)
-            self.f16_weights(p, stream=st)
-            ab = self.f16_bn_bound(src) if (normed and self.training) else x_amax
+            self.bounds.f16_weights(p, stream=st)
+            ab = self.bounds.f16_bn_bound(src) if (normed and self.training) else x_amax
             if f1:
                 e = self.f('dsnt_conv1x1_fwd_f16x3', x.buf, p.wq16, p.wq_stride, p.wb, ab, p.b, y.buf, sc, sh, relu | f1_shr, r1,
                            part, g, tail)
@@ -1081,9 +708,7 @@ class Tape:
         x, y, p, g = c.x, c.y, c.p, c.g
         c.slot = c.slot_k = None
         if c.need_input_grad and self.param_arena is not None:
-            c.slot, c.slot_k = self.dgrad_total, len(self.dgrad_slots)
-            self.dgrad_slots.append((p, c.slot))
-            self.dgrad_total += (p.w.numel() + 7) // 8 * 8
+            c.slot, c.slot_k = self.bounds.dgrad_slot(p)
         c.bucket = self.cur_bucket
         # the whole backward of this convolution as ONE launch (csrc/bwd1.hip): 1x1 behind a train-mode BatchNorm, both
         # operand bounds known on the device
@@ -1108,8 +733,8 @@ class Tape:
         """Emit c's backward: the one-launch 1x1 form, or weight gradient and data gradient; then the residual inputs' gradients."""
         y = c.y
         gy, ap = y.grad, y.pending_apply
-        fused = c.fuse1 and self.dgrad_planes16 is not None
-        fold3 = bool(c.fold3_ok and ap is not None and gy is None and self.dgrad_planes16 is not None and c.need_input_grad and
+        fused = c.fuse1 and self.bounds.dgrad_planes16 is not None
+        fold3 = bool(c.fold3_ok and ap is not None and gy is None and self.bounds.dgrad_planes16 is not None and c.need_input_grad and
                      ap['bound'] is not None)
         if ap is not None and (not fused or gy is not None) and not fold3:
             self.materialize_apply(y)
@@ -1140,12 +765,9 @@ class Tape:
         nw = p.w.numel()
         shr = self._share()
         nsp = self.lib.dsnt_conv1x1_bwd_splits(C.byref(g), shr)
-        ws = self.empty(self.lib.dsnt_conv1x1_bwd_ws_floats(C.byref(g), shr))      # lives until the bucket's reduction
-        self._ws_ptrs.add(ws.data_ptr())
-        wd = self.dgrad_f32[c.slot:c.slot + nw]
-        wq16 = self.dgrad_planes16[c.slot:c.slot + nw]
-        wbd = self.dgrad_bounds[64 * c.slot_k:64 * c.slot_k + 64]
-        self._f16_dw_rows.append([wd.data_ptr(), wq16.data_ptr(), wbd.data_ptr(), nw, self.dgrad_total, 0, 0])
+        ws = self.wgrads.slab(p, self.lib.dsnt_conv1x1_bwd_ws_floats(C.byref(g), shr), nsp)
+        wd, wq16, wbd = self.bounds.dgrad_f16(c.slot, c.slot_k, nw)
+        total = self.bounds.dgrad_total
         if ap is not None:
             aps, applied = self._bn_apply(y, ap)
             dy, gb = ap['dz'], ap['bound']
@@ -1155,25 +777,25 @@ class Tape:
             aps, dy, gb = None, gy, y.grad_amax
             grad = dict(g=dy, g_bound=gb)
         if c.normed:
-            ab = self.f16_bn_bound_bwd(src)
+            ab = self.bounds.f16_bn_bound_bwd(src)
             # (the BatchNorm in front of THIS convolution may in turn be left to the 1x1 convolution before it)
             fold = self.fold_ok(src)
             dz = self._dz_buffer(x, fold)
-            dz_amax = self.amax_slot() if fold else None
+            dz_amax = self.bounds.amax_slot() if fold else None
             part = self.scratch('bnpart', nsp * 2 * x.C).view(-1)
-            e = self.b(name, self._bn_epilogue(x, src), dy, aps, wq16, self.dgrad_total, wbd, ab, gb, dz, part, ws, dz_amax, shr, g)
+            e = self.b(name, self._bn_epilogue(x, src), dy, aps, wq16, total, wbd, ab, gb, dz, part, ws, dz_amax, shr, g)
         else:
             # no BatchNorm in front of it (projection shortcuts, the `fc` convolutions): dL/dx itself is written, or
             # added to what x's gradient holds already
             ab = c.x_amax
             buf, acc = self.grad_target(x, amax=True)
-            e = self.b(name, self._bn_epilogue(x, None), dy, None, wq16, self.dgrad_total, wbd, ab, gb, buf, None, ws,
+            e = self.b(name, self._bn_epilogue(x, None), dy, None, wq16, total, wbd, ab, gb, buf, None, ws,
                        x.grad_amax, shr | acc, g)
-        self._struct_bytes(name, 4 * (x.buf.numel() + (y.buf.numel() if ap is not None else 0)))
+        # (the tensors the launch names inside a struct: `emit` counts the plain arguments)
+        self.bwd.count(name, 4 * (x.buf.numel() + (y.buf.numel() if ap is not None else 0)))
         u = dict(kind='bwd1', name=c.name, x=x.buf, sc=c.sc, sh=c.sh, relu=c.relu, a_bound=ab, w=wd, w_bound=wbd)
         u.update(grad)
         self.f16_uses.append((e, u))
-        self._reduce_row(ws, p, nsp)
         if c.normed:
             self._norm_backward(src, dz, reduced=(part, nsp), finalised=False, dz_amax=dz_amax)
 
@@ -1181,46 +803,21 @@ class Tape:
         """Parameter gradients of c (flat arena, overwritten every step).  Returns (the lane they run on, whether dL/dy stays
         intact for them as the `base` of the residual inputs' gradients)."""
         p, g = c.p, c.g
-        cur = wl = self.lane
-        # the weight gradient feeds nothing downstream in backward: run it on its own lane so the data-gradient chain never waits
-        # for it.  DSNT_X_WGRAD_LANE_ROWS > 0: only the large convolutions of the chain's lanes whose dY nobody writes again (no
-        # residual inputs: the gradient buffer is not donated onwards) — their weight gradients then fill the chip while the
-        # main lane walks the launch-bound low-resolution levels
-        if self.wgrad_lane is not None and (self.wgrad_lane_rows == 0 or (
-                cur in self.chain_lanes and c.res1 is None and c.res2 is None and g.N * g.Ho * g.Wo >= self.wgrad_lane_rows)):
-            wl = self.wgrad_lane
-        hold = wl != cur and self._release_left > 0
-        if hold:
-            listed, self.bwd = self.bwd, self._held
-        self.sync_bwd(cur, wl)
-        self.lane = wl
-        if wl != cur:
-            # gy may be donated onwards and accumulated into by a later launch of another lane: that writer waits
-            # for the weight-gradient lane first (grad_target)
-            self._wgrad_lane_reads.add(gy.data_ptr())
-        # DSNT_WGRAD_SHARE_CHIP (-0.2 ms): one workgroup per CU beside the chain — except for the first convolution of the
-        # network (no data gradient: it is the LAST launch of backward and has the chip to itself)
-        share = 2 if (wl != cur and c.need_input_grad) else 0
-        # DSNT_WGRAD_NARROW for the hourglass stacks' 3x3 weight gradients: the lane has slack there (the 1x1 weight
-        # gradients left it), the stem's bucket is the tail of backward and keeps the wider plan
-        if share and self.wgrad_narrow in ('1', {0: '2'}.get(c.bucket, '3')):
-            share |= 4
+        cur = self.lane
         w6 = self.use_bf16x6 and bool(self.lib.dsnt_conv_wgrad_bf16x6_ok(C.byref(g)))
         defer_res = False
-        if self.defer_reduce:
-            defer_res = self._conv_wgrad_slab(c, gy, share, w6, wl == cur)
-        else:
-            ws = self.scratch('wgrad', self.lib.dsnt_conv_wgrad_ws_floats(C.byref(g)))
-            self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', c.x.buf, c.sc, c.sh, c.relu, gy, ws, p.gw, p.gb, 0, g)
-            if p.post_reduce is not None:      # the stem's space-to-depth gradient -> the parameter's 7x7 layout
-                self.b(p.post_reduce[0], *p.post_reduce[1])
-        self.lane = cur
-        if hold:
-            self.bwd = listed
+        with self.wgrads.placed(c, gy) as (wl, share):
+            if self.defer_reduce:
+                defer_res = self._conv_wgrad_slab(c, gy, share, w6, wl == cur)
+            else:
+                ws = self.scratch('wgrad', self.lib.dsnt_conv_wgrad_ws_floats(C.byref(g)))
+                self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', c.x.buf, c.sc, c.sh, c.relu, gy, ws, p.gw, p.gb, 0, g)
+                if p.post_reduce is not None:      # the stem's space-to-depth gradient -> the parameter's 7x7 layout
+                    self.b(p.post_reduce[0], *p.post_reduce[1])
         return wl, defer_res
 
     def _conv_wgrad_slab(self, c, gy, share, w6, on_chain):
-        """c's weight gradient into a slab of its own that the bucket's one reduction launch sums (`flush_wgrad`): a launch here,
+        """c's weight gradient into a slab of its own that the bucket's one reduction launch sums (`WgradQueue.flush`): a launch here,
         or — low-resolution convolutions — a descriptor for the bucket's grouped launch.  Returns `defer_res`."""
         x, y, p, g, normed, sc, sh, relu = c.x, c.y, c.p, c.g, c.normed, c.sc, c.sh, c.relu
         # deferred to the bucket's grouped launch: x, gy and the BN vectors are written once per
@@ -1232,20 +829,18 @@ class Tape:
         # ... or, WITH residual inputs (conv3 of the low-resolution Bottlenecks): dL/dy is not donated to them but
         # handed over as the `base` their own gradient continues out of place, and so stays intact as well
         residuals = [r for r in (c.res1, c.res2) if r is not None]
-        defer_res = bool(groupable and residuals and self.share_grads and self.defer_res and all(
-            r._grad is None and r.base is None and r.pending_apply is None and r.pending_add is None for r in residuals))
+        defer_res = bool(groupable and residuals and self.share_grads and self.defer_res and all(r.untouched for r in residuals))
         grouped = groupable and (not residuals or defer_res)
         # fp16x3: both operand bounds exist (A: train-mode BN parameters, dY: one bn-backward apply wrote it)
         w16 = w6 and self.use_f16x3 and (normed or c.x_amax is not None) and y.grad_amax is not None
-        ab = (self.f16_bn_bound_bwd(c.src) if normed else c.x_amax) if w16 else None
+        ab = (self.bounds.f16_bn_bound_bwd(c.src) if normed else c.x_amax) if w16 else None
         if w16 and not grouped:
             # dsnt_conv_wgrad_f16x3 cuts the pixels of a 3x3 convolution into its own slabs (halo kernel)
             nws = self.lib.dsnt_conv_wgrad_f16x3_ws_floats(C.byref(g), share)
             splits = self.lib.dsnt_conv_wgrad_f16x3_splits(C.byref(g), share)
         else:
             nws, splits = self.lib.dsnt_conv_wgrad_ws_floats(C.byref(g)), self.lib.dsnt_conv_wgrad_splits(C.byref(g))
-        ws = self.empty(nws)         # lives until the bucket's reduction
-        self._ws_ptrs.add(ws.data_ptr())
+        ws = self.wgrads.slab(p, nws, splits)
         use = dict(kind='wgrad', name=c.name, x=x.buf, sc=sc, sh=sh, relu=relu, a_bound=ab, g=gy, g_bound=y.grad_amax)
         if grouped:
             desc = C.create_string_buffer(self.lib.dsnt_conv_wgrad_desc_bytes())
@@ -1253,28 +848,24 @@ class Tape:
             if w16:
                 nblk = self.lib.dsnt_conv_wgrad_desc_f16x3(_lib.ptr(x.buf), _lib.ptr(gsc), _lib.ptr(gsh), relu, _lib.ptr(gy),
                                                            _lib.ptr(ws), _lib.ptr(ab), _lib.ptr(y.grad_amax), C.byref(g), desc)
-                self._pending_group_uses.append(use)
             else:
                 nblk = self.lib.dsnt_conv_wgrad_desc(_lib.ptr(x.buf), _lib.ptr(gsc), _lib.ptr(gsh), relu, _lib.ptr(gy),
                                                      _lib.ptr(ws), C.byref(g), desc)
             if nblk <= 0:
                 raise RuntimeError('dsnt_conv_wgrad_desc failed: %s' % self.lib.dsnt_last_error().decode())
-            self._pending_group.append((desc.raw, nblk))
+            self.wgrads.group(desc.raw, nblk, use if w16 else None)
         elif w16:
             e = self.b('dsnt_conv_wgrad_f16x3', x.buf, sc, sh, relu, gy, ws, None, None, share, ab, y.grad_amax, g)
             self.f16_uses.append((e, use))
         else:
             self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', x.buf, sc, sh, relu, gy, ws, None, None,
                    share if w6 else 0, g)
-        if p.post_reduce is not None:
-            self._post_reduce.append(p.post_reduce)
-        self._reduce_row(ws, p, splits)
         return defer_res
 
     def _conv_dgrad_operands(self, c, gy):
         """What c's data gradient launches on: the geometry (`c.gd`, or — a strided convolution the phase kernel of csrc/dgrad_up.hip
         refuses — the stride-1 one over a zero-stuffed dL/dy) and the re-packed weights in the precision the launch takes."""
-        x, p, g = c.x, c.p, c.g
+        x, p, g, bd = c.x, c.p, c.g, self.bounds
         d = _Dgrad()
         nw = p.w.numel()
         pad_d = p.dil * (p.R - 1) - p.pad
@@ -1291,8 +882,8 @@ class Tape:
             d.gd = ConvGeom(x.N, Hs, Ws, p.Cout, x.H, x.W, p.Cin, p.R, p.S, 1, pad_d, p.dil)
         d.wq = d.wq_stride = d.wq16 = d.wbd = d.d_stream = None
         if c.slot is not None:
-            d.wd = self.dgrad_f32[c.slot:c.slot + nw]
-            d.wq, d.wq_stride = self.dgrad_planes[c.slot:c.slot + nw], self.dgrad_total
+            d.wd = bd.dgrad_f32[c.slot:c.slot + nw]
+            d.wq, d.wq_stride = bd.dgrad_planes[c.slot:c.slot + nw], bd.dgrad_total
             d.d6 = d.gd is not None and self._use6(d.gd)
         else:       # stand-alone use without a parameter arena
             d.wd = self.scratch('wdgrad', nw)
@@ -1302,14 +893,11 @@ class Tape:
                 d.wq, d.wq_stride = self.scratch('wdgrad6', 3 * nw, torch.bfloat16, 8), nw
                 self.b('dsnt_split_bf16x3', d.wd, d.wq, nw)
         d.g_amax = c.y.grad_amax if (self.use_f16x3 and p.stride == 1) else None
-        d.d16 = d.d6 and d.g_amax is not None and c.slot is not None and self.dgrad_planes16 is not None
+        d.d16 = d.d6 and d.g_amax is not None and c.slot is not None and self.bounds.dgrad_planes16 is not None
         if d.d16:
-            d.wq16 = self.dgrad_planes16[c.slot:c.slot + nw]
-            d.wbd = self.dgrad_bounds[64 * c.slot_k:64 * c.slot_k + 64]
             # (the data gradient's filter is [Cin][3][3][Cout]: its "Cout" is this convolution's Cin)
             d.d_stream = self.stream_ok(p, d.gd, x.M, None)
-            self._f16_dw_rows.append([d.wd.data_ptr(), d.wq16.data_ptr(), d.wbd.data_ptr(), nw, self.dgrad_total] +
-                                     ([p.Cin, p.Cout] if d.d_stream else [0, 0]))
+            _, d.wq16, d.wbd = bd.dgrad_f16(c.slot, c.slot_k, nw, (p.Cin, p.Cout) if d.d_stream else (0, 0))
         return d
 
     def _conv_dgrad_launch(self, c, d, out, res, part=None, bnb=None, tail=None):
@@ -1317,7 +905,7 @@ class Tape:
         if d.native:
             self.b('dsnt_conv_dgrad_strided', d.gsrc, d.wd, out, res, part, c.g, bnb, tail)
         elif d.d16:
-            e = self.b('dsnt_conv_fwd_f16x3_stream' if d.d_stream else 'dsnt_conv_fwd_f16x3_ex', d.gsrc, d.wq16, self.dgrad_total,
+            e = self.b('dsnt_conv_fwd_f16x3_stream' if d.d_stream else 'dsnt_conv_fwd_f16x3_ex', d.gsrc, d.wq16, self.bounds.dgrad_total,
                        d.wbd, d.g_amax, None, out, None, None, self._share(d.d_stream or c.p.R == 1), res, None, part, d.gd, bnb, tail)
             self.f16_uses.append((e, dict(kind='dgrad', name=c.name, g=d.gsrc, g_bound=d.g_amax, w=d.wd, w_bound=d.wbd)))
         elif d.d6:
@@ -1334,8 +922,7 @@ class Tape:
         d = self._conv_dgrad_operands(c, gy)
         if not c.normed:
             # (d6: the large-tile kernels; their epilogue can leave max|written gradient| as the next bound)
-            buf, acc = self.grad_target(x, amax=bool(d.d6 or d.native), base_ok=True)
-            base = self.take_base()         # (x's gradient continues one it does not own: the residual operand)
+            buf, acc, base = self.grad_target_base(x, amax=bool(d.d6 or d.native))      # (base: the residual operand)
             tl = None
             if x.grad_amax is not None:
                 tl = BnTail()
@@ -1357,14 +944,14 @@ class Tape:
         bnb = self._bn_epilogue(x, src)
         tl, dz_amax = None, None
         if fold:
-            tl, dz_amax = BnTail(), self.amax_slot()
+            tl, dz_amax = BnTail(), self.bounds.amax_slot()
             tl.amax = dz_amax.data_ptr()
         if ap is not None:
             assert d.d16 and d.d_stream and not d.native
             name = 'dsnt_conv_dgrad_f16x3_stream_apply'
             aps, applied = self._bn_apply(y, ap)
-            e = self.b(name, ap['dz'], aps, gy, d.wq16, self.dgrad_total, d.wbd, ap['bound'], dz, part, self._share(), d.gd, bnb, tl)
-            self._struct_bytes(name, 4 * y.buf.numel())
+            e = self.b(name, ap['dz'], aps, gy, d.wq16, self.bounds.dgrad_total, d.wbd, ap['bound'], dz, part, self._share(), d.gd, bnb, tl)
+            self.bwd.count(name, 4 * y.buf.numel())
             self.f16_uses.append((e, dict(kind='dgrad', name=c.name, w=d.wd, w_bound=d.wbd, g_bound=ap['bound'], g_apply=applied)))
         else:
             self._conv_dgrad_launch(c, d, dz, None, part, bnb, tl)
@@ -1387,7 +974,7 @@ class Tape:
                 # the buffer went to the first residual input; this one has a single consumer, so its gradient is dL/dy
                 # and nothing else, and its producer only READS it (it gives no buffer away): shared, not copied.  Every
                 # later writer of the buffer comes after that reader in lane order, or waits for the lane that reads
-                # (`_wgrad_lane_reads` is keyed by the buffer)
+                # (`WgradQueue.before_write` goes by the buffer)
                 r.grad, r.grad_amax, r.grad_shared = gy, y.grad_amax, True
             else:
                 donated = self.grad_identity(r, gy, donate=not donated, g_amax=y.grad_amax) or donated
@@ -1437,10 +1024,8 @@ class Tape:
                     # a second gradient of x that arrived in a buffer of its own (the skip branch's: Hourglass._level) rides along
                     assert acc == 1
                     self.b('dsnt_maxpool2_bwd_add', y.grad, idx, buf, acc, add[0], x.N, x.H, x.W, x.C, x.grad_amax)
-                elif x.grad_amax is not None:
-                    self.b('dsnt_maxpool2_bwd_amax', y.grad, idx, buf, acc, x.N, x.H, x.W, x.C, x.grad_amax)
                 else:
-                    self.b('dsnt_maxpool2_bwd', y.grad, idx, buf, acc, x.N, x.H, x.W, x.C)
+                    self.b_amax('dsnt_maxpool2_bwd', y.grad, idx, buf, acc, x.N, x.H, x.W, x.C, amax=x.grad_amax)
             self.on_backward(backward)
         return y
 
@@ -1464,7 +1049,7 @@ class Tape:
         y = self.act(x.N, x.H, x.W, x.C, name)
         x.uses += 1
         skip.uses += 1
-        if os.environ.get('DSNT_DEBUG_NO_RELU'):
+        if self.no_relu:
             relu = False
         self.materialize(n)
         self.f('dsnt_bn_add_act_fwd', x.buf, n.scale, n.shift, skip.buf, 1 if relu else 0, y.buf, x.M, x.C)
@@ -1473,8 +1058,7 @@ class Tape:
                 # the block input's gradient can START as dz and continue out of place (below): dz is then handed out as a `base`
                 # that later launches — possibly of another lane, possibly held back — still read, so it gets a buffer of its own
                 # (a shared scratch would be overwritten by the next block's backward with nothing ordering its readers first)
-                share = bool(self.share_grads and skip._grad is None and skip.base is None and skip.pending_apply is None and
-                             skip.pending_add is None)
+                share = bool(self.share_grads and skip.untouched)
                 if relu:
                     # the ReLU mask (from the stored y), dz and the BatchNorm's two reductions in ONE pass
                     dz = (self.empty(x.M * x.C) if share else self.scratch('dz_tail', x.M * x.C).view(-1)[:x.M * x.C])
@@ -1485,7 +1069,7 @@ class Tape:
                 else:
                     dz = y.grad
                     self._norm_backward(n, dz)
-                if share and skip._grad is None and skip.base is None:
+                if share and skip.untouched:
                     # the block input's gradient starts as dz and continues out of place (the data gradient of conv1 adds it as its
                     # residual operand): no copy
                     skip.base, skip.base_amax = dz, None
@@ -1501,18 +1085,13 @@ class Tape:
         out.gives_away = True                   # dL/d out's buffer becomes dL/d up in backward
         self._f_with_stats('dsnt_upsample2_add_fwd', out, (up.buf, low.buf, out.buf), (up.N, up.H, up.W, up.C))
         if self.record:
-            point = self.wgrad_lane is not None and low.M <= self.release_rows
-            self._release_total += point
+            point = self.wgrads.release_point(low.M)
 
             def backward():
                 if point:
-                    self._release_left -= 1
-                    self.release_wgrads()
+                    self.wgrads.pass_release_point()
                 buf, acc = self.grad_target(low, amax=True)
-                if low.grad_amax is not None:
-                    self.b('dsnt_upsample2_bwd_amax', out.grad, buf, acc, up.N, up.H, up.W, up.C, low.grad_amax)
-                else:
-                    self.b('dsnt_upsample2_bwd', out.grad, buf, acc, up.N, up.H, up.W, up.C)
+                self.b_amax('dsnt_upsample2_bwd', out.grad, buf, acc, up.N, up.H, up.W, up.C, amax=low.grad_amax)
                 self.grad_identity(up, out.grad, donate=True, g_amax=out.grad_amax)
             self.on_backward(backward)
         return out
@@ -1565,8 +1144,8 @@ class Tape:
         # the re-packed filter and its planes: one tiny launch on the MAIN lane right before the convolution (the table-driven
         # preparation of all other weights runs on the side lane beside it)
         self.f('dsnt_s2d_weights_prep', p.w, w2, p2.wq16, p2.wq, p2.wb, p.Cout)
-        self._f16_w_seen.add(p2.wq16.data_ptr())    # (prepared here, not by the table-driven launch)
+        self.bounds.prepared_elsewhere(p2.wq16)     # (here, not by the table-driven launch)
         mark = len(self.fwd)
         y = self.conv(xs, p2, want_stats=True, need_input_grad=False, name=name)
-        self._prep_exempt.update(id(e) for e in self.fwd[mark:])
+        self.bounds.exempt(self.fwd[mark:])
         return y

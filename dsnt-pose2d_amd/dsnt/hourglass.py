@@ -172,8 +172,7 @@ class Program:
         self.in_flight = False      # a forward of this program is waiting for its backward (hourglass._Run)
         self.owner = None           # ... and this is that forward's token
         dev = arena.device
-        tape = Tape(dev, training, record)
-        tape.want_input_grad = bool(input_grad and record)     # the stem then keeps its data gradient (no space-to-depth form)
+        tape = Tape(dev, training, record, want_input_grad=bool(input_grad and record))
         tape.param_arena = arena.params
         self.tape = tape
         names = {id(m): n for n, m in root.named_modules()}
@@ -239,7 +238,7 @@ class Program:
         if record:
             tape.finish()
         # weight planes, operand bounds, data-gradient weights: before the first convolution that reads them
-        tape.emit_f16_prep(prep_pos, prep_head)
+        tape.bounds.emit_f16_prep(prep_pos, prep_head)
         if record:
             if self.input_grad:
                 self.gx = tape.empty(N, Cc, H, W)
@@ -575,7 +574,7 @@ class HourglassNet(TapeModule):
         stem = P.conv(self.conv1)
         # d loss / d image (the reference's autograd gives it; train.py never asks): the plain 7x7 / stride 2 convolution with its
         # zero-stuffed data gradient instead of the space-to-depth form
-        gi = getattr(t, 'want_input_grad', False)
+        gi = t.want_input_grad
         x = (None if gi else t.stem_s2d(x, stem)) or t.conv(x, stem, want_stats=True, need_input_grad=gi, name='stem')
         x = t.bn_act(x, P.bn(self.bn1), relu=True, name='stem_act')
         x = _trace_seq(self.layer1, t, x, P)

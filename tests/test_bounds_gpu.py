@@ -133,8 +133,9 @@ def test_every_fp16x3_bound_dominates_its_operand(base, reg, batch, min_uses):
     assert torch.isfinite(g).all().item() and float(g.norm()) > 0
     # every bound slot of the program is finite and non-negative
     t = prog.tape
-    if t._amax_buf is not None:
-        assert torch.isfinite(t._amax_buf[:t._amax_used]).all().item() and float(t._amax_buf[:t._amax_used].min()) >= 0.0
+    slots = t.bounds.claimed()[0]
+    if slots is not None:
+        assert torch.isfinite(slots).all().item() and float(slots.min()) >= 0.0
 
 
 def test_nonfinite_guard_blocks_the_update_and_reports_asynchronously():

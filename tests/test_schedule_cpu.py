@@ -61,10 +61,10 @@ def test_forward_list_preparation_runs_beside_the_stem(tape):
     assert 'dsnt_bn_act_fwd_stats' in before and before.count('dsnt_stem4_fwd_f16x3') == 1 and 'dsnt_conv_fwd_f16x3_ex' not in before
     # ... and that wait comes before the first launch that reads ANY prepared plane or bound, the stream-layout 3x3 kernel included
     readers = ('dsnt_conv_fwd_f16x3_ex', 'dsnt_conv_fwd_f16x3_stream', 'dsnt_conv_fwd_bf16x6_ex', 'dsnt_conv_fwd_bf16x6')
-    first_reader = next(i for i, e in enumerate(fwd) if e[2] in readers and id(e) not in tape._prep_exempt)
+    first_reader = next(i for i, e in enumerate(fwd) if e[2] in readers and id(e) not in tape.bounds._prep_exempt)
     assert first_sync < first_reader
     first_stream = next(i for i, e in enumerate(fwd) if e[2] == 'dsnt_conv_fwd_f16x3_stream')
-    assert first_sync < first_stream and 'dsnt_conv_fwd_f16x3_stream' in tape._PREP_CONSUMERS
+    assert first_sync < first_stream and 'dsnt_conv_fwd_f16x3_stream' in tape.bounds._PREP_CONSUMERS
     assert 'dsnt_nchw_to_nhwc' not in [e[2] for e in fwd]         # the NHWC copy of the image is gone
     assert {e[3] for e in fwd if e[0] is not None} == {0, 1, 3}     # two side lanes for the skip branches
 
@@ -247,7 +247,7 @@ def test_persistent_stage_runs_of_the_recorded_lists(tape):
     from dsnt import _lib
     lib = _lib.load()
     for lst, lo, hi in ((tape.fwd, 2 * 24, 2 * 32), (tape.bwd, 2 * 40, 2 * 56)):
-        h, marks = tape._compile(lst)
+        h, marks = lst.record()
         try:
             size = lib.dsnt_list_size(h)
             n = C.c_int(0)
@@ -267,6 +267,27 @@ def test_persistent_stage_runs_of_the_recorded_lists(tape):
             assert lib.dsnt_list_size(h) == size and lib.dsnt_list_stages(h, None) == 0
         finally:
             lib.dsnt_list_destroy(h)
+
+
+def test_launch_list_stands_alone(monkeypatch_module):
+    """A LaunchList with no Tape and no model behind it: two launches on two lanes, a lane synchronisation and a bucket mark between
+    them.  It records itself into a C list of two segments, once — a second compile hands back the same handle."""
+    from dsnt import _lib
+    from dsnt.launchlist import Lanes, LaunchList
+    monkeypatch_module.setattr(_lib, 'ptr', lambda t: C.c_void_p(t.data_ptr()) if t is not None else None)
+    lib = _lib.load()
+    lst = LaunchList(lib, Lanes(True, 2))
+    a, b = torch.ones(64), torch.ones(32)
+    lst.emit(0, 'dsnt_fill_zero', a, a.numel())
+    lst.sync(0, 1)
+    lst.mark(7, 0)
+    lst.emit(1, 'dsnt_fill_zero', b, b.numel())
+    assert [(e[2], e[3]) for e in lst] == [('dsnt_fill_zero', 0), ('sync', 0), ('bucket', 0), ('dsnt_fill_zero', 1)]
+    assert lst.nbytes == 4 * (64 + 32) and lst.bytes_by_name == {'dsnt_fill_zero': 4 * (64 + 32)}
+    h, marks = lst.compile()
+    assert lib.dsnt_list_segments(h) == 2 and lib.dsnt_list_size(h) >= 2 and marks == [(7, 0)]
+    assert lst.compile()[0] == h
+    assert float(a.min()) == 1.0 and float(b.min()) == 1.0      # recorded, not launched
 
 
 def test_schedule_dump_is_canonical_and_sees_a_moved_launch(monkeypatch_module):

@@ -31,6 +31,7 @@ SWITCHES = [('off_conv3s', dict(DSNT_OFF='conv3s+gemm1+wgrad3+wgrad1')), ('off_b
 MATRIX = ([('%s_b%d' % (b, n), [b, 'train', '%d,3,256,256' % n], {}) for b, n in
            (('hg1', 32), ('hg2', 32), ('hg8', 16), ('resnet18', 8), ('resnet34', 8), ('resnet50', 8))] +
           [('hg2_128', ['hg2', 'train', '4,3,128,128'], {}), ('hg2_eval', ['hg2', 'eval', '32,3,256,256', '--reg', 'none'], {}),
+           ('hg2_128_no_relu', ['hg2', 'train', '4,3,128,128'], dict(DSNT_DEBUG_NO_RELU='1')),
            ('hg2_eval_record', ['hg2', 'eval', '4,3,128,128', '--record'], {}),
            ('hg2_input_grad', ['hg2', 'train', '32,3,256,256', '--input-grad'], {}), ('standalone', ['standalone', 'train', '2,8,16,16'], {})] +
           [('%s_%s' % (b, tag), [b, 'train', '%d,3,256,256' % n], env) for tag, env in SWITCHES for b, n in (('hg2', 32), ('resnet34', 8))] +
@@ -58,7 +59,7 @@ def trace(base, training, shape, reg='js', record=None, input_grad=False):
         x = t.conv(t.act(N, H, W, Cc, 'x'), ps[0], want_stats=True, name='raw')
         t.to_planar(t.conv(t.norm(x, bn), ps[1], name='normed'), Cc)
         t.finish()
-        t.emit_f16_prep(0)
+        t.bounds.emit_f16_prep(0)
         return t, ([('p%d.%d' % (i, j), v) for i, p in enumerate(ps) for j, v in enumerate((p.w, p.b, p.gw, p.gb))] +
                    [('bn%d' % i, v) for i, v in enumerate(bnt)])
     m = build_mpii_pose_model(base=base, output_strat='dsnt', reg=reg)
@@ -74,7 +75,7 @@ def dump(tape, extra=()):
     """(text, number of pointers that lie in no known allocation)."""
     named = [('k%d' % i, t) for i, t in enumerate(tape._keep)] + [('s:%s:%d' % k, t) for k, t in tape._scratch.items()]
     named += list(extra) + [('act%d' % i, a.buf) for i, a in enumerate(tape.acts)]
-    named += [('ident%d' % i, t) for i, t in enumerate(tape._ident or ())] + [('amax', tape._amax_buf), ('famax', tape._famax_buf)]
+    named += [('ident%d' % i, t) for i, t in enumerate(tape._ident or ())] + list(zip(('amax', 'famax'), tape.bounds.claimed()))
     allocs = {}
     for label, t in named:
         if isinstance(t, torch.Tensor) and t.untyped_storage().nbytes():
@@ -133,6 +134,8 @@ def dump(tape, extra=()):
     for e, u in tape.f16_uses:
         lines.append('use %s %s' % (where.get(id(e), '?'), arg(u)))
     lines.append('unresolved pointers: %d' % missed[0])
+    # the algorithmic byte counts (bench.py reads the first two): part of what a refactor must leave as it was
+    lines.append('bytes fwd=%d bwd=%d %s' % (tape.bytes_fwd, tape.bytes_bwd, ' '.join('%s=%d' % kv for kv in sorted(tape.bytes_by_name.items()))))
     return '\n'.join(lines) + '\n', missed[0]
 
 
