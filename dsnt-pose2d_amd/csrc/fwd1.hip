@@ -26,18 +26,27 @@ struct Fwd1P {
     const float* bias; const float* res; float* y; float* stats;
     OutBoundsP ob;
     int M, Cout, nstages, spw;
+    // DS: the projection shortcut of the same block (hourglass.py:44-48), a second product of the same width over the RAW block input
+    const float* x2; const unsigned short* wq2; const float* a_bound2; const float* w_bound2; const float* bias2;
 };
 
 // KK = input channels (the contraction), CW = 16-column tiles per wave, NWV = waves per workgroup (16 CW NWV output columns per
-// workgroup; blockIdx.y = column chunk), PRO: BatchNorm(+ReLU) on the operand, RES: one residual addend
-template <int KK, int CW, int NWV, bool PRO, bool RES>
+// workgroup; blockIdx.y = column chunk), PRO: BatchNorm(+ReLU) on the operand, RES: one residual addend.
+// DS (with PRO, without RES): the residual is not read but COMPUTED — conv3 of a Bottleneck and its projection shortcut in one
+// launch: res = x2 W2^T + bias2 over a second staged operand of the same width.  The two products have different fp16x3 scales,
+// so they keep separate accumulators; the shortcut's value is rounded to fp32 as its own launch would store it and then added
+// as the residual, in that launch's order: every output bit is what the two launches give.  W2 stays in registers, both planes
+// (the LDS holds a second activation image instead).
+template <int KK, int CW, int NWV, bool PRO, bool RES, bool DS = false>
 __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
+    static_assert(!DS || (PRO && !RES), "the shortcut form: BatchNorm operand, computed residual");
+    constexpr int NOP = DS ? 2 : 1;             // staged operands
     constexpr int CC = 16 * CW * NWV;
     constexpr int NTHR = 64 * NWV;
     constexpr int KS = KK / 32;
     constexpr int PITCH = KK * 2 + 32;          // bytes per pixel row of one plane (and per column row of the W image)
     constexpr int PL = 32 * PITCH;
-    constexpr int IMG = 2 * PL;
+    constexpr int IMG = NOP * 2 * PL;
     constexpr int WLO = CC * PITCH;
     constexpr int K4 = KK / 4;
     constexpr int U = 32 * K4 / NTHR;
@@ -45,7 +54,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
     static_assert(U >= 1 && U * NTHR == 32 * K4, "staging units per thread");
     const unsigned OOB = 0xF0000000u;
     extern __shared__ __attribute__((aligned(16))) unsigned char f1_smem[];
-    unsigned char* img = f1_smem;                                   // [2 buffers][2 planes][32 pixels][PITCH]
+    unsigned char* img = f1_smem;                                   // [2 buffers][NOP operands][2 planes][32 pixels][PITCH]
     unsigned char* wlo = f1_smem + 2 * IMG;                         // [CC][PITCH]: lo plane of W
     float* vec = reinterpret_cast<float*>(wlo + WLO);               // PRO: [2][KK] scale, shift (x operand scale)
 
@@ -59,6 +68,8 @@ __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
     const int s1 = min(p.nstages, s0 + p.spw);
     const float sa = pow2_scale(bound64(p.a_bound)), sw = pow2_scale(bound64(p.w_bound));
     const float osc = 1.f / (sa * sw);
+    const float sa2 = DS ? pow2_scale(bound64(p.a_bound2)) : 1.f, sw2 = DS ? pow2_scale(bound64(p.w_bound2)) : 1.f;
+    const float osc2 = 1.f / (sa2 * sw2);
 
     auto stage_off = [&](const int s, const unsigned stage_bytes) {      // (scalar select, laundered: bwd1.hip)
         const unsigned o = s < s1 ? (unsigned)s * stage_bytes : OOB;
@@ -69,11 +80,16 @@ __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.x), 0, (int)((size_t)p.M * KK * 4u), 0x00020000);
     const unsigned xlane = (unsigned)((prow * KK + 4 * k4) * 4);
-    f1_u32x4 R[U];
+    const __amdgpu_buffer_rsrc_t x2r = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(DS ? p.x2 : p.x), 0, (int)((size_t)p.M * KK * 4u), 0x00020000);
+    f1_u32x4 R[U], R2[DS ? U : 1];
     auto issue = [&](const int s) {
         const unsigned so = stage_off(s, 32u * KK * 4u) + xlane;
 #pragma unroll
-        for (int i = 0; i < U; ++i) R[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, so + (unsigned)(RSTEP * i * KK * 4), 0, 0);
+        for (int i = 0; i < U; ++i) {
+            R[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, so + (unsigned)(RSTEP * i * KK * 4), 0, 0);
+            if (DS) R2[i] = __builtin_amdgcn_raw_buffer_load_b128(x2r, so + (unsigned)(RSTEP * i * KK * 4), 0, 0);
+        }
     };
     const float relu_lo = (PRO && p.in_relu) ? 0.f : -__builtin_inff();
     auto transform = [&](const int buf) {
@@ -96,6 +112,13 @@ __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
             split4h(v, q1, q2);
             *reinterpret_cast<uint2*>(base + RSTEP * i * PITCH) = q1;
             *reinterpret_cast<uint2*>(base + RSTEP * i * PITCH + PL) = q2;
+            if (DS) {                           // the raw operand of the shortcut: the !PRO arithmetic
+                float4 t = make_float4(__uint_as_float(R2[i].x), __uint_as_float(R2[i].y), __uint_as_float(R2[i].z), __uint_as_float(R2[i].w));
+                t.x *= sa2; t.y *= sa2; t.z *= sa2; t.w *= sa2;
+                split4h(t, q1, q2);
+                *reinterpret_cast<uint2*>(base + RSTEP * i * PITCH + 2 * PL) = q1;
+                *reinterpret_cast<uint2*>(base + RSTEP * i * PITCH + 3 * PL) = q2;
+            }
         }
     };
     issue(s0);
@@ -137,14 +160,26 @@ __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
                 *reinterpret_cast<const uint4*>(p.wq + (size_t)p.wq_stride + (size_t)(col0 + c) * KK + 8 * k8);
         }
     }
+    f16x8 whi2[DS ? KS : 1][CW], wlo2[DS ? KS : 1][CW];
+    if (DS) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int cw = 0; cw < CW; ++cw) {
+                const unsigned short* w2 = p.wq2 + (size_t)(col0 + c0 + 16 * cw + lc) * KK + 32 * ks + 8 * lg;
+                whi2[ks][cw] = *reinterpret_cast<const f16x8*>(w2);
+                wlo2[ks][cw] = *reinterpret_cast<const f16x8*>(w2 + (size_t)p.wq_stride);
+            }
+    }
     if (PRO) {
         for (int k = tid; k < KK; k += NTHR) { vec[k] = p.in_scale[k] * sa; vec[KK + k] = p.in_shift[k] * sa; }
     }
-    float cb[CW], asc[CW], ash[CW];
+    float cb[CW], cb2[CW], asc[CW], ash[CW];
 #pragma unroll
     for (int cw = 0; cw < CW; ++cw) {
         const int c = col0 + c0 + 16 * cw + lc;
         cb[cw] = p.bias ? p.bias[c] : 0.f;
+        cb2[cw] = (DS && p.bias2) ? p.bias2[c] : 0.f;
         asc[cw] = p.ob.amax_bn ? p.ob.amax_scale[c] : 0.f;
         ash[cw] = p.ob.amax_bn ? p.ob.amax_shift[c] : 0.f;
     }
@@ -169,9 +204,9 @@ __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
         const unsigned ib = (unsigned)(buf * IMG);
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
-            f32x4 acc[CW];
+            f32x4 acc[CW], acs[CW];
 #pragma unroll
-            for (int cw = 0; cw < CW; ++cw) acc[cw] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int cw = 0; cw < CW; ++cw) { acc[cw] = (f32x4){0.f, 0.f, 0.f, 0.f}; acs[cw] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const unsigned ao = ib + (unsigned)(rt * 16 * PITCH + 64 * ks) + a_lane;
@@ -184,6 +219,16 @@ __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
                     acc[cw] = __builtin_amdgcn_mfma_f32_16x16x32_f16(d1, b2, acc[cw], 0, 0, 0);
                     acc[cw] = __builtin_amdgcn_mfma_f32_16x16x32_f16(d1, whi[ks][cw], acc[cw], 0, 0, 0);
                 }
+                if (DS) {                       // the shortcut's product, in the MFMA order of its own launch
+                    const f16x8 e1 = *reinterpret_cast<const f16x8*>(f1_smem + ao + 2 * PL);
+                    const f16x8 e2 = *reinterpret_cast<const f16x8*>(f1_smem + ao + 3 * PL);
+#pragma unroll
+                    for (int cw = 0; cw < CW; ++cw) {
+                        acs[cw] = __builtin_amdgcn_mfma_f32_16x16x32_f16(e2, whi2[ks][cw], acs[cw], 0, 0, 0);
+                        acs[cw] = __builtin_amdgcn_mfma_f32_16x16x32_f16(e1, wlo2[ks][cw], acs[cw], 0, 0, 0);
+                        acs[cw] = __builtin_amdgcn_mfma_f32_16x16x32_f16(e1, whi2[ks][cw], acs[cw], 0, 0, 0);
+                    }
+                }
             }
             const unsigned obase = (unsigned)(s * 32 + 16 * rt) * (unsigned)ld * 4u + ylane;
 #pragma unroll
@@ -192,6 +237,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void fwd1_kernel(Fwd1P p) {
                 for (int r = 0; r < 4; ++r) {
                     float v = acc[cw][r] * osc + cb[cw];
                     if (RES) v += rv[rt][cw][r];
+                    if (DS) { const float sk = acs[cw][r] * osc2 + cb2[cw]; v += sk; }
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, obase + (unsigned)(cw * 64), (unsigned)(r * ld * 4), 0);
                     am = fmaxf(am, fabsf(v));
                     am2 = fmaxf(am2, fabsf(fmaxf(fmaf(v, asc[cw], ash[cw]), am2lo)));      // (unconditional: a uniform branch per element otherwise)
@@ -311,4 +357,44 @@ extern "C" int dsnt_conv1x1_fwd_f16x3(const float* x, const void* w_planes, int6
     default: f1_launch_cfg<64, 1, 8>(pl, p, st); break;
     }
     DSNT_CHECK_LAUNCH("dsnt_conv1x1_fwd_f16x3");
+}
+
+// conv3 of a Bottleneck with a projection shortcut and that shortcut in one launch (fwd1_kernel<.., DS>): y = conv(relu?(bn(x))) + bias
+// + (conv_ds(x_ds) + bias_ds), statistics and bounds of y as the conv3 launch leaves them
+extern "C" int dsnt_conv1x1_fwd_ds_f16x3(const float* x, const float* x_ds, const void* w_planes, const void* w_planes_ds,
+                                         int64_t plane_stride, const float* w_bound, const float* w_bound_ds,
+                                         const float* a_bound, const float* a_bound_ds, const float* bias,
+                                         const float* bias_ds, float* y, const float* in_scale, const float* in_shift,
+                                         int in_relu, float* stats_partial, const dsnt_conv_geom* g,
+                                         const dsnt_conv_geom* g_ds, const dsnt_out_bounds* tail, void* stream) {
+    DSNT_REQUIRE(x && x_ds && w_planes && w_planes_ds && w_bound && w_bound_ds && a_bound && a_bound_ds && y && in_scale &&
+                 in_shift && g && g_ds, DSNT_ERR_ARG, "dsnt_conv1x1_fwd_ds_f16x3: bad argument");
+    const Fwd1Plan pl = dsnt_fwd1_plan(g, (in_relu & DSNT_CONV_SHARE_CHIP) != 0);
+    DSNT_REQUIRE(pl.ok && (pl.cfg == 1 || pl.cfg == 4), DSNT_ERR_SHAPE,
+                 "dsnt_conv1x1_fwd_ds_f16x3: geometry not supported (64 -> 128 or 128 -> 256 channels, dsnt_conv1x1_fwd_ok)");
+    DSNT_REQUIRE(g_ds->Cin == g->Cin && g_ds->Cout == g->Cout && g_ds->N == g->N && g_ds->H == g->H && g_ds->W == g->W &&
+                 dsnt_fwd1_plan(g_ds, (in_relu & DSNT_CONV_SHARE_CHIP) != 0).ok, DSNT_ERR_SHAPE,
+                 "dsnt_conv1x1_fwd_ds_f16x3: the shortcut must have the convolution's geometry (equal halves)");
+    DSNT_REQUIRE(dsnt_aligned16(x) && dsnt_aligned16(x_ds) && dsnt_aligned16(w_planes) && dsnt_aligned16(w_planes_ds) &&
+                 dsnt_aligned16(y) && dsnt_aligned16(in_scale) && dsnt_aligned16(in_shift) && plane_stride % 8 == 0, DSNT_ERR_ALIGN,
+                 "dsnt_conv1x1_fwd_ds_f16x3: 16-byte alignment required");
+    Fwd1P p;
+    memset(&p, 0, sizeof(p));
+    if (int e = out_bounds_fill(p.ob, tail, "dsnt_conv1x1_fwd_ds_f16x3")) return e;
+    p.x = x; p.in_scale = in_scale; p.in_shift = in_shift; p.in_relu = in_relu & 1;
+    p.wq = (const unsigned short*)w_planes; p.wq_stride = plane_stride; p.a_bound = a_bound; p.w_bound = w_bound;
+    p.bias = bias; p.y = y; p.stats = stats_partial;
+    p.x2 = x_ds; p.wq2 = (const unsigned short*)w_planes_ds; p.a_bound2 = a_bound_ds; p.w_bound2 = w_bound_ds; p.bias2 = bias_ds;
+    p.M = g->N * g->H * g->W; p.Cout = g->Cout; p.nstages = pl.nstages; p.spw = pl.spw;
+    hipStream_t st = (hipStream_t)stream;
+    const int pitch = g->Cin * 2 + 32;
+    const int lds = pl.lds + 2 * 2 * 32 * pitch;            // the second activation image
+    if (pl.cfg == 1) {
+        DSNT_SET_MAX_LDS((fwd1_kernel<128, 2, 8, true, false, true>), lds);
+        DSNT_LAUNCH((fwd1_kernel<128, 2, 8, true, false, true>), dim3(pl.nwg, 1), dim3(512), lds, st, p);
+    } else {
+        DSNT_SET_MAX_LDS((fwd1_kernel<64, 1, 8, true, false, true>), lds);
+        DSNT_LAUNCH((fwd1_kernel<64, 1, 8, true, false, true>), dim3(pl.nwg, 1), dim3(512), lds, st, p);
+    }
+    DSNT_CHECK_LAUNCH("dsnt_conv1x1_fwd_ds_f16x3");
 }

@@ -12,7 +12,8 @@ def _f32_bits(v):
 
 class Bounds:
     # launches that read weight planes or operand bounds: the preparation must have finished before the first of them
-    _PREP_CONSUMERS = ('dsnt_conv_fwd_f16x3_ex', 'dsnt_conv_fwd_f16x3_stream', 'dsnt_conv1x1_fwd_f16x3', 'dsnt_stem4_fwd_f16x3',
+    _PREP_CONSUMERS = ('dsnt_conv_fwd_f16x3_ex', 'dsnt_conv_fwd_f16x3_stream', 'dsnt_conv1x1_fwd_f16x3', 'dsnt_conv1x1_fwd_ds_f16x3',
+                       'dsnt_stem4_fwd_f16x3',
                        'dsnt_conv_fwd_bf16x6_ex', 'dsnt_conv_fwd_bf16x6')
 
     def __init__(self, tape):

@@ -195,6 +195,11 @@ class Tape:
         self.fold3 = 'fold3' not in off
         self.fold3_rows = int(os.environ.get('DSNT_X_FOLD3_ROWS', '16384'))
         self.stem4 = 'stem4' not in off    # the stem's forward (csrc/stem4.hip)
+        # conv3 of a Bottleneck and its projection shortcut (the stem's layer1 and layer3) as one forward launch: the skip tensor
+        # is neither written nor read back (`ds_fuse_ok`; DSNT_OFF=dsfuse: two launches).  From DSNT_X_DS_FUSE_ROWS rows: the
+        # 128 x 128 and 64 x 64 levels from batch 4 and 16 on.
+        self.ds_fuse = 'dsfuse' not in off
+        self.ds_fuse_rows = int(os.environ.get('DSNT_X_DS_FUSE_ROWS', '65536'))
         # round 6: runs of small dependent launches of one lane as ONE persistent launch (csrc/stage.h).  OFF by default — built,
         # bit-identical to the launches it replaces (tests/test_stage_gpu.py), and measured SLOWER: hg2 batch 32 11.06 -> 11.97 ms,
         # hg8 batch 16 24.1 -> 25.7 ms with every run fused; 11.17 / 24.04 (no gain) with only the <= 64-workgroup launches of the
@@ -599,6 +604,84 @@ class Tape:
             self._conv_backward_plan(c)
             self.on_backward(lambda: self._conv_backward(c))
         return y
+
+    # ------------------------------------------------------------------ conv3 + projection shortcut in one launch
+    def ds_fuse_ok(self, x, p_ds, p3):
+        """conv3 of a Bottleneck (p3) and its projection shortcut (p_ds, over the block input x) can run as ONE forward launch
+        (csrc/fwd1.hip DS): a train step on fp16x3 from DSNT_X_DS_FUSE_ROWS rows, equal halves, the forward's `_ok` predicate,
+        x's producer able to leave max|x|.  Asked BEFORE the block is traced: on the fused path the shortcut is not traced on its
+        own and the skip tensor never exists.  The backward stays two launches (`_conv_backward_ds`)."""
+        if not (self.ds_fuse and self.training and self.record and self.use_f16x3 and self.fwd1):
+            return False
+        if not (p_ds.R == 1 and p_ds.S == 1 and p_ds.stride == 1 and p3.R == 1 and p3.S == 1 and p3.stride == 1 and
+                (p_ds.Cin, p_ds.Cout) == (p3.Cin, p3.Cout) and (p3.Cin, p3.Cout) in ((64, 128), (128, 256)) and
+                x.M >= self.ds_fuse_rows and p_ds.post_reduce is None and p3.post_reduce is None):
+            return False
+        if any(p.wq is None or p.wq16 is None for p in (p_ds, p3)) or p_ds.wq_stride != p3.wq_stride:
+            return False
+        g = self.geom(x, p_ds)
+        if not (self._use6(g) and self.lib.dsnt_conv1x1_fwd_ok(C.byref(g))):
+            return False
+        return self.bounds.operand_amax(x) is not None      # (claims the producer's tail, as the shortcut's own launch would)
+
+    def conv_ds(self, src, p, x_ds, p_ds, want_stats=False, name='', name_ds='ds'):
+        """y = conv(src) + bias + (conv_ds(x_ds) + bias_ds): `conv(src, p, res1=conv(x_ds, p_ds))` without the skip tensor
+        (the caller has asked `ds_fuse_ok`)."""
+        c, cd = _Conv(), _Conv()
+        c.src, c.p, c.res1, c.res2, c.name, c.need_input_grad = src, p, None, None, name, True
+        c.normed, c.x = True, src.x
+        c.g = self.geom(c.x, p)
+        cd.src, cd.p, cd.res1, cd.res2, cd.name, cd.need_input_grad = x_ds, p_ds, None, None, name_ds, True
+        cd.normed, cd.x = False, x_ds
+        cd.g = self.geom(x_ds, p_ds)
+        c.y = cd.y = y = self.act(c.x.N, c.g.Ho, c.g.Wo, p.Cout, name)
+        c.x.uses += 1
+        x_ds.uses += 1
+        c.sc, c.sh, c.relu = src.scale, src.shift, 1 if src.relu else 0
+        cd.sc, cd.sh, cd.relu = None, None, 0
+        self._conv_forward_ds(c, cd, want_stats)
+        # (the shortcut's plan first: the order in which the two-launch path asks for the data-gradient slots)
+        self._conv_backward_plan(cd)
+        self._conv_backward_plan(c)
+        y.fold_ok = False               # dL/dy feeds two convolutions: it has to exist in memory
+        self.on_backward(lambda: self._conv_backward_ds(c, cd))
+        return y
+
+    def _conv_forward_ds(self, c, cd, want_stats):
+        src, x, y, p, g = c.src, c.x, c.y, c.p, c.g
+        self.check_lane(src)
+        c.use6 = cd.use6 = True
+        c.use16 = cd.use16 = True
+        shr = self._share()
+        part = None
+        if want_stats:
+            tiles = self.lib.dsnt_conv1x1_fwd_stats_rows(C.byref(g), shr)
+            part = self.empty(tiles, 2, p.Cout)
+            y.stats = (part, tiles)
+        y.amax_tail = tail = BnTail()
+        ab = self.bounds.f16_bn_bound(src)
+        c.x_amax, cd.x_amax = None, self.bounds.operand_amax(cd.x)
+        self.materialize(src)
+        for q in (p, cd.p):
+            self.bounds.f16_weights(q, stream=False)
+        e = self.f('dsnt_conv1x1_fwd_ds_f16x3', x.buf, cd.x.buf, p.wq16, cd.p.wq16, p.wq_stride, p.wb, cd.p.wb, ab, cd.x_amax,
+                   p.b, cd.p.b, y.buf, c.sc, c.sh, c.relu | shr, part, g, cd.g, tail)
+        # one info per operand pair (tests/test_bounds_gpu.py)
+        self.f16_uses.append((e, dict(kind='fwd', name=c.name, x=x.buf, sc=c.sc, sh=c.sh, relu=c.relu, a_bound=ab,
+                                      w=p.w, w_bound=p.wb)))
+        self.f16_uses.append((e, dict(kind='fwd', name=cd.name, x=cd.x.buf, sc=None, sh=None, relu=0, a_bound=cd.x_amax,
+                                      w=cd.p.w, w_bound=cd.p.wb)))
+
+    def _conv_backward_ds(self, c, cd):
+        """The backward of `conv_ds`: the two convolutions' own backwards over the same dL/dy, conv3's first (what bn3 and conv2
+        wait for).  The shortcut's is then the FIRST writer of dL/dx where its stand-alone trace made it the last; the sum of the
+        two fp32 contributions is the same either way."""
+        y = c.y
+        if y.pending_apply is not None:
+            self.materialize_apply(y)
+        assert y.grad is not None, 'no gradient reached conv output ' + c.name
+        self._conv_backward(c)
+        self._conv_backward(cd)
 
     def _share(self, persistent=True):
         """DSNT_CONV_SHARE_CHIP (bit 1 of a launch's flag word) on the side lanes' launches of the persistent kernels (3x3: 3/2

@@ -433,12 +433,16 @@ class Bottleneck(TapeModule):
 
     def trace(self, t, x, P):
         skip = x
-        if self.downsample is not None:
-            skip = t.conv(x, P.conv(self.downsample[0]), name='ds')
+        # the projection shortcut: a launch of its own, or (large launches) inside conv3's — no skip tensor then
+        p3, pd = P.conv(self.conv3), (P.conv(self.downsample[0]) if self.downsample is not None else None)
+        fuse = pd is not None and t.ds_fuse_ok(x, pd, p3)
+        if pd is not None and not fuse:
+            skip = t.conv(x, pd, name='ds')
         y = t.conv(t.norm(x, P.bn(self.bn1)), P.conv(self.conv1), want_stats=True, name='c1')
         y = t.conv(t.norm(y, P.bn(self.bn2)), P.conv(self.conv2), want_stats=True, name='c2')
-        return t.conv(t.norm(y, P.bn(self.bn3)), P.conv(self.conv3), res1=skip, want_stats=True,
-                      name='c3')
+        if fuse:
+            return t.conv_ds(t.norm(y, P.bn(self.bn3)), p3, x, pd, want_stats=True, name='c3')
+        return t.conv(t.norm(y, P.bn(self.bn3)), p3, res1=skip, want_stats=True, name='c3')
 
 
 def _trace_seq(seq, t, x, P):

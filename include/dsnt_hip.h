@@ -415,6 +415,19 @@ int dsnt_conv1x1_fwd_f16x3(const float* x, const void* w_planes, int64_t plane_s
                            const float* a_bound, const float* bias, float* y, const float* in_scale,
                            const float* in_shift, int in_relu, const float* res1, float* stats_partial,
                            const dsnt_conv_geom* g, const dsnt_out_bounds* tail, void* stream);
+/* conv3 of a Bottleneck WITH a projection shortcut, and that shortcut, in one launch of the same kernel
+ * (the reference's hourglass.py:25,44-48: `out = self.conv3(out); residual = self.downsample(x); out += residual`):
+ *   y = conv(relu?(x in_scale + in_shift)) + bias + (conv_ds(x_ds) + bias_ds)
+ * — what dsnt_conv1x1_fwd_f16x3(x_ds, ..., skip) followed by dsnt_conv1x1_fwd_f16x3(x, ..., res1 = skip) leave in y, its
+ * statistics rows and its `tail`, bit for bit (two accumulator sets, one per operand pair with its own bounds; the shortcut's
+ * value rounded to fp32 before it is added), without the skip tensor: 537 MB instead of 1075 MB for 64 -> 128 channels at
+ * 128 x 128, batch 32.  Both convolutions have the same geometry (g_ds == g in Cin, Cout and pixels: DSNT_ERR_SHAPE otherwise) and
+ * their weight planes the same plane_stride; (Cin, Cout) in {(64, 128), (128, 256)}.  Called by dsnt/engine.py `_conv_forward_ds`. */
+int dsnt_conv1x1_fwd_ds_f16x3(const float* x, const float* x_ds, const void* w_planes, const void* w_planes_ds,
+                              int64_t plane_stride, const float* w_bound, const float* w_bound_ds, const float* a_bound,
+                              const float* a_bound_ds, const float* bias, const float* bias_ds, float* y,
+                              const float* in_scale, const float* in_shift, int in_relu, float* stats_partial,
+                              const dsnt_conv_geom* g, const dsnt_conv_geom* g_ds, const dsnt_out_bounds* tail, void* stream);
 /* The stem (hourglass.py:157 `self.conv1`, 7x7 / stride 2 / pad 3 on the image) in its space-to-depth form: a 4x4 / stride 1 /
  * pad 1 convolution of the 16-channel image dsnt_s2d_input leaves ([N][H/2+1][W/2+1][16]), 64 output channels, fp16x3 — on a halo
  * kernel of its own (csrc/stem4.hip: the 7 x 35 input halo of a 4 x 32 output patch staged once for all 16 taps, weights in
