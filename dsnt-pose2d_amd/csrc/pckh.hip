@@ -44,6 +44,17 @@ extern "C" int dsnt_pckh(const float* pred, const float* target, const double* m
 // its non-zero cells with one 64-bit atomic each, so the global traffic is bounded by grid x cells whatever the batch.
 static_assert(DSNT_PCKH_HIST_MAX_T % 8 == 0, "pckh_hist_kernel reads the edges eight at a time");
 struct pckh_thresholds { double t[DSNT_PCKH_HIST_MAX_T]; };
+// Bin of a distance, for pckh_hist_kernel and score_hist_kernel.  Ascending edges: the thresholds d exceeds are a prefix,
+// and their number is the bin.  The index is uniform, so eight edges are one scalar load of the kernel argument; the host
+// pads the edges with +inf, which only a NaN exceeds (NaN exceeds all: bin T).
+__device__ __forceinline__ int pckh_column(const pckh_thresholds& thr, double d, int T) {
+    int k = 0;
+    for (int q = 0; q < T; q += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) k += (d <= thr.t[q + u]) ? 0 : 1;
+    }
+    return min(k, T);
+}
 __global__ __launch_bounds__(DSNT_PCKH_HIST_BLOCK)
 void pckh_hist_kernel(const float* __restrict__ pred, const float* __restrict__ target, const double* __restrict__ m,
                       const double* __restrict__ b, const float* __restrict__ mask, const double* __restrict__ head,
@@ -62,16 +73,7 @@ void pckh_hist_kernel(const float* __restrict__ pred, const float* __restrict__ 
         const bool v = mask[i] == 1.f;
         if (dist) dist[i] = v ? d : (double)NAN;
         if (!v) continue;
-        // ascending edges: the thresholds d exceeds are a prefix, and their number is the bin.  The index is uniform, so
-        // eight edges are one scalar load of the kernel argument; the host pads the edges with +inf, which only a NaN
-        // exceeds (NaN exceeds all: bin T).
-        int k = 0;
-        for (int q = 0; q < T; q += 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) k += (d <= thr.t[q + u]) ? 0 : 1;
-        }
-        k = min(k, T);
-        const int c = j * (T + 1) + k;
+        const int c = j * (T + 1) + pckh_column(thr, d, T);
         if (use_lds) atomicAdd(cnt + c, 1u);
         else atomicAdd(table + c, 1ull);
     }
@@ -83,6 +85,19 @@ void pckh_hist_kernel(const float* __restrict__ pred, const float* __restrict__ 
         }
     }
 }
+// The T <= DSNT_PCKH_HIST_MAX_T thresholds of `who` as the kernels take them: finite, strictly ascending, padded with +inf.
+// 0 or the error code.
+static int pckh_thresholds_arg(const char* who, const double* thresholds, int T, pckh_thresholds* out) {
+    for (int k = 0; k < DSNT_PCKH_HIST_MAX_T; ++k) out->t[k] = (double)INFINITY;
+    for (int k = 0; k < T; ++k) {
+        const double t = thresholds[k];
+        DSNT_REQUIRE(t - t == 0.0, DSNT_ERR_ARG, "%s: threshold %d is not finite", who, k);
+        DSNT_REQUIRE(k == 0 || t > thresholds[k - 1], DSNT_ERR_ARG, "%s: thresholds must be strictly ascending (index %d)",
+                     who, k);
+        out->t[k] = t;
+    }
+    return DSNT_OK;
+}
 extern "C" int dsnt_pckh_hist(const float* pred, const float* target, const double* m, const double* b,
                               const float* mask, const double* head, const double* thresholds, int T,
                               unsigned long long* table, double* dist, int B, int J, void* stream) {
@@ -92,14 +107,7 @@ extern "C" int dsnt_pckh_hist(const float* pred, const float* target, const doub
                  DSNT_PCKH_HIST_MAX_T);
     DSNT_REQUIRE((long)J * (T + 1) <= 0x7fffffffL, DSNT_ERR_ARG, "dsnt_pckh_hist: J * (T + 1) does not fit an int");
     pckh_thresholds thr;
-    for (int k = 0; k < DSNT_PCKH_HIST_MAX_T; ++k) thr.t[k] = (double)INFINITY;
-    for (int k = 0; k < T; ++k) {
-        const double t = thresholds[k];
-        DSNT_REQUIRE(t - t == 0.0, DSNT_ERR_ARG, "dsnt_pckh_hist: threshold %d is not finite", k);
-        DSNT_REQUIRE(k == 0 || t > thresholds[k - 1], DSNT_ERR_ARG,
-                     "dsnt_pckh_hist: thresholds must be strictly ascending (index %d)", k);
-        thr.t[k] = t;
-    }
+    if (const int rc = pckh_thresholds_arg("dsnt_pckh_hist", thresholds, T, &thr)) return rc;
     const long total = (long)B * J;
     const long want = (total + DSNT_PCKH_HIST_BLOCK - 1) / DSNT_PCKH_HIST_BLOCK;
     const int grid = (int)(want < DSNT_PCKH_HIST_MAX_BLOCKS ? want : DSNT_PCKH_HIST_MAX_BLOCKS);
@@ -107,6 +115,113 @@ extern "C" int dsnt_pckh_hist(const float* pred, const float* target, const doub
     DSNT_LAUNCH(pckh_hist_kernel, dim3(grid), dim3(DSNT_PCKH_HIST_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
                 mask, head, thr, T, table, dist, B, J, use_lds);
     DSNT_CHECK_LAUNCH("dsnt_pckh_hist");
+}
+
+// Score against distance (include/dsnt_hip.h: dsnt_score_hist): pckh_hist_kernel with a second index, the row of the
+// joint's score among the score edges, so table[j][r][k] summed over r is pckh_hist_kernel's table bit for bit.  Same grid,
+// same striding, same two accumulation paths; the LDS copy is u32 [J][S + 2][T + 1] (32 KiB at the limit).
+static_assert(DSNT_SCORE_HIST_MAX_S % 8 == 0, "score_row reads the edges eight at a time");
+static_assert(DSNT_SCORE_HIST_LDS_CELLS * sizeof(unsigned) <= 64 * 1024, "the LDS table is a static allocation");
+struct score_edges { double e[DSNT_SCORE_HIST_MAX_S]; };
+// Row of a score: the number of edges that are <= the score (ascending edges: those are a prefix), S + 1 for a NaN.  The
+// host pads the edges with +inf, which only a score of +inf reaches: capped at S.  The index is uniform, so eight edges
+// are one scalar load of the kernel argument, as in pckh_hist_kernel.
+__device__ __forceinline__ int score_row(const score_edges& edges, float score, int S) {
+    const double s = (double)score;
+    int r = 0;
+    for (int q = 0; q < S; q += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) r += (edges.e[q + u] <= s) ? 1 : 0;
+    }
+    return s != s ? S + 1 : min(r, S);
+}
+__global__ __launch_bounds__(DSNT_PCKH_HIST_BLOCK)
+void score_hist_kernel(const float* __restrict__ pred, const float* __restrict__ target, const double* __restrict__ m,
+                       const double* __restrict__ b, const float* __restrict__ mask, const double* __restrict__ head,
+                       const float* __restrict__ score, const score_edges edges, int S, const pckh_thresholds thr, int T,
+                       unsigned long long* table, int B, int J, int use_lds) {
+    __shared__ unsigned cnt[DSNT_SCORE_HIST_LDS_CELLS];
+    const int cells = J * (S + 2) * (T + 1);
+    if (use_lds) {
+        for (int c = threadIdx.x; c < cells; c += blockDim.x) cnt[c] = 0u;
+        __syncthreads();
+    }
+    const long total = (long)B * J;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        if (!(mask[i] == 1.f)) continue;
+        const long n = i / J;
+        const int j = (int)(i - n * J);
+        const double d = pckh_distance(pred, target, m, b, head, i, n);
+        const int c = (j * (S + 2) + score_row(edges, score[i], S)) * (T + 1) + pckh_column(thr, d, T);
+        if (use_lds) atomicAdd(cnt + c, 1u);
+        else atomicAdd(table + c, 1ull);
+    }
+    if (use_lds) {
+        __syncthreads();
+        for (int c = threadIdx.x; c < cells; c += blockDim.x) {
+            const unsigned v = cnt[c];
+            if (v) atomicAdd(table + c, (unsigned long long)v);
+        }
+    }
+}
+// The edges of either entry point: S in range, finite, strictly ascending; padded with +inf.  0 or the error code.
+static int score_edges_arg(const char* who, const double* score_edges_host, int S, score_edges* out) {
+    DSNT_REQUIRE(S >= 1 && S <= DSNT_SCORE_HIST_MAX_S, DSNT_ERR_ARG, "%s: S=%d outside 1..%d", who, S, DSNT_SCORE_HIST_MAX_S);
+    for (int k = 0; k < DSNT_SCORE_HIST_MAX_S; ++k) out->e[k] = (double)INFINITY;
+    for (int k = 0; k < S; ++k) {
+        const double e = score_edges_host[k];
+        DSNT_REQUIRE(e - e == 0.0, DSNT_ERR_ARG, "%s: score edge %d is not finite", who, k);
+        DSNT_REQUIRE(k == 0 || e > score_edges_host[k - 1], DSNT_ERR_ARG,
+                     "%s: score edges must be strictly ascending (index %d)", who, k);
+        out->e[k] = e;
+    }
+    return DSNT_OK;
+}
+extern "C" int dsnt_score_hist(const float* pred, const float* target, const double* m, const double* b,
+                               const float* mask, const double* head, const float* score, const double* score_edges_host,
+                               int S, const double* thresholds, int T, unsigned long long* table, int B, int J,
+                               void* stream) {
+    DSNT_REQUIRE(pred && target && m && b && mask && head && score && score_edges_host && thresholds && table && B > 0 &&
+                 J > 0, DSNT_ERR_ARG, "dsnt_score_hist: bad argument");
+    DSNT_REQUIRE(T >= 1 && T <= DSNT_PCKH_HIST_MAX_T, DSNT_ERR_ARG, "dsnt_score_hist: T=%d outside 1..%d", T,
+                 DSNT_PCKH_HIST_MAX_T);
+    score_edges edges;
+    if (const int rc = score_edges_arg("dsnt_score_hist", score_edges_host, S, &edges)) return rc;
+    DSNT_REQUIRE((long)J * (S + 2) * (T + 1) <= 0x7fffffffL, DSNT_ERR_ARG,
+                 "dsnt_score_hist: J * (S + 2) * (T + 1) does not fit an int");
+    pckh_thresholds thr;
+    if (const int rc = pckh_thresholds_arg("dsnt_score_hist", thresholds, T, &thr)) return rc;
+    const long total = (long)B * J;
+    const long want = (total + DSNT_PCKH_HIST_BLOCK - 1) / DSNT_PCKH_HIST_BLOCK;
+    const int grid = (int)(want < DSNT_PCKH_HIST_MAX_BLOCKS ? want : DSNT_PCKH_HIST_MAX_BLOCKS);
+    const int use_lds = (long)J * (S + 2) * (T + 1) <= DSNT_SCORE_HIST_LDS_CELLS ? 1 : 0;
+    DSNT_LAUNCH(score_hist_kernel, dim3(grid), dim3(DSNT_PCKH_HIST_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
+                mask, head, score, edges, S, thr, T, table, B, J, use_lds);
+    DSNT_CHECK_LAUNCH("dsnt_score_hist");
+}
+
+// out[i] = values[joint of i][row of score[i]] (include/dsnt_hip.h: dsnt_score_lookup): the calibration table applied to a
+// batch of scores.  Plain stores over a grid stride.
+__global__ __launch_bounds__(DSNT_SCORE_LOOKUP_BLOCK)
+void score_lookup_kernel(const float* __restrict__ score, const score_edges edges, int S, const float* __restrict__ values,
+                         int per_joint, float* __restrict__ out, long n, int J) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int j = per_joint ? (int)(i % J) : 0;
+        out[i] = values[j * (S + 2) + score_row(edges, score[i], S)];
+    }
+}
+extern "C" int dsnt_score_lookup(const float* score, const double* score_edges_host, int S, const float* values,
+                                 int per_joint, float* out, int64_t n, int J, void* stream) {
+    DSNT_REQUIRE(score && score_edges_host && values && out && n > 0 && J > 0 && (per_joint == 0 || per_joint == 1),
+                 DSNT_ERR_ARG, "dsnt_score_lookup: bad argument");
+    score_edges edges;
+    if (const int rc = score_edges_arg("dsnt_score_lookup", score_edges_host, S, &edges)) return rc;
+    DSNT_REQUIRE((long)J * (S + 2) <= 0x7fffffffL, DSNT_ERR_ARG, "dsnt_score_lookup: J * (S + 2) does not fit an int");
+    const long want = ((long)n + DSNT_SCORE_LOOKUP_BLOCK - 1) / DSNT_SCORE_LOOKUP_BLOCK;
+    const int grid = (int)(want < DSNT_SCORE_LOOKUP_MAX_BLOCKS ? want : DSNT_SCORE_LOOKUP_MAX_BLOCKS);
+    DSNT_LAUNCH(score_lookup_kernel, dim3(grid), dim3(DSNT_SCORE_LOOKUP_BLOCK), 0, (hipStream_t)stream, score, edges, S,
+                values, per_joint, out, (long)n, J);
+    DSNT_CHECK_LAUNCH("dsnt_score_lookup");
 }
 
 // Misprediction field (bin/investigate.py:62-99; include/dsnt_hip.h: dsnt_error_field): per joint, a bins x bins grid over

@@ -12,6 +12,10 @@ is a cumulative sum of that table taken when the user asks.
 
 `ErrorField` is the reference's `bin/investigate.py` on the device: where in the frame joints are missed and which way
 (`dsnt_error_field`), again one launch per batch into device-resident tables.
+
+`Reliability` asks whether a per-joint confidence knows when the joint is right: one launch per batch adds into a table of
+score row against distance column (`dsnt_score_hist`), from which accuracy per score, risk against
+coverage, an operating point and a monotone `ScoreCalibration` (applied on the device by `dsnt_score_lookup`) are read.
 """
 import ctypes
 
@@ -457,3 +461,302 @@ class ErrorField:
         dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
         dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
         self._take(counts, sums)
+
+
+def _fp32_ascending(values, most, what):
+    """`values` as the fp64 values of their fp32 roundings: between 1 and `most`, finite and strictly ascending."""
+    out = [float(np.float32(v)) for v in np.asarray(values, dtype=np.float64).reshape(-1)]
+    if not 1 <= len(out) <= most:
+        raise ValueError('between 1 and %d %s, got %d' % (most, what, len(out)))
+    if not all(np.isfinite(out)) or any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError('%s must be finite and strictly ascending as fp32 values' % what)
+    return out
+
+
+def _ratio(num, den):
+    """num / den in fp64, NaN where den is 0."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(den > 0, np.asarray(num, np.float64) / np.asarray(den, np.float64), np.nan)
+
+
+def _pav(hits, n, increasing):
+    """Pool-adjacent-violators over the rows with support: `hits`, `n` are Python ints per score row in ascending score.
+    Returns the pooled `(hits, n)` of every supported row (None for the others), rates non-decreasing in the score if
+    `increasing`, else non-increasing.  Pools are integer pairs compared by cross-multiplication: exact."""
+    rows = [r for r in range(len(n)) if n[r] > 0]
+    if not increasing:
+        rows.reverse()                    # non-increasing in the score is non-decreasing walked from the top
+    pools = []                            # [hits, n, rows]
+    for r in rows:
+        pools.append([hits[r], n[r], [r]])
+        while len(pools) > 1 and pools[-2][0] * pools[-1][1] > pools[-1][0] * pools[-2][1]:
+            h, m, members = pools.pop()
+            pools[-1][0] += h
+            pools[-1][1] += m
+            pools[-1][2] += members
+    out = [None] * len(n)
+    for h, m, members in pools:
+        for r in members:
+            out[r] = (h, m)
+    return out
+
+
+class Reliability:
+    """Does a per-joint score (a confidence such as `stats['peak']`, or a spread) know when the joint is right?
+
+    `table[j][r][k]` counts the valid joints `j` whose score lies in row `r` and whose distance lies in `PCKhCurve`'s
+    column `k`.  With the `S` score edges `e`, row `r` is the number of edges `<=` the score: row 0 is `score < e[0]`, row
+    `S` is `score >= e[S - 1]`, a score on an edge belongs to the row above it, and row `S + 1` holds the NaN scores
+    ("unscored").  Edges and thresholds are held as the fp64 values of their fp32 roundings, so an fp32 score compares
+    exactly.  Summed over the score rows the table is `PCKhCurve`'s.  Everything read from it is computed on the host
+    from the integers.  `name` below is a joint name, a group name or a joint index."""
+
+    JOINT_NAMES = PCKhEvaluator.JOINT_NAMES
+    JOINT_GROUPS = PCKhEvaluator.JOINT_GROUPS
+    MAX_THRESHOLDS = 64                   # DSNT_PCKH_HIST_MAX_T
+    MAX_EDGES = 64                        # DSNT_SCORE_HIST_MAX_S
+
+    def __init__(self, score_edges, thresholds=(0.5,), n_joints=16, higher_is_better=True, joint_names=None,
+                 joint_groups=None):
+        self.n_joints = int(n_joints)
+        self.higher_is_better = bool(higher_is_better)
+        if self.n_joints < 1:
+            raise ValueError('n_joints must be positive')
+        if joint_names is None and self.n_joints == len(self.JOINT_NAMES):
+            joint_names = self.JOINT_NAMES
+            if joint_groups is None:
+                joint_groups = self.JOINT_GROUPS
+        self.joint_names = list(joint_names) if joint_names is not None else []
+        if self.joint_names and len(self.joint_names) != self.n_joints:
+            raise ValueError('%d joint names for %d joints' % (len(self.joint_names), self.n_joints))
+        groups = {g: sorted(self.joint_names.index(n) for n in names) for g, names in (joint_groups or {}).items()}
+        groups.setdefault('all', list(range(self.n_joints)))
+        self.groups = groups
+        self._set_thresholds(thresholds)
+        self._set_edges(score_edges)
+        self._tables = {}                 # device -> int64 [J, S + 2, T + 1], the kernel adds into it
+        self._host = torch.zeros(self.n_joints, self.S + 2, self.T + 1, dtype=torch.int64)    # merged, loaded, reduced
+        self._identity = {}               # (device, B) -> (m, b) of `add`
+
+    def _set_thresholds(self, thresholds):
+        thr = _fp32_ascending(thresholds, self.MAX_THRESHOLDS, 'thresholds')
+        self.thresholds = torch.tensor(thr, dtype=torch.float64)
+        self.T = len(thr)
+        self._thr_arg = (ctypes.c_double * self.T)(*thr)          # host array, passed by value to the kernel
+
+    def _set_edges(self, score_edges):
+        edges = _fp32_ascending(score_edges, self.MAX_EDGES, 'score edges')
+        self.score_edges = torch.tensor(edges, dtype=torch.float64)
+        self.S = len(edges)
+        self._edges_arg = (ctypes.c_double * self.S)(*edges)      # host array, passed by value to the kernel
+
+    # ------------------------------------------------------------------ adding batches
+    def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b, score):
+        """Add a batch given in normalised coords (back-projected in fp64 as in `PCKhEvaluator.add_normalized`) with its
+        scores, f32 `[B, J]` on the device (any view, e.g. `stats['peak']`): one kernel, no reduction and no host
+        synchronisation."""
+        B, J = norm_pred.shape[0], norm_pred.shape[1]
+        if J != self.n_joints:
+            raise ValueError('%d joints, the table has %d' % (J, self.n_joints))
+        if tuple(score.shape) != (B, J):
+            raise ValueError('scores of shape %s for %d x %d joints' % (tuple(score.shape), B, J))
+        dev = norm_pred.device
+        pred = norm_pred.detach().to(torch.float32).contiguous()
+        target = norm_target.detach().to(device=dev, dtype=torch.float32).contiguous()
+        m = transform_m.to(device=dev, dtype=torch.float64).contiguous()
+        b = transform_b.to(device=dev, dtype=torch.float64).reshape(B, 2).contiguous()
+        mask = joint_mask.to(device=dev, dtype=torch.float32).contiguous()
+        head = head_lengths.to(device=dev, dtype=torch.float64).contiguous()
+        score = score.detach().to(device=dev, dtype=torch.float32).contiguous()
+        table = self._tables.get(dev)
+        if table is None:
+            table = self._tables[dev] = torch.zeros_like(self._host, device=dev)
+        call('dsnt_score_hist', ptr(pred), ptr(target), ptr(m), ptr(b), ptr(mask), ptr(head), ptr(score),
+             self._edges_arg, self.S, self._thr_arg, self.T, ptr(table), B, J)
+
+    def add(self, pred, target, joint_mask, head_lengths, score):
+        """Add a batch whose coords are already in image space."""
+        B, dev = pred.shape[0], pred.device
+        ident = self._identity.get((dev, B))
+        if ident is None:
+            ident = self._identity[dev, B] = (torch.eye(2, dtype=torch.float64, device=dev).repeat(B, 1, 1),
+                                              torch.zeros(B, 2, dtype=torch.float64, device=dev))
+        self.add_normalized(pred, target, joint_mask, head_lengths, *ident, score)
+
+    def reset(self):
+        for t in self._tables.values():
+            t.zero_()
+        self._host.zero_()
+
+    # ------------------------------------------------------------------ reading results
+    def counts(self):
+        """The table, int64 [J, S + 2, T + 1] on the host."""
+        total = self._host.clone()
+        for t in self._tables.values():
+            total += t.cpu()
+        return total
+
+    # the `name` and `threshold` lookups are `PCKhCurve`'s (as `ErrorField` takes `_rows`): they read `groups`,
+    # `joint_names`, `n_joints`, `thresholds` and `T` only
+    _rows = PCKhCurve._rows
+    _index = PCKhCurve._index
+
+    def _hits(self, counts, threshold, name):
+        """(hits, support) per score row, int64 numpy [S + 2], of the joints of `name` at one constructed threshold."""
+        k = self._index(threshold)
+        table = counts[self._rows(name)].sum(0).numpy()
+        return table[:, :k + 1].sum(1), table.sum(1)
+
+    def accuracy(self, threshold=0.5, name='total_mpii'):
+        """`(rate f64 [S + 2], support int64 [S + 2])`: the hit rate of every score row (the last is the unscored row),
+        NaN where the row is empty."""
+        hits, n = self._hits(self.counts(), threshold, name)
+        return _ratio(hits, n), n
+
+    def risk_coverage(self, threshold=0.5, name='total_mpii'):
+        """What is kept, and how good it is, at each of the S + 1 cuts on the score: a dict of `cut` f64, `kept` int64,
+        `coverage` f64 and `pckh` f64.  With `higher_is_better` cut c keeps the joints with `score >= cut[c]`, cut =
+        [-inf, e_0, ..., e_{S-1}]; otherwise those with `score < cut[c]`, cut = [e_0, ..., e_{S-1}, +inf].  `coverage` =
+        kept / valid, where valid counts the unscored joints too, which no cut keeps; `pckh` is NaN where nothing is kept."""
+        hits, n = self._hits(self.counts(), threshold, name)
+        edges = self.score_edges.numpy()
+        if self.higher_is_better:         # cut c keeps the score rows >= c
+            cut = np.concatenate(([-np.inf], edges))
+            kept, good = n[:-1][::-1].cumsum()[::-1], hits[:-1][::-1].cumsum()[::-1]
+        else:                             # cut c keeps the score rows <= c
+            cut = np.concatenate((edges, [np.inf]))
+            kept, good = n[:-1].cumsum(), hits[:-1].cumsum()
+        return {'cut': cut, 'kept': kept.copy(), 'coverage': _ratio(kept, np.full_like(kept, n.sum())),
+                'pckh': _ratio(good, kept)}
+
+    def operating_point(self, min_pckh, threshold=0.5, name='total_mpii'):
+        """`(cut, coverage, pckh)` of the cut that keeps the most joints while their PCKh is at least `min_pckh` (the
+        loosest such cut where several keep as many); None if no cut that keeps a joint reaches it."""
+        rc = self.risk_coverage(threshold, name)
+        order = range(self.S + 1) if self.higher_is_better else range(self.S, -1, -1)      # loosest cut first
+        best = None
+        for c in order:
+            if rc['kept'][c] > 0 and rc['pckh'][c] >= min_pckh and (best is None or rc['kept'][c] > rc['kept'][best]):
+                best = c
+        return None if best is None else (float(rc['cut'][best]), float(rc['coverage'][best]), float(rc['pckh'][best]))
+
+    def _calibrated_row(self, hits, n):
+        """f32 [S + 2]: P(hit | score row), monotone over the rows with support (`_pav`); a scored row without support
+        takes the value of the nearest supported row below it in score, else the nearest above; the unscored row its own
+        rate.  NaN where there is nothing to go by."""
+        S = self.S
+        pools = _pav([int(v) for v in hits[:S + 1]], [int(v) for v in n[:S + 1]], self.higher_is_better)
+        row = np.full(S + 2, np.nan, np.float32)
+        above = next((p for p in pools if p is not None), None)    # for the rows below the first supported one
+        below = None
+        for r in range(S + 1):
+            below = pools[r] if pools[r] is not None else below
+            pool = below if below is not None else above
+            if pool is not None:
+                row[r] = np.float32(pool[0] / pool[1])
+        if n[S + 1] > 0:
+            row[S + 1] = np.float32(int(hits[S + 1]) / int(n[S + 1]))
+        return row
+
+    def calibration(self, threshold=0.5, name=None, score=None):
+        """A `ScoreCalibration` of P(joint within `threshold` | score): with `name=None` one row of values per joint,
+        otherwise one shared row from that joint or group.  `score` names the statistic this table was fed, which
+        `predict(calibration=)` will apply it to (`stat_score`); by default 'peak' if `higher_is_better`, else 'spread'."""
+        counts = self.counts()
+        names = range(self.n_joints) if name is None else [name]
+        values = np.stack([self._calibrated_row(*self._hits(counts, threshold, nm)) for nm in names])
+        if score is None:
+            score = 'peak' if self.higher_is_better else 'spread'
+        return ScoreCalibration(self.score_edges, values, score)
+
+    # ------------------------------------------------------------------ combining and saving
+    def _take(self, counts):
+        """Make `counts` (host) the whole state."""
+        for t in self._tables.values():
+            t.zero_()
+        self._host = counts.to(device='cpu', dtype=torch.int64).clone()
+
+    def merge(self, other):
+        if (other.n_joints != self.n_joints or not torch.equal(other.thresholds, self.thresholds)
+                or not torch.equal(other.score_edges, self.score_edges)):
+            raise ValueError('merge needs the same joints and identical score edges and thresholds')
+        self._host += other.counts()
+
+    def state_dict(self):
+        return {'score_edges': self.score_edges.clone(), 'thresholds': self.thresholds.clone(),
+                'higher_is_better': self.higher_is_better, 'table': self.counts()}
+
+    def load_state_dict(self, state):
+        table, thresholds, edges = state['table'], state['thresholds'], state['score_edges']
+        if table.dim() != 3 or tuple(table.shape) != (self.n_joints, edges.numel() + 2, thresholds.numel() + 1):
+            raise ValueError('table of shape %s for %d joints, %d score edges and %d thresholds'
+                             % (tuple(table.shape), self.n_joints, edges.numel(), thresholds.numel()))
+        self._set_thresholds(thresholds.cpu().numpy())
+        self._set_edges(edges.cpu().numpy())
+        self.higher_is_better = bool(state['higher_is_better'])
+        self._tables = {}                 # (their shape may have changed)
+        self._take(table)
+
+    def all_reduce(self, group=None):
+        """Sum the table over the ranks of a `torch.distributed` group; nothing to do in a single process."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        counts = self.counts()
+        if dist.get_backend(group) == 'nccl':
+            counts = counts.cuda()
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
+        self._take(counts)
+
+
+class ScoreCalibration:
+    """A step function of a per-joint score: `values[j][r]` for the score row `r` of `Reliability` (`values` f32
+    `[J, S + 2]`, or `[1, S + 2]` shared by all joints; the last column answers a NaN score).  `score` names the statistic
+    it was fitted on, for `stat_score`.  Calling it applies it on the device (`dsnt_score_lookup`): one launch, and no
+    host synchronisation once `values` has been uploaded to that device."""
+
+    MAX_EDGES = Reliability.MAX_EDGES
+
+    def __init__(self, score_edges, values, score='peak'):
+        self.load_state_dict({'score_edges': score_edges, 'values': values, 'score': score})
+
+    def state_dict(self):
+        return {'score_edges': self.score_edges.clone(), 'values': self.values.clone(), 'score': self.score}
+
+    def load_state_dict(self, state):
+        edges = _fp32_ascending(torch.as_tensor(state['score_edges']).cpu().numpy(), self.MAX_EDGES, 'score edges')
+        values = torch.as_tensor(state['values']).detach().to(device='cpu', dtype=torch.float32).contiguous().clone()
+        if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] != len(edges) + 2:
+            raise ValueError('values of shape %s for %d score edges' % (tuple(values.shape), len(edges)))
+        self.score_edges = torch.tensor(edges, dtype=torch.float64)
+        self.S = len(edges)
+        self._edges_arg = (ctypes.c_double * self.S)(*edges)      # host array, passed by value to the kernel
+        self.values = values
+        self.score = str(state['score'])
+        self._values = {}                 # device -> the values there
+
+    def __call__(self, score):
+        """The value of every score: f32, the shape of `score` (`[..., J]` where the values are per joint)."""
+        rows = self.values.shape[0]
+        if rows > 1 and (score.dim() < 1 or score.shape[-1] != rows):
+            raise ValueError('scores of shape %s for values of %d joints' % (tuple(score.shape), rows))
+        s = score.detach().to(torch.float32).contiguous()
+        out = torch.empty_like(s)
+        if s.numel():
+            values = self._values.get(s.device)
+            if values is None:
+                values = self._values[s.device] = self.values.to(s.device)
+            call('dsnt_score_lookup', ptr(s), self._edges_arg, self.S, ptr(values), int(rows > 1), ptr(out), s.numel(),
+                 rows)
+        return out
+
+
+def stat_score(stats, name):
+    """The score called `name` of a statistics dict (`inference.STATS_DOC`), f32 `[B, J]`: 'peak' (higher is better), or
+    'spread' = `sqrt(trace(cov_image))` in pixels (lower is better)."""
+    if name == 'peak':
+        return stats['peak']
+    if name == 'spread':
+        cov = stats['cov_image']
+        return torch.sqrt(cov[..., 0, 0] + cov[..., 1, 1]).float()
+    raise KeyError('no score called %r: peak or spread' % (name,))

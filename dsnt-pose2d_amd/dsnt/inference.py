@@ -17,7 +17,7 @@ launch (`flip_merge_head`, `dsnt_flip_merge_head`) merges the last stack's logit
 (`dsnt_crop_affine`), then evaluated as `predict` does, and the joints come back in the images' pixels.
 
 `return_stats=True` on the three adds a confidence and a spread per joint, taken from the heat-map the coordinates come
-from (see `STATS_DOC`).
+from (see `STATS_DOC`); `calibration=` (an `evaluator.ScoreCalibration`) turns one of them into `p_correct`.
 """
 import ctypes
 import time
@@ -104,8 +104,22 @@ STATS_DOC = """The per-joint statistics dict (`return_stats=True`, `flip_merge_h
   * `cov` f32 `[B, J, 3]`: `(vxx, vyy, vxy)` about that mean, normalised units;
   * `cov_image` f64 `[B, J, 2, 2]`: `transform_m^T . cov . transform_m`, the covariance in original-image pixels^2.
 For the 'gauss' strategy the map is the raw merged heat-map, no distribution: `peak`, `peak_index` and `mass` describe it
-as it is, and `mean`, `cov` and `cov_image` are NaN.  Nothing is calibrated to [0, 1]: `peak` (confidence, higher is
-better) and `sqrt(trace(cov_image))` (spread in pixels, lower is better) are the two quantities to threshold on."""
+as it is, and `mean`, `cov` and `cov_image` are NaN.  Nothing here is calibrated to [0, 1]: `peak` (confidence, higher is
+better) and `sqrt(trace(cov_image))` (spread in pixels, lower is better) are the two quantities to threshold on, and
+`evaluator.Reliability` on a validation set says where.  With `calibration=cal` (an `evaluator.ScoreCalibration` fitted
+there) the dict gains
+  * `p_correct` f32 `[B, J]`: `cal(stat_score(stats, cal.score))`, the validation set's P(joint within the PCKh threshold)
+    at this score (`dsnt_score_lookup`; NaN for a `predict_boxes` sample without a crop)."""
+
+
+def _calibrate(st, return_stats, calibration):
+    """Add `p_correct` to the statistics dict in the list `st` (empty without `return_stats`)."""
+    if calibration is None:
+        return
+    if not return_stats:
+        raise ValueError('dsnt: calibration= needs return_stats=True (p_correct is returned in the statistics dict)')
+    from .evaluator import stat_score
+    st[0]['p_correct'] = calibration(stat_score(st[0], calibration.score))
 
 
 def _cov_image(cov, tm):
@@ -197,7 +211,7 @@ def _set_heatmaps(model, hm):
 
 
 def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=False, return_normalized=False,
-            return_stats=False):
+            return_stats=False, calibration=None):
     """Joint positions in original-image pixels for a batch, on the device: f64 `[B, J, 2]`.
 
     `inputs` f32 `[B, 3, S, S]` on the device, or with `paired=True` the `[2B, 3, S, S]` `input_pair` of
@@ -216,7 +230,9 @@ def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=Fa
       * flip, 'dsnt' / 'gauss': from the fused launch itself (`dsnt_flip_merge_head_stats`);
       * flip, 'fc': `dsnt_heatmap_stats` on the post-activation map of the merged logits;
       * no flip: `dsnt_heatmap_stats` on the last stack's heat-maps (for an hourglass NOT `model.heatmaps`, which is the
-        first stack's) after the forward."""
+        first stack's) after the forward.
+    `calibration` (with `return_stats=True`): the dict also holds `p_correct`, one more launch; everything else keeps its
+    bits."""
     model.eval()
     S = 2 if (use_flipped and paired) else 1
     if inputs.size(0) % S:
@@ -245,17 +261,19 @@ def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=Fa
             coords = dutil.decode_heatmaps(out) if model.output_strat == 'gauss' else out.detach().float()
             img = torch.baddbmm(tb, coords.double(), tm)
             st = [_map_stats(_predicted_map(model), tm, model.output_strat != 'gauss')] if return_stats else []
+    _calibrate(st, return_stats, calibration)
     res = (img, coords) if return_normalized else (img,)
     res += tuple(st)
     return res if len(res) > 1 else res[0]
 
 
-def predict_dataset(model, dataset, use_flipped=True, batch_size=32, time_meter=None, return_stats=False):
+def predict_dataset(model, dataset, use_flipped=True, batch_size=32, time_meter=None, return_stats=False,
+                    calibration=None):
     """`generate_predictions` at any batch size: a CPU DoubleTensor `[len(dataset), J, 2]` of joint positions in
     original-image pixels, per sample what the batch-1 flip loop gives.  Predictions stay on the device until the
     one copy at the end; with a `time_meter` each batch is timed, which synchronises once per batch.
     `return_stats=True` returns `(predictions, stats)`: the statistics dict of `STATS_DOC` over the whole dataset as CPU
-    tensors, concatenated on the device and copied once like the predictions."""
+    tensors, concatenated on the device and copied once like the predictions; with `calibration`, `p_correct` among them."""
     model.cuda()
     model.eval()
     loader = DataLoader(dataset, batch_size, num_workers=0)
@@ -263,7 +281,7 @@ def predict_dataset(model, dataset, use_flipped=True, batch_size=32, time_meter=
     for batch in loader:
         start = time.perf_counter()
         img = predict(model, batch['input'].cuda(), batch['transform_m'].cuda(), batch['transform_b'].cuda(),
-                      use_flipped=use_flipped, return_stats=return_stats)
+                      use_flipped=use_flipped, return_stats=return_stats, calibration=calibration)
         if return_stats:
             img, st = img
             stats.append(st)
@@ -297,7 +315,7 @@ def _box_augment_for(specs, mean, std, device):
 
 
 def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_size=384, return_normalized=False,
-                  return_stats=False):
+                  return_stats=False, calibration=None):
     """Joint positions in original-image pixels for person boxes in full images: f64 `[B, J, 2]` on the device.
 
     `pool` a `data.ImagePool`; sample b is image `idx[b]` (int64 `[B]`) with the box matrix `matrix[b]` (f64
@@ -313,7 +331,7 @@ def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_si
     normalisation constants).  `return_normalized=True` returns `(image_coords, normalised f32 coords)`.
     `return_stats=True` appends the statistics dict of `STATS_DOC`; `cov_image` follows the transposed `transform_m`, so
     it is in the image's pixels for any invertible box matrix, and a sample without a crop has NaN statistics (its
-    `peak_index` is -1)."""
+    `peak_index` is -1).  With `calibration` the dict also holds `p_correct`, NaN for such a sample."""
     crops, valid = pool.crop(idx, matrix, crop_size)
     B, dev = crops.shape[0], crops.device
     aug = _box_augment_for(model.image_specs, mean, std, dev)
@@ -326,7 +344,7 @@ def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_si
     tm = s['transform_m'].transpose(1, 2).contiguous()
     img, coords, *st = predict(model, s['input_pair'] if use_flipped else s['input'], tm, s['transform_b'],
                                use_flipped=use_flipped, paired=use_flipped, return_normalized=True,
-                               return_stats=return_stats)
+                               return_stats=return_stats, calibration=calibration)
     img = torch.where(valid.view(B, 1, 1), img, float('nan'))
     res = (img, torch.where(valid.view(B, 1, 1), coords, float('nan'))) if return_normalized else (img,)
     if return_stats:

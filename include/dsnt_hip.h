@@ -798,6 +798,36 @@ int dsnt_error_field(const float* pred, const float* target, const double* m, co
                      const float* mask, const double* head, float threshold,
                      const double* edges, int bins, int64_t* counts, double* sums,
                      int B, int J, void* stream);
+/* Does the confidence know?  One launch ADDS a batch to a two-way histogram per joint: the score of a joint (any per-joint
+ * statistic, e.g. the heat-map's peak) against its normalised distance.  pred, target, m, b, mask, head, thresholds and T
+ * are dsnt_pckh_hist's, with the same checks; d is dsnt_pckh's distance (same fp64 expression) and the column k is
+ * dsnt_pckh_hist's: the smallest index with d <= thresholds[k], or T when there is none (beyond the last threshold, NaN,
+ * inf).  score: device f32 [B][J].  The row r is the number of score_edges that are <= the score widened to fp64: row 0 is
+ * score < e[0], row S is score >= e[S - 1], a score equal to an edge goes to the upper row, -inf to row 0, +inf to row S;
+ * a NaN score goes to row S + 1, the "unscored" row.  A joint with mask == 1 adds 1 to table[j][r][k]; other masks add
+ * nothing.  Summed over r the table is dsnt_pckh_hist's, bit for bit.
+ * score_edges: HOST double[S], 1 <= S <= DSNT_SCORE_HIST_MAX_S, finite and strictly ascending, passed by value to the
+ * kernel and padded with +inf, as the thresholds are (DSNT_ERR_ARG otherwise, nothing launched).  table: device u64
+ * [J][S + 2][T + 1]; the kernel only adds (64-bit integer atomics: order-independent, bit-reproducible), the caller zeroes.
+ * The grid and striding are dsnt_pckh_hist's.  While J * (S + 2) * (T + 1) <= DSNT_SCORE_HIST_LDS_CELLS each workgroup
+ * counts in a u32 LDS copy of the table and flushes its non-zero cells with one 64-bit atomic each; above that every joint
+ * adds to `table` directly.  dsnt_version() >= 126. */
+#define DSNT_SCORE_HIST_MAX_S 64
+#define DSNT_SCORE_HIST_LDS_CELLS 8192
+int dsnt_score_hist(const float* pred, const float* target, const double* m, const double* b,
+                    const float* mask, const double* head, const float* score,
+                    const double* score_edges, int S, const double* thresholds, int T,
+                    unsigned long long* table, int B, int J, void* stream);
+/* The table read back as a function of the score: out[i] = values[(per_joint ? i % J : 0) * (S + 2) + row(score[i])] for
+ * i in 0..n-1, row being dsnt_score_hist's rule (NaN scores read row S + 1).  score, out: device f32 [n] (n = B * J with
+ * per_joint); values: device f32 [J][S + 2], or [1][S + 2] when per_joint == 0; NaN entries pass through.  score_edges as
+ * above.  per_joint is 0 or 1, n >= 1, J >= 1 (DSNT_ERR_ARG otherwise, nothing launched).  Plain stores; the grid is
+ * min(ceil(n / DSNT_SCORE_LOOKUP_BLOCK), DSNT_SCORE_LOOKUP_MAX_BLOCKS) workgroups striding over n.
+ * dsnt_version() >= 126. */
+#define DSNT_SCORE_LOOKUP_BLOCK 256
+#define DSNT_SCORE_LOOKUP_MAX_BLOCKS 1024
+int dsnt_score_lookup(const float* score, const double* score_edges, int S, const float* values,
+                      int per_joint, float* out, int64_t n, int J, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation
  * data.py:118-226 (MPIIDataset.__getitem__, use_aug) batched on the device; semantics in csrc/augment.hip.
