@@ -4,7 +4,7 @@
 
 // ---------------------------------------------------------------- PCKh hits
 // Distance of joint i (of image n) between the back-projected prediction and target, in head lengths: one expression for
-// pckh_kernel, pckh_hist_kernel and error_field_kernel, so that the curve at a threshold holds the very hits of the
+// pckh_kernel, joint_table_kernel and error_field_kernel, so that the curve at a threshold holds the very hits of the
 // single-threshold kernel and the field's misses are exactly its non-hits.
 __device__ __forceinline__ double pckh_distance(const float* __restrict__ pred, const float* __restrict__ target,
                                                 const double* __restrict__ m, const double* __restrict__ b,
@@ -38,15 +38,31 @@ extern "C" int dsnt_pckh(const float* pred, const float* target, const double* m
     DSNT_CHECK_LAUNCH("dsnt_pckh");
 }
 
-// PCKh curve: a histogram of d per joint with the thresholds as bin edges (include/dsnt_hip.h: dsnt_pckh_hist).  Integer adds
-// only, so the table does not depend on the order of arrival.  At most DSNT_PCKH_HIST_MAX_BLOCKS workgroups stride over
-// B * J; with use_lds each counts in an LDS copy of the table (u32: a workgroup sees fewer than 2^31 joints) and flushes
-// its non-zero cells with one 64-bit atomic each, so the global traffic is bounded by grid x cells whatever the batch.
-static_assert(DSNT_PCKH_HIST_MAX_T % 8 == 0, "pckh_hist_kernel reads the edges eight at a time");
+// The ascending edges of `who` as a kernel takes them in its argument: the n of `host`, finite and strictly ascending, then
+// +inf to the end of `out`.  `what` names one of them in the messages.  0 or the error code.
+template <int N>
+static int ascending_arg(const char* who, const char* what, const double* host, int n, double (&out)[N]) {
+    for (int k = 0; k < N; ++k) out[k] = (double)INFINITY;
+    for (int k = 0; k < n; ++k) {
+        DSNT_REQUIRE(host[k] - host[k] == 0.0, DSNT_ERR_ARG, "%s: %s %d is not finite", who, what, k);
+        DSNT_REQUIRE(k == 0 || host[k] > host[k - 1], DSNT_ERR_ARG, "%s: %ss must be strictly ascending (index %d)", who,
+                     what, k);
+        out[k] = host[k];
+    }
+    return DSNT_OK;
+}
+
+// PCKh curve: a histogram of d per joint with the thresholds as bin edges (include/dsnt_hip.h: dsnt_pckh_hist), and score
+// against distance (dsnt_score_hist): the same with a second index, the row of the joint's score among the score edges,
+// so table[j][r][k] summed over r is the curve's table bit for bit.  Integer adds only, so the table does not depend on
+// the order of arrival.  At most DSNT_PCKH_HIST_MAX_BLOCKS workgroups stride over B * J; with use_lds each counts in an
+// LDS copy of the table (u32: a workgroup sees fewer than 2^31 joints) and flushes its non-zero cells with one 64-bit
+// atomic each, so the global traffic is bounded by grid x cells whatever the batch.
+static_assert(DSNT_PCKH_HIST_MAX_T % 8 == 0, "pckh_column reads the edges eight at a time");
 struct pckh_thresholds { double t[DSNT_PCKH_HIST_MAX_T]; };
-// Bin of a distance, for pckh_hist_kernel and score_hist_kernel.  Ascending edges: the thresholds d exceeds are a prefix,
-// and their number is the bin.  The index is uniform, so eight edges are one scalar load of the kernel argument; the host
-// pads the edges with +inf, which only a NaN exceeds (NaN exceeds all: bin T).
+// Bin of a distance.  Ascending edges: the thresholds d exceeds are a prefix, and their number is the bin.  The index is
+// uniform, so eight edges are one scalar load of the kernel argument; the host pads the edges with +inf, which only a NaN
+// exceeds (NaN exceeds all: bin T).
 __device__ __forceinline__ int pckh_column(const pckh_thresholds& thr, double d, int T) {
     int k = 0;
     for (int q = 0; q < T; q += 8) {
@@ -55,77 +71,12 @@ __device__ __forceinline__ int pckh_column(const pckh_thresholds& thr, double d,
     }
     return min(k, T);
 }
-__global__ __launch_bounds__(DSNT_PCKH_HIST_BLOCK)
-void pckh_hist_kernel(const float* __restrict__ pred, const float* __restrict__ target, const double* __restrict__ m,
-                      const double* __restrict__ b, const float* __restrict__ mask, const double* __restrict__ head,
-                      const pckh_thresholds thr, int T, unsigned long long* table, double* dist, int B, int J, int use_lds) {
-    __shared__ unsigned cnt[DSNT_PCKH_HIST_LDS_CELLS];
-    const int cells = J * (T + 1);
-    if (use_lds) {
-        for (int c = threadIdx.x; c < cells; c += blockDim.x) cnt[c] = 0u;
-        __syncthreads();
-    }
-    const long total = (long)B * J;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long n = i / J;
-        const int j = (int)(i - n * J);
-        const double d = pckh_distance(pred, target, m, b, head, i, n);
-        const bool v = mask[i] == 1.f;
-        if (dist) dist[i] = v ? d : (double)NAN;
-        if (!v) continue;
-        const int c = j * (T + 1) + pckh_column(thr, d, T);
-        if (use_lds) atomicAdd(cnt + c, 1u);
-        else atomicAdd(table + c, 1ull);
-    }
-    if (use_lds) {
-        __syncthreads();
-        for (int c = threadIdx.x; c < cells; c += blockDim.x) {
-            const unsigned v = cnt[c];
-            if (v) atomicAdd(table + c, (unsigned long long)v);
-        }
-    }
-}
-// The T <= DSNT_PCKH_HIST_MAX_T thresholds of `who` as the kernels take them: finite, strictly ascending, padded with +inf.
-// 0 or the error code.
-static int pckh_thresholds_arg(const char* who, const double* thresholds, int T, pckh_thresholds* out) {
-    for (int k = 0; k < DSNT_PCKH_HIST_MAX_T; ++k) out->t[k] = (double)INFINITY;
-    for (int k = 0; k < T; ++k) {
-        const double t = thresholds[k];
-        DSNT_REQUIRE(t - t == 0.0, DSNT_ERR_ARG, "%s: threshold %d is not finite", who, k);
-        DSNT_REQUIRE(k == 0 || t > thresholds[k - 1], DSNT_ERR_ARG, "%s: thresholds must be strictly ascending (index %d)",
-                     who, k);
-        out->t[k] = t;
-    }
-    return DSNT_OK;
-}
-extern "C" int dsnt_pckh_hist(const float* pred, const float* target, const double* m, const double* b,
-                              const float* mask, const double* head, const double* thresholds, int T,
-                              unsigned long long* table, double* dist, int B, int J, void* stream) {
-    DSNT_REQUIRE(pred && target && m && b && mask && head && thresholds && table && B > 0 && J > 0,
-                 DSNT_ERR_ARG, "dsnt_pckh_hist: bad argument");
-    DSNT_REQUIRE(T >= 1 && T <= DSNT_PCKH_HIST_MAX_T, DSNT_ERR_ARG, "dsnt_pckh_hist: T=%d outside 1..%d", T,
-                 DSNT_PCKH_HIST_MAX_T);
-    DSNT_REQUIRE((long)J * (T + 1) <= 0x7fffffffL, DSNT_ERR_ARG, "dsnt_pckh_hist: J * (T + 1) does not fit an int");
-    pckh_thresholds thr;
-    if (const int rc = pckh_thresholds_arg("dsnt_pckh_hist", thresholds, T, &thr)) return rc;
-    const long total = (long)B * J;
-    const long want = (total + DSNT_PCKH_HIST_BLOCK - 1) / DSNT_PCKH_HIST_BLOCK;
-    const int grid = (int)(want < DSNT_PCKH_HIST_MAX_BLOCKS ? want : DSNT_PCKH_HIST_MAX_BLOCKS);
-    const int use_lds = (long)J * (T + 1) <= DSNT_PCKH_HIST_LDS_CELLS ? 1 : 0;
-    DSNT_LAUNCH(pckh_hist_kernel, dim3(grid), dim3(DSNT_PCKH_HIST_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
-                mask, head, thr, T, table, dist, B, J, use_lds);
-    DSNT_CHECK_LAUNCH("dsnt_pckh_hist");
-}
-
-// Score against distance (include/dsnt_hip.h: dsnt_score_hist): pckh_hist_kernel with a second index, the row of the
-// joint's score among the score edges, so table[j][r][k] summed over r is pckh_hist_kernel's table bit for bit.  Same grid,
-// same striding, same two accumulation paths; the LDS copy is u32 [J][S + 2][T + 1] (32 KiB at the limit).
 static_assert(DSNT_SCORE_HIST_MAX_S % 8 == 0, "score_row reads the edges eight at a time");
 static_assert(DSNT_SCORE_HIST_LDS_CELLS * sizeof(unsigned) <= 64 * 1024, "the LDS table is a static allocation");
 struct score_edges { double e[DSNT_SCORE_HIST_MAX_S]; };
 // Row of a score: the number of edges that are <= the score (ascending edges: those are a prefix), S + 1 for a NaN.  The
 // host pads the edges with +inf, which only a score of +inf reaches: capped at S.  The index is uniform, so eight edges
-// are one scalar load of the kernel argument, as in pckh_hist_kernel.
+// are one scalar load of the kernel argument, as in pckh_column.
 __device__ __forceinline__ int score_row(const score_edges& edges, float score, int S) {
     const double s = (double)score;
     int r = 0;
@@ -135,24 +86,47 @@ __device__ __forceinline__ int score_row(const score_edges& edges, float score, 
     }
     return s != s ? S + 1 : min(r, S);
 }
+// The rows of a joint in the table, as the kernel's argument: one (the curve; nothing travels with the launch), or the
+// S + 2 score rows.
+struct one_row {
+    static constexpr bool scored = false;
+    __host__ __device__ int rows() const { return 1; }
+    __device__ int row(long) const { return 0; }
+};
+struct score_rows {
+    static constexpr bool scored = true;
+    const float* __restrict__ score;
+    score_edges edges;
+    int S;
+    __host__ __device__ int rows() const { return S + 2; }
+    __device__ int row(long i) const { return score_row(edges, score[i], S); }
+};
+// The LDS copy is u32 [J][rows][T + 1], LDS_CELLS at the most (32 KiB for the scores).  Only the curve has `dist`, which
+// takes NaN where the mask is not 1; with scores a joint that is masked out is skipped before its distance.  `by` comes
+// last and the curve reads the mask after the distance: its instantiation is then instruction for instruction the
+// kernel it had to itself, with the same argument layout.
+template <int LDS_CELLS, typename Rows>
 __global__ __launch_bounds__(DSNT_PCKH_HIST_BLOCK)
-void score_hist_kernel(const float* __restrict__ pred, const float* __restrict__ target, const double* __restrict__ m,
-                       const double* __restrict__ b, const float* __restrict__ mask, const double* __restrict__ head,
-                       const float* __restrict__ score, const score_edges edges, int S, const pckh_thresholds thr, int T,
-                       unsigned long long* table, int B, int J, int use_lds) {
-    __shared__ unsigned cnt[DSNT_SCORE_HIST_LDS_CELLS];
-    const int cells = J * (S + 2) * (T + 1);
+void joint_table_kernel(const float* __restrict__ pred, const float* __restrict__ target, const double* __restrict__ m,
+                        const double* __restrict__ b, const float* __restrict__ mask, const double* __restrict__ head,
+                        const pckh_thresholds thr, int T, unsigned long long* table, double* dist, int B, int J,
+                        int use_lds, const Rows by) {
+    __shared__ unsigned cnt[LDS_CELLS];
+    const int cells = J * by.rows() * (T + 1);
     if (use_lds) {
         for (int c = threadIdx.x; c < cells; c += blockDim.x) cnt[c] = 0u;
         __syncthreads();
     }
     const long total = (long)B * J;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        if (!(mask[i] == 1.f)) continue;
+        if (Rows::scored && !(mask[i] == 1.f)) continue;
         const long n = i / J;
         const int j = (int)(i - n * J);
         const double d = pckh_distance(pred, target, m, b, head, i, n);
-        const int c = (j * (S + 2) + score_row(edges, score[i], S)) * (T + 1) + pckh_column(thr, d, T);
+        const bool v = Rows::scored || mask[i] == 1.f;
+        if (!Rows::scored && dist) dist[i] = v ? d : (double)NAN;
+        if (!v) continue;
+        const int c = (j * by.rows() + by.row(i)) * (T + 1) + pckh_column(thr, d, T);
         if (use_lds) atomicAdd(cnt + c, 1u);
         else atomicAdd(table + c, 1ull);
     }
@@ -164,18 +138,34 @@ void score_hist_kernel(const float* __restrict__ pred, const float* __restrict__
         }
     }
 }
-// The edges of either entry point: S in range, finite, strictly ascending; padded with +inf.  0 or the error code.
-static int score_edges_arg(const char* who, const double* score_edges_host, int S, score_edges* out) {
-    DSNT_REQUIRE(S >= 1 && S <= DSNT_SCORE_HIST_MAX_S, DSNT_ERR_ARG, "%s: S=%d outside 1..%d", who, S, DSNT_SCORE_HIST_MAX_S);
-    for (int k = 0; k < DSNT_SCORE_HIST_MAX_S; ++k) out->e[k] = (double)INFINITY;
-    for (int k = 0; k < S; ++k) {
-        const double e = score_edges_host[k];
-        DSNT_REQUIRE(e - e == 0.0, DSNT_ERR_ARG, "%s: score edge %d is not finite", who, k);
-        DSNT_REQUIRE(k == 0 || e > score_edges_host[k - 1], DSNT_ERR_ARG,
-                     "%s: score edges must be strictly ascending (index %d)", who, k);
-        out->e[k] = e;
-    }
-    return DSNT_OK;
+// Both entry points from here on: the table fits an int index (`cells` is how the message writes its size), the thresholds,
+// one workgroup per DSNT_PCKH_HIST_BLOCK joints up to DSNT_PCKH_HIST_MAX_BLOCKS, and the LDS copy if the table fits it.
+template <int LDS_CELLS, typename Rows>
+static int joint_table_launch(const char* who, const char* cells, const float* pred, const float* target, const double* m,
+                              const double* b, const float* mask, const double* head, const Rows& by,
+                              const double* thresholds, int T, unsigned long long* table, double* dist, int B, int J,
+                              void* stream) {
+    const long n_cells = (long)J * by.rows() * (T + 1);
+    DSNT_REQUIRE(n_cells <= 0x7fffffffL, DSNT_ERR_ARG, "%s: %s does not fit an int", who, cells);
+    pckh_thresholds thr;
+    if (const int rc = ascending_arg(who, "threshold", thresholds, T, thr.t)) return rc;
+    const long want = ((long)B * J + DSNT_PCKH_HIST_BLOCK - 1) / DSNT_PCKH_HIST_BLOCK;
+    const int grid = (int)(want < DSNT_PCKH_HIST_MAX_BLOCKS ? want : DSNT_PCKH_HIST_MAX_BLOCKS);
+    const int use_lds = n_cells <= LDS_CELLS ? 1 : 0;
+    const auto kernel = joint_table_kernel<LDS_CELLS, Rows>;
+    DSNT_LAUNCH(kernel, dim3(grid), dim3(DSNT_PCKH_HIST_BLOCK), 0, (hipStream_t)stream, pred, target, m, b, mask, head,
+                thr, T, table, dist, B, J, use_lds, by);
+    DSNT_CHECK_LAUNCH(who);
+}
+extern "C" int dsnt_pckh_hist(const float* pred, const float* target, const double* m, const double* b,
+                              const float* mask, const double* head, const double* thresholds, int T,
+                              unsigned long long* table, double* dist, int B, int J, void* stream) {
+    DSNT_REQUIRE(pred && target && m && b && mask && head && thresholds && table && B > 0 && J > 0,
+                 DSNT_ERR_ARG, "dsnt_pckh_hist: bad argument");
+    DSNT_REQUIRE(T >= 1 && T <= DSNT_PCKH_HIST_MAX_T, DSNT_ERR_ARG, "dsnt_pckh_hist: T=%d outside 1..%d", T,
+                 DSNT_PCKH_HIST_MAX_T);
+    return joint_table_launch<DSNT_PCKH_HIST_LDS_CELLS>("dsnt_pckh_hist", "J * (T + 1)", pred, target, m, b, mask, head,
+                                                        one_row{}, thresholds, T, table, dist, B, J, stream);
 }
 extern "C" int dsnt_score_hist(const float* pred, const float* target, const double* m, const double* b,
                                const float* mask, const double* head, const float* score, const double* score_edges_host,
@@ -185,19 +175,12 @@ extern "C" int dsnt_score_hist(const float* pred, const float* target, const dou
                  J > 0, DSNT_ERR_ARG, "dsnt_score_hist: bad argument");
     DSNT_REQUIRE(T >= 1 && T <= DSNT_PCKH_HIST_MAX_T, DSNT_ERR_ARG, "dsnt_score_hist: T=%d outside 1..%d", T,
                  DSNT_PCKH_HIST_MAX_T);
-    score_edges edges;
-    if (const int rc = score_edges_arg("dsnt_score_hist", score_edges_host, S, &edges)) return rc;
-    DSNT_REQUIRE((long)J * (S + 2) * (T + 1) <= 0x7fffffffL, DSNT_ERR_ARG,
-                 "dsnt_score_hist: J * (S + 2) * (T + 1) does not fit an int");
-    pckh_thresholds thr;
-    if (const int rc = pckh_thresholds_arg("dsnt_score_hist", thresholds, T, &thr)) return rc;
-    const long total = (long)B * J;
-    const long want = (total + DSNT_PCKH_HIST_BLOCK - 1) / DSNT_PCKH_HIST_BLOCK;
-    const int grid = (int)(want < DSNT_PCKH_HIST_MAX_BLOCKS ? want : DSNT_PCKH_HIST_MAX_BLOCKS);
-    const int use_lds = (long)J * (S + 2) * (T + 1) <= DSNT_SCORE_HIST_LDS_CELLS ? 1 : 0;
-    DSNT_LAUNCH(score_hist_kernel, dim3(grid), dim3(DSNT_PCKH_HIST_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
-                mask, head, score, edges, S, thr, T, table, B, J, use_lds);
-    DSNT_CHECK_LAUNCH("dsnt_score_hist");
+    DSNT_REQUIRE(S >= 1 && S <= DSNT_SCORE_HIST_MAX_S, DSNT_ERR_ARG, "dsnt_score_hist: S=%d outside 1..%d", S,
+                 DSNT_SCORE_HIST_MAX_S);
+    score_rows by{score, {}, S};
+    if (const int rc = ascending_arg("dsnt_score_hist", "score edge", score_edges_host, S, by.edges.e)) return rc;
+    return joint_table_launch<DSNT_SCORE_HIST_LDS_CELLS>("dsnt_score_hist", "J * (S + 2) * (T + 1)", pred, target, m, b,
+                                                         mask, head, by, thresholds, T, table, nullptr, B, J, stream);
 }
 
 // out[i] = values[joint of i][row of score[i]] (include/dsnt_hip.h: dsnt_score_lookup): the calibration table applied to a
@@ -214,8 +197,10 @@ extern "C" int dsnt_score_lookup(const float* score, const double* score_edges_h
                                  int per_joint, float* out, int64_t n, int J, void* stream) {
     DSNT_REQUIRE(score && score_edges_host && values && out && n > 0 && J > 0 && (per_joint == 0 || per_joint == 1),
                  DSNT_ERR_ARG, "dsnt_score_lookup: bad argument");
+    DSNT_REQUIRE(S >= 1 && S <= DSNT_SCORE_HIST_MAX_S, DSNT_ERR_ARG, "dsnt_score_lookup: S=%d outside 1..%d", S,
+                 DSNT_SCORE_HIST_MAX_S);
     score_edges edges;
-    if (const int rc = score_edges_arg("dsnt_score_lookup", score_edges_host, S, &edges)) return rc;
+    if (const int rc = ascending_arg("dsnt_score_lookup", "score edge", score_edges_host, S, edges.e)) return rc;
     DSNT_REQUIRE((long)J * (S + 2) <= 0x7fffffffL, DSNT_ERR_ARG, "dsnt_score_lookup: J * (S + 2) does not fit an int");
     const long want = ((long)n + DSNT_SCORE_LOOKUP_BLOCK - 1) / DSNT_SCORE_LOOKUP_BLOCK;
     const int grid = (int)(want < DSNT_SCORE_LOOKUP_MAX_BLOCKS ? want : DSNT_SCORE_LOOKUP_MAX_BLOCKS);
@@ -239,7 +224,7 @@ struct error_field_edges { double e[DSNT_ERROR_FIELD_MAX_BINS + 1]; };          
 static_assert(DSNT_ERROR_FIELD_MAX_BINS % 8 == 0, "error_field_cell reads the edges eight at a time");
 // Cell [by][bx] of a target inside the frame.  Along an axis: the number of edges e[1..bins] that are <= t, capped at
 // bins - 1, which is e[k] <= t < e[k + 1] with the last edge closed.  t is finite and the padding is +inf, so the padding
-// never counts; the index is uniform, so eight edges are one scalar load of the kernel argument, as in pckh_hist_kernel.
+// never counts; the index is uniform, so eight edges are one scalar load of the kernel argument, as in pckh_column.
 __device__ __forceinline__ int error_field_cell(const error_field_edges& edges, double tx, double ty, int bins) {
     int kx = 0, ky = 0;
     for (int q = 0; q < bins; q += 8) {
@@ -357,14 +342,7 @@ extern "C" int dsnt_error_field(const float* pred, const float* target, const do
     DSNT_REQUIRE(bins >= 1 && bins <= DSNT_ERROR_FIELD_MAX_BINS, DSNT_ERR_ARG, "dsnt_error_field: bins=%d outside 1..%d",
                  bins, DSNT_ERROR_FIELD_MAX_BINS);
     error_field_edges e;
-    for (int k = 0; k <= DSNT_ERROR_FIELD_MAX_BINS; ++k) e.e[k] = (double)INFINITY;
-    for (int k = 0; k <= bins; ++k) {
-        const double t = edges[k];
-        DSNT_REQUIRE(t - t == 0.0, DSNT_ERR_ARG, "dsnt_error_field: edge %d is not finite", k);
-        DSNT_REQUIRE(k == 0 || t > edges[k - 1], DSNT_ERR_ARG,
-                     "dsnt_error_field: edges must be strictly ascending (index %d)", k);
-        e.e[k] = t;
-    }
+    if (const int rc = ascending_arg("dsnt_error_field", "edge", edges, bins + 1, e.e)) return rc;
     const double hi = e.e[bins];
     DSNT_LAUNCH(error_field_kernel, dim3(J), dim3(DSNT_ERROR_FIELD_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
                 mask, head, threshold, e, hi, bins, (long long*)counts, sums, B, J);

@@ -16,6 +16,9 @@ is a cumulative sum of that table taken when the user asks.
 `Reliability` asks whether a per-joint confidence knows when the joint is right: one launch per batch adds into a table of
 score row against distance column (`dsnt_score_hist`), from which accuracy per score, risk against
 coverage, an operating point and a monotone `ScoreCalibration` (applied on the device by `dsnt_score_lookup`) are read.
+
+The three table evaluators keep their joint names and their state in `_JointTables`; all four prepare a batch with
+`_batch_args`.
 """
 import ctypes
 
@@ -23,6 +26,18 @@ import numpy as np
 import torch
 
 from ._lib import ptr, call
+
+
+def _batch_args(norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b):
+    """`(pred, target, m, b, mask, head)` as the kernels take them: f32, f32, f64, f64 `[B, 2]`, f32, f64, contiguous and
+    on `norm_pred`'s device."""
+    B, dev = norm_pred.shape[0], norm_pred.device
+    return (norm_pred.detach().to(torch.float32).contiguous(),
+            norm_target.detach().to(device=dev, dtype=torch.float32).contiguous(),
+            transform_m.to(device=dev, dtype=torch.float64).contiguous(),
+            transform_b.to(device=dev, dtype=torch.float64).reshape(B, 2).contiguous(),
+            joint_mask.to(device=dev, dtype=torch.float32).contiguous(),
+            head_lengths.to(device=dev, dtype=torch.float64).contiguous())
 
 
 class _Meter:
@@ -92,16 +107,10 @@ class PCKhEvaluator:
         `coords @ transform_m + transform_b` (fp64) on the device, then thresholded."""
         B, J = norm_pred.shape[0], norm_pred.shape[1]
         dev = norm_pred.device
-        pred = norm_pred.detach().to(torch.float32).contiguous()
-        target = norm_target.detach().to(device=dev, dtype=torch.float32).contiguous()
-        m = transform_m.to(device=dev, dtype=torch.float64).contiguous()
-        b = transform_b.to(device=dev, dtype=torch.float64).reshape(B, 2).contiguous()
-        mask = joint_mask.to(device=dev, dtype=torch.float32).contiguous()
-        head = head_lengths.to(device=dev, dtype=torch.float64).contiguous()
+        args = _batch_args(norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b)
         hits = torch.empty(B, J, device=dev)
         valid = torch.empty(B, J, device=dev)
-        call('dsnt_pckh', ptr(pred), ptr(target), ptr(m), ptr(b), ptr(mask), ptr(head),
-             float(self.threshold), ptr(hits), ptr(valid), B, J)
+        call('dsnt_pckh', *map(ptr, args), float(self.threshold), ptr(hits), ptr(valid), B, J)
         self._accumulate(hits, valid)
 
     def add(self, pred, target, joint_mask, head_lengths):
@@ -119,19 +128,26 @@ class PCKhEvaluator:
             m.reset()
 
 
-class PCKhCurve:
-    """PCKh at many thresholds, and the area under that curve, from one integer table on the device.
+def _fp32_ascending(values, most, what):
+    """`values` as the fp64 values of their fp32 roundings: between 1 and `most`, finite and strictly ascending."""
+    out = [float(np.float32(v)) for v in np.asarray(values, dtype=np.float64).reshape(-1)]
+    if not 1 <= len(out) <= most:
+        raise ValueError('between 1 and %d %s, got %d' % (most, what, len(out)))
+    if not all(np.isfinite(out)) or any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError('%s must be finite and strictly ascending as fp32 values' % what)
+    return out
 
-    `table[j][k]` counts the valid joints `j` whose distance lies in `(thresholds[k - 1], thresholds[k]]`; column `T`
-    holds those beyond the last threshold (NaN and inf among them).  Each threshold is held as the fp64 value of its
-    fp32 rounding, as `dsnt_pckh` holds its one threshold, so `pckh(t)` is the very count `PCKhEvaluator(t)` gives.
-    `name` below is a joint name, a group name or a joint index."""
+
+class _JointTables:
+    """What the table evaluators share: the names of joints and groups, and the state.  The state is a tuple of host
+    tensors (`_host`: merged, loaded and reduced) plus, per device that fed a batch, a tuple of tensors of the same
+    shapes that the kernel adds into (`_tables`); their sum is the total.  A subclass sets `_host` when it is constructed
+    and raises in `_mergeable` unless another accumulator counts the same thing."""
 
     JOINT_NAMES = PCKhEvaluator.JOINT_NAMES
     JOINT_GROUPS = PCKhEvaluator.JOINT_GROUPS
-    MAX_THRESHOLDS = 64                   # DSNT_PCKH_HIST_MAX_T
 
-    def __init__(self, thresholds=None, n_joints=16, joint_names=None, joint_groups=None):
+    def __init__(self, n_joints, joint_names, joint_groups):
         self.n_joints = int(n_joints)
         if self.n_joints < 1:
             raise ValueError('n_joints must be positive')
@@ -145,66 +161,8 @@ class PCKhCurve:
         groups = {g: sorted(self.joint_names.index(n) for n in names) for g, names in (joint_groups or {}).items()}
         groups.setdefault('all', list(range(self.n_joints)))
         self.groups = groups
-        self._set_thresholds(np.arange(51) / 100 if thresholds is None else thresholds)
-        self._tables = {}                 # device -> int64 [J, T + 1], the kernel adds into it
-        self._host = torch.zeros(self.n_joints, self.T + 1, dtype=torch.int64)    # merged, loaded and reduced counts
+        self._tables = {}                 # device -> the tensors there, in the order the devices were first used
         self._identity = {}               # (device, B) -> (m, b) of `add`
-
-    def _set_thresholds(self, thresholds):
-        thr = [float(np.float32(t)) for t in np.asarray(thresholds, dtype=np.float64).reshape(-1)]
-        if not 1 <= len(thr) <= self.MAX_THRESHOLDS:
-            raise ValueError('between 1 and %d thresholds, got %d' % (self.MAX_THRESHOLDS, len(thr)))
-        if not all(np.isfinite(thr)) or any(b <= a for a, b in zip(thr, thr[1:])):
-            raise ValueError('thresholds must be finite and strictly ascending as fp32 values')
-        self.thresholds = torch.tensor(thr, dtype=torch.float64)
-        self.T = len(thr)
-        self._thr_arg = (ctypes.c_double * self.T)(*thr)          # host array, passed by value to the kernel
-
-    # ------------------------------------------------------------------ adding batches
-    def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b,
-                       return_distances=False):
-        """Add a batch given in normalised coords (back-projected in fp64 as in `PCKhEvaluator.add_normalized`): one
-        kernel, no reduction and no host synchronisation.  `return_distances`: the f64 [B, J] distances in head lengths,
-        NaN where the mask is not 1."""
-        B, J = norm_pred.shape[0], norm_pred.shape[1]
-        if J != self.n_joints:
-            raise ValueError('%d joints, the table has %d' % (J, self.n_joints))
-        dev = norm_pred.device
-        pred = norm_pred.detach().to(torch.float32).contiguous()
-        target = norm_target.detach().to(device=dev, dtype=torch.float32).contiguous()
-        m = transform_m.to(device=dev, dtype=torch.float64).contiguous()
-        b = transform_b.to(device=dev, dtype=torch.float64).reshape(B, 2).contiguous()
-        mask = joint_mask.to(device=dev, dtype=torch.float32).contiguous()
-        head = head_lengths.to(device=dev, dtype=torch.float64).contiguous()
-        table = self._tables.get(dev)
-        if table is None:
-            table = self._tables[dev] = torch.zeros(J, self.T + 1, dtype=torch.int64, device=dev)
-        dist = torch.empty(B, J, dtype=torch.float64, device=dev) if return_distances else None
-        call('dsnt_pckh_hist', ptr(pred), ptr(target), ptr(m), ptr(b), ptr(mask), ptr(head), self._thr_arg, self.T,
-             ptr(table), ptr(dist), B, J)
-        return dist
-
-    def add(self, pred, target, joint_mask, head_lengths):
-        """Add a batch whose coords are already in image space."""
-        B, dev = pred.shape[0], pred.device
-        ident = self._identity.get((dev, B))
-        if ident is None:
-            ident = self._identity[dev, B] = (torch.eye(2, dtype=torch.float64, device=dev).repeat(B, 1, 1),
-                                              torch.zeros(B, 2, dtype=torch.float64, device=dev))
-        self.add_normalized(pred, target, joint_mask, head_lengths, *ident)
-
-    def reset(self):
-        for t in self._tables.values():
-            t.zero_()
-        self._host.zero_()
-
-    # ------------------------------------------------------------------ reading results
-    def counts(self):
-        """The table, int64 [J, T + 1] on the host."""
-        total = self._host.clone()
-        for t in self._tables.values():
-            total += t.cpu()
-        return total
 
     def _rows(self, name):
         if isinstance(name, (int, np.integer)) and not isinstance(name, bool):
@@ -220,6 +178,72 @@ class PCKhCurve:
     def _names(self):
         return (self.joint_names or list(range(self.n_joints))) + list(self.groups)
 
+    def _on(self, dev):
+        """The tables on `dev`, zero when it is first used."""
+        tables = self._tables.get(dev)
+        if tables is None:
+            tables = self._tables[dev] = tuple(torch.zeros_like(t, device=dev) for t in self._host)
+        return tables
+
+    def _identity_on(self, dev, B):
+        """The identity transform `(m, b)` of a batch whose coords are already in image space."""
+        ident = self._identity.get((dev, B))
+        if ident is None:
+            ident = self._identity[dev, B] = (torch.eye(2, dtype=torch.float64, device=dev).repeat(B, 1, 1),
+                                              torch.zeros(B, 2, dtype=torch.float64, device=dev))
+        return ident
+
+    def reset(self):
+        for tables in list(self._tables.values()) + [self._host]:
+            for t in tables:
+                t.zero_()
+
+    def _total(self):
+        """The state on the host, as fresh tensors: `_host` plus each device's tables."""
+        total = tuple(t.clone() for t in self._host)
+        for tables in self._tables.values():
+            for t, d in zip(total, tables):
+                t += d.cpu()
+        return total
+
+    def _take(self, *state):
+        """Make `state` the whole state: the device tables are zeroed where they are."""
+        for tables in self._tables.values():
+            for t in tables:
+                t.zero_()
+        self._host = tuple(t.to(device='cpu', dtype=h.dtype).clone() for t, h in zip(state, self._host))
+
+    def merge(self, other):
+        """Add `other`'s total to this one's host state."""
+        self._mergeable(other)
+        for t, o in zip(self._host, other._total()):
+            t += o
+
+    def all_reduce(self, group=None):
+        """Sum the state over the ranks of a `torch.distributed` group (evaluation sharded with
+        `EpochLoader(rank=, world_size=)`); nothing to do in a single process."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        state = self._total()
+        if dist.get_backend(group) == 'nccl':
+            state = tuple(t.cuda() for t in state)
+        for t in state:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        self._take(*state)
+
+
+class _ThresholdTables(_JointTables):
+    """One integer table whose last axis is the distance column of `dsnt_pckh_hist`: the thresholds, and the count."""
+
+    MAX_THRESHOLDS = 64                   # DSNT_PCKH_HIST_MAX_T
+
+    def _set_thresholds(self, thresholds):
+        thr = _fp32_ascending(thresholds, self.MAX_THRESHOLDS, 'thresholds')
+        self.thresholds = torch.tensor(thr, dtype=torch.float64)
+        self.T = len(thr)
+        self._thr_arg = (ctypes.c_double * self.T)(*thr)          # host array, passed by value to the kernel
+
     def _index(self, threshold):
         t = float(np.float32(threshold))
         hit = (self.thresholds == t).nonzero()
@@ -227,6 +251,44 @@ class PCKhCurve:
             raise KeyError('PCKh@%r was not accumulated: not one of the %d thresholds' % (threshold, self.T))
         return int(hit)
 
+    def counts(self):
+        """The table, int64 on the host."""
+        return self._total()[0]
+
+
+class PCKhCurve(_ThresholdTables):
+    """PCKh at many thresholds, and the area under that curve, from one integer table `[J, T + 1]` on the device.
+
+    `table[j][k]` counts the valid joints `j` whose distance lies in `(thresholds[k - 1], thresholds[k]]`; column `T`
+    holds those beyond the last threshold (NaN and inf among them).  Each threshold is held as the fp64 value of its
+    fp32 rounding, as `dsnt_pckh` holds its one threshold, so `pckh(t)` is the very count `PCKhEvaluator(t)` gives.
+    `name` below is a joint name, a group name or a joint index."""
+
+    def __init__(self, thresholds=None, n_joints=16, joint_names=None, joint_groups=None):
+        super().__init__(n_joints, joint_names, joint_groups)
+        self._set_thresholds(np.arange(51) / 100 if thresholds is None else thresholds)
+        self._host = (torch.zeros(self.n_joints, self.T + 1, dtype=torch.int64),)
+
+    # ------------------------------------------------------------------ adding batches
+    def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b,
+                       return_distances=False):
+        """Add a batch given in normalised coords (back-projected in fp64 as in `PCKhEvaluator.add_normalized`): one
+        kernel, no reduction and no host synchronisation.  `return_distances`: the f64 [B, J] distances in head lengths,
+        NaN where the mask is not 1."""
+        B, J = norm_pred.shape[0], norm_pred.shape[1]
+        if J != self.n_joints:
+            raise ValueError('%d joints, the table has %d' % (J, self.n_joints))
+        dev = norm_pred.device
+        args = _batch_args(norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b)
+        dist = torch.empty(B, J, dtype=torch.float64, device=dev) if return_distances else None
+        call('dsnt_pckh_hist', *map(ptr, args), self._thr_arg, self.T, ptr(self._on(dev)[0]), ptr(dist), B, J)
+        return dist
+
+    def add(self, pred, target, joint_mask, head_lengths):
+        """Add a batch whose coords are already in image space."""
+        self.add_normalized(pred, target, joint_mask, head_lengths, *self._identity_on(pred.device, pred.shape[0]))
+
+    # ------------------------------------------------------------------ reading results
     def _valid(self, counts, name):
         return int(counts[self._rows(name)].sum())
 
@@ -266,16 +328,9 @@ class PCKhCurve:
         return out
 
     # ------------------------------------------------------------------ combining and saving
-    def _take(self, counts):
-        """Make `counts` (host) the whole state."""
-        for t in self._tables.values():
-            t.zero_()
-        self._host = counts.to(device='cpu', dtype=torch.int64).clone()
-
-    def merge(self, other):
+    def _mergeable(self, other):
         if other.n_joints != self.n_joints or not torch.equal(other.thresholds, self.thresholds):
             raise ValueError('merge needs the same joints and identical thresholds')
-        self._host += other.counts()
 
     def state_dict(self):
         return {'thresholds': self.thresholds.clone(), 'table': self.counts()}
@@ -289,20 +344,8 @@ class PCKhCurve:
         self._tables = {}                 # (their width may have changed)
         self._take(table)
 
-    def all_reduce(self, group=None):
-        """Sum the table over the ranks of a `torch.distributed` group (evaluation sharded with
-        `EpochLoader(rank=, world_size=)`); nothing to do in a single process."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        counts = self.counts()
-        if dist.get_backend(group) == 'nccl':
-            counts = counts.cuda()
-        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
-        self._take(counts)
 
-
-class ErrorField:
+class ErrorField(_JointTables):
     """Where in the frame joints miss PCKh@`threshold`, and in which direction (reference `bin/investigate.py`).
 
     The normalised ground-truth location of every valid joint inside [-1, 1]^2 falls into one cell of a `bins` x `bins`
@@ -314,35 +357,21 @@ class ErrorField:
 
     One owner per cell adds a batch's samples in ascending order, so tables fed by `add_normalized` alone are
     bit-identical however the set was cut into batches.  `merge` and `all_reduce` add fp64 sums on the host, in the
-    order in which they are called: the last bits of `mean_offset` then depend on that order (the counts never do)."""
+    order in which they are called, and `all_reduce` in the backend's order: the last bits of `mean_offset` then depend
+    on that order (the counts never do)."""
 
-    JOINT_NAMES = PCKhEvaluator.JOINT_NAMES
-    JOINT_GROUPS = PCKhEvaluator.JOINT_GROUPS
     MAX_BINS = 32                         # DSNT_ERROR_FIELD_MAX_BINS
 
     def __init__(self, bins=8, threshold=0.5, n_joints=16, joint_names=None, joint_groups=None):
-        self.bins, self.n_joints, self.threshold = int(bins), int(n_joints), float(threshold)
+        self.bins, self.threshold = int(bins), float(threshold)
         if not 1 <= self.bins <= self.MAX_BINS:
             raise ValueError('between 1 and %d bins, got %d' % (self.MAX_BINS, self.bins))
-        if self.n_joints < 1:
-            raise ValueError('n_joints must be positive')
-        if joint_names is None and self.n_joints == len(self.JOINT_NAMES):
-            joint_names = self.JOINT_NAMES
-            if joint_groups is None:
-                joint_groups = self.JOINT_GROUPS
-        self.joint_names = list(joint_names) if joint_names is not None else []
-        if self.joint_names and len(self.joint_names) != self.n_joints:
-            raise ValueError('%d joint names for %d joints' % (len(self.joint_names), self.n_joints))
-        groups = {g: sorted(self.joint_names.index(n) for n in names) for g, names in (joint_groups or {}).items()}
-        groups.setdefault('all', list(range(self.n_joints)))
-        self.groups = groups
+        super().__init__(n_joints, joint_names, joint_groups)
         self.edges = np.linspace(-1, 1, self.bins + 1)
         self.centres = 0.5 * self.edges[1:] + 0.5 * self.edges[:-1]
         self._edges_arg = (ctypes.c_double * (self.bins + 1))(*self.edges)    # host array, passed by value to the kernel
         shape = (self.n_joints, self.bins, self.bins)
-        self._tables = {}                 # device -> (int64 [3, J, bins, bins], f64 [2, J, bins, bins]), the kernel adds
-        self._host = (torch.zeros((3,) + shape, dtype=torch.int64),           # merged, loaded and reduced state
-                      torch.zeros((2,) + shape, dtype=torch.float64))
+        self._host = (torch.zeros((3,) + shape, dtype=torch.int64), torch.zeros((2,) + shape, dtype=torch.float64))
 
     # ------------------------------------------------------------------ adding batches
     def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b):
@@ -351,35 +380,15 @@ class ErrorField:
         B, J = norm_pred.shape[0], norm_pred.shape[1]
         if J != self.n_joints:
             raise ValueError('%d joints, the tables have %d' % (J, self.n_joints))
-        dev = norm_pred.device
-        pred = norm_pred.detach().to(torch.float32).contiguous()
-        target = norm_target.detach().to(device=dev, dtype=torch.float32).contiguous()
-        m = transform_m.to(device=dev, dtype=torch.float64).contiguous()
-        b = transform_b.to(device=dev, dtype=torch.float64).reshape(B, 2).contiguous()
-        mask = joint_mask.to(device=dev, dtype=torch.float32).contiguous()
-        head = head_lengths.to(device=dev, dtype=torch.float64).contiguous()
-        tables = self._tables.get(dev)
-        if tables is None:
-            tables = self._tables[dev] = tuple(torch.zeros_like(t, device=dev) for t in self._host)
-        call('dsnt_error_field', ptr(pred), ptr(target), ptr(m), ptr(b), ptr(mask), ptr(head), self.threshold,
-             self._edges_arg, self.bins, ptr(tables[0]), ptr(tables[1]), B, J)
-
-    def reset(self):
-        for tables in list(self._tables.values()) + [self._host]:
-            for t in tables:
-                t.zero_()
+        args = _batch_args(norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b)
+        counts, sums = self._on(norm_pred.device)
+        call('dsnt_error_field', *map(ptr, args), self.threshold, self._edges_arg, self.bins, ptr(counts), ptr(sums), B, J)
 
     # ------------------------------------------------------------------ reading results
     def tables(self):
         """(counts int64 [3, J, bins, bins]: total, miss, miss with a finite offset; sums f64 [2, J, bins, bins]: of dx
         and of dy) on the host."""
-        counts, sums = self._host[0].clone(), self._host[1].clone()
-        for c, s in self._tables.values():
-            counts += c.cpu()
-            sums += s.cpu()
-        return counts, sums
-
-    _rows = PCKhCurve._rows
+        return self._total()
 
     def _plane(self, table, name):
         """One plane [J, bins, bins] summed over the joints of `name`, in ascending index."""
@@ -419,20 +428,9 @@ class ErrorField:
         return X[at], Y[at], field[..., 0][at], field[..., 1][at], C[at]
 
     # ------------------------------------------------------------------ combining and saving
-    def _take(self, counts, sums):
-        """Make the two host tables the whole state."""
-        for tables in self._tables.values():
-            for t in tables:
-                t.zero_()
-        self._host = (counts.to(device='cpu', dtype=torch.int64).clone(), sums.to(device='cpu', dtype=torch.float64).clone())
-
-    def merge(self, other):
-        """Add `other`'s tables to this one's (fp64 sums added on the host: see the class docstring)."""
+    def _mergeable(self, other):
         if (other.n_joints, other.bins, other.threshold) != (self.n_joints, self.bins, self.threshold):
             raise ValueError('merge needs the same joints, bins and threshold')
-        counts, sums = other.tables()
-        self._host[0].add_(counts)
-        self._host[1].add_(sums)
 
     def state_dict(self):
         counts, sums = self.tables()
@@ -448,29 +446,6 @@ class ErrorField:
             raise ValueError('tables of shape %s and %s for %d joints and %d bins'
                              % (tuple(counts.shape), tuple(sums.shape), self.n_joints, self.bins))
         self._take(counts, sums)
-
-    def all_reduce(self, group=None):
-        """Sum the tables over the ranks of a `torch.distributed` group; nothing to do in a single process.  The fp64
-        sums are reduced in the backend's order (see the class docstring)."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        counts, sums = self.tables()
-        if dist.get_backend(group) == 'nccl':
-            counts, sums = counts.cuda(), sums.cuda()
-        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
-        self._take(counts, sums)
-
-
-def _fp32_ascending(values, most, what):
-    """`values` as the fp64 values of their fp32 roundings: between 1 and `most`, finite and strictly ascending."""
-    out = [float(np.float32(v)) for v in np.asarray(values, dtype=np.float64).reshape(-1)]
-    if not 1 <= len(out) <= most:
-        raise ValueError('between 1 and %d %s, got %d' % (most, what, len(out)))
-    if not all(np.isfinite(out)) or any(b <= a for a, b in zip(out, out[1:])):
-        raise ValueError('%s must be finite and strictly ascending as fp32 values' % what)
-    return out
 
 
 def _ratio(num, den):
@@ -501,48 +476,26 @@ def _pav(hits, n, increasing):
     return out
 
 
-class Reliability:
+class Reliability(_ThresholdTables):
     """Does a per-joint score (a confidence such as `stats['peak']`, or a spread) know when the joint is right?
 
-    `table[j][r][k]` counts the valid joints `j` whose score lies in row `r` and whose distance lies in `PCKhCurve`'s
-    column `k`.  With the `S` score edges `e`, row `r` is the number of edges `<=` the score: row 0 is `score < e[0]`, row
-    `S` is `score >= e[S - 1]`, a score on an edge belongs to the row above it, and row `S + 1` holds the NaN scores
-    ("unscored").  Edges and thresholds are held as the fp64 values of their fp32 roundings, so an fp32 score compares
-    exactly.  Summed over the score rows the table is `PCKhCurve`'s.  Everything read from it is computed on the host
-    from the integers.  `name` below is a joint name, a group name or a joint index."""
+    `table[j][r][k]`, int64 `[J, S + 2, T + 1]`, counts the valid joints `j` whose score lies in row `r` and whose
+    distance lies in `PCKhCurve`'s column `k`.  With the `S` score edges `e`, row `r` is the number of edges `<=` the
+    score: row 0 is `score < e[0]`, row `S` is `score >= e[S - 1]`, a score on an edge belongs to the row above it, and
+    row `S + 1` holds the NaN scores ("unscored").  Edges and thresholds are held as the fp64 values of their fp32
+    roundings, so an fp32 score compares exactly.  Summed over the score rows the table is `PCKhCurve`'s.  Everything
+    read from it is computed on the host from the integers.  `name` below is a joint name, a group name or a joint
+    index."""
 
-    JOINT_NAMES = PCKhEvaluator.JOINT_NAMES
-    JOINT_GROUPS = PCKhEvaluator.JOINT_GROUPS
-    MAX_THRESHOLDS = 64                   # DSNT_PCKH_HIST_MAX_T
     MAX_EDGES = 64                        # DSNT_SCORE_HIST_MAX_S
 
     def __init__(self, score_edges, thresholds=(0.5,), n_joints=16, higher_is_better=True, joint_names=None,
                  joint_groups=None):
-        self.n_joints = int(n_joints)
         self.higher_is_better = bool(higher_is_better)
-        if self.n_joints < 1:
-            raise ValueError('n_joints must be positive')
-        if joint_names is None and self.n_joints == len(self.JOINT_NAMES):
-            joint_names = self.JOINT_NAMES
-            if joint_groups is None:
-                joint_groups = self.JOINT_GROUPS
-        self.joint_names = list(joint_names) if joint_names is not None else []
-        if self.joint_names and len(self.joint_names) != self.n_joints:
-            raise ValueError('%d joint names for %d joints' % (len(self.joint_names), self.n_joints))
-        groups = {g: sorted(self.joint_names.index(n) for n in names) for g, names in (joint_groups or {}).items()}
-        groups.setdefault('all', list(range(self.n_joints)))
-        self.groups = groups
+        super().__init__(n_joints, joint_names, joint_groups)
         self._set_thresholds(thresholds)
         self._set_edges(score_edges)
-        self._tables = {}                 # device -> int64 [J, S + 2, T + 1], the kernel adds into it
-        self._host = torch.zeros(self.n_joints, self.S + 2, self.T + 1, dtype=torch.int64)    # merged, loaded, reduced
-        self._identity = {}               # (device, B) -> (m, b) of `add`
-
-    def _set_thresholds(self, thresholds):
-        thr = _fp32_ascending(thresholds, self.MAX_THRESHOLDS, 'thresholds')
-        self.thresholds = torch.tensor(thr, dtype=torch.float64)
-        self.T = len(thr)
-        self._thr_arg = (ctypes.c_double * self.T)(*thr)          # host array, passed by value to the kernel
+        self._host = (torch.zeros(self.n_joints, self.S + 2, self.T + 1, dtype=torch.int64),)
 
     def _set_edges(self, score_edges):
         edges = _fp32_ascending(score_edges, self.MAX_EDGES, 'score edges')
@@ -561,46 +514,16 @@ class Reliability:
         if tuple(score.shape) != (B, J):
             raise ValueError('scores of shape %s for %d x %d joints' % (tuple(score.shape), B, J))
         dev = norm_pred.device
-        pred = norm_pred.detach().to(torch.float32).contiguous()
-        target = norm_target.detach().to(device=dev, dtype=torch.float32).contiguous()
-        m = transform_m.to(device=dev, dtype=torch.float64).contiguous()
-        b = transform_b.to(device=dev, dtype=torch.float64).reshape(B, 2).contiguous()
-        mask = joint_mask.to(device=dev, dtype=torch.float32).contiguous()
-        head = head_lengths.to(device=dev, dtype=torch.float64).contiguous()
+        args = _batch_args(norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b)
         score = score.detach().to(device=dev, dtype=torch.float32).contiguous()
-        table = self._tables.get(dev)
-        if table is None:
-            table = self._tables[dev] = torch.zeros_like(self._host, device=dev)
-        call('dsnt_score_hist', ptr(pred), ptr(target), ptr(m), ptr(b), ptr(mask), ptr(head), ptr(score),
-             self._edges_arg, self.S, self._thr_arg, self.T, ptr(table), B, J)
+        call('dsnt_score_hist', *map(ptr, args), ptr(score), self._edges_arg, self.S, self._thr_arg, self.T,
+             ptr(self._on(dev)[0]), B, J)
 
     def add(self, pred, target, joint_mask, head_lengths, score):
         """Add a batch whose coords are already in image space."""
-        B, dev = pred.shape[0], pred.device
-        ident = self._identity.get((dev, B))
-        if ident is None:
-            ident = self._identity[dev, B] = (torch.eye(2, dtype=torch.float64, device=dev).repeat(B, 1, 1),
-                                              torch.zeros(B, 2, dtype=torch.float64, device=dev))
-        self.add_normalized(pred, target, joint_mask, head_lengths, *ident, score)
-
-    def reset(self):
-        for t in self._tables.values():
-            t.zero_()
-        self._host.zero_()
+        self.add_normalized(pred, target, joint_mask, head_lengths, *self._identity_on(pred.device, pred.shape[0]), score)
 
     # ------------------------------------------------------------------ reading results
-    def counts(self):
-        """The table, int64 [J, S + 2, T + 1] on the host."""
-        total = self._host.clone()
-        for t in self._tables.values():
-            total += t.cpu()
-        return total
-
-    # the `name` and `threshold` lookups are `PCKhCurve`'s (as `ErrorField` takes `_rows`): they read `groups`,
-    # `joint_names`, `n_joints`, `thresholds` and `T` only
-    _rows = PCKhCurve._rows
-    _index = PCKhCurve._index
-
     def _hits(self, counts, threshold, name):
         """(hits, support) per score row, int64 numpy [S + 2], of the joints of `name` at one constructed threshold."""
         k = self._index(threshold)
@@ -670,17 +593,10 @@ class Reliability:
         return ScoreCalibration(self.score_edges, values, score)
 
     # ------------------------------------------------------------------ combining and saving
-    def _take(self, counts):
-        """Make `counts` (host) the whole state."""
-        for t in self._tables.values():
-            t.zero_()
-        self._host = counts.to(device='cpu', dtype=torch.int64).clone()
-
-    def merge(self, other):
+    def _mergeable(self, other):
         if (other.n_joints != self.n_joints or not torch.equal(other.thresholds, self.thresholds)
                 or not torch.equal(other.score_edges, self.score_edges)):
             raise ValueError('merge needs the same joints and identical score edges and thresholds')
-        self._host += other.counts()
 
     def state_dict(self):
         return {'score_edges': self.score_edges.clone(), 'thresholds': self.thresholds.clone(),
@@ -696,17 +612,6 @@ class Reliability:
         self.higher_is_better = bool(state['higher_is_better'])
         self._tables = {}                 # (their shape may have changed)
         self._take(table)
-
-    def all_reduce(self, group=None):
-        """Sum the table over the ranks of a `torch.distributed` group; nothing to do in a single process."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        counts = self.counts()
-        if dist.get_backend(group) == 'nccl':
-            counts = counts.cuda()
-        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
-        self._take(counts)
 
 
 class ScoreCalibration:

@@ -98,6 +98,21 @@ def case(B, J, seed):
     return pred, target, m, b, mask, head, score
 
 
+def awkward(pred, target, m, b, mask, head, device='cpu'):
+    """The first six arrays of `case` as tensors on `device` in the argument order of `add_normalized`, in forms the kernels
+    cannot take: `pred` a strided fp64 view, `target` and `mask` fp64, `head` f32, `transform_m` a transposed view and
+    `transform_b` f32 `[B, 1, 2]` (tests/test_evaluator_shared_cpu.py, tests/test_evaluator_shared_gpu.py)."""
+    import torch
+    wide = torch.zeros(pred.shape[:2] + (4,), dtype=torch.float64, device=device)
+    wide[..., ::2] = torch.from_numpy(pred).to(device)
+    m_t = torch.from_numpy(m).to(device).transpose(1, 2).contiguous().transpose(1, 2)
+    out = (wide[..., ::2], torch.from_numpy(target).double().to(device), torch.from_numpy(mask).double().to(device),
+           torch.from_numpy(head).float().to(device), m_t,
+           torch.from_numpy(b).float().reshape(pred.shape[0], 1, 2).to(device))
+    assert not out[0].is_contiguous() and not out[4].is_contiguous()
+    return out
+
+
 def clear_of_thresholds(d, thr):
     """No distance within 1e-9 relative of a threshold, so that an fp64 contraction difference moves no joint across a
     bin edge.  (Score rows need no margin: fp32 scores against fp32-valued edges compare exactly.)"""
