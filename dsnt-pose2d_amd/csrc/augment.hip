@@ -60,31 +60,12 @@
 // its valid byte 0.  Stores: a thread packs 4 pixels (12 bytes) into three dword stores, so a wave writes 768
 // contiguous bytes; odd R (a crop not dword-aligned) and a crop's last partial group store bytes.
 #include "common.h"
+#include "philox.h"
 #include <math.h>
 
 namespace {
 
 constexpr int AUG_NT = 256;
-
-struct Philox {
-    __device__ static void round(uint32_t ctr[4], const uint32_t key[2]) {
-        const uint32_t lo0 = 0xD2511F53u * ctr[0], hi0 = __umulhi(0xD2511F53u, ctr[0]);
-        const uint32_t lo1 = 0xCD9E8D57u * ctr[2], hi1 = __umulhi(0xCD9E8D57u, ctr[2]);
-        const uint32_t c0 = hi1 ^ ctr[1] ^ key[0], c2 = hi0 ^ ctr[3] ^ key[1];
-        ctr[0] = c0; ctr[1] = lo1; ctr[2] = c2; ctr[3] = lo0;
-    }
-    // Philox4x32-10
-    __device__ static void gen(uint32_t out[4], uint64_t seed, uint64_t step, uint32_t sample, uint32_t k) {
-        uint32_t ctr[4] = {sample, (uint32_t)step, (uint32_t)(step >> 32), k};
-        uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-        for (int r = 0; r < 10; ++r) {
-            round(ctr, key);
-            key[0] += 0x9E3779B9u;
-            key[1] += 0xBB67AE85u;
-        }
-        for (int i = 0; i < 4; ++i) out[i] = ctr[i];
-    }
-};
 
 // (0, 1]: 24 random bits
 __device__ inline double unit(uint32_t x) { return (double)((x >> 8) + 1u) * (1.0 / 16777216.0); }

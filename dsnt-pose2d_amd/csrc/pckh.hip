@@ -1,6 +1,7 @@
 // The PCKh evaluators (evaluator.py:66, train.py:243-258): the hit test at one threshold, the one-launch histogram
 // behind the PCKh curve and the misprediction field of bin/investigate.py, all on one fp64 distance expression.
 #include "common.h"
+#include "philox.h"
 
 // ---------------------------------------------------------------- PCKh hits
 // Distance of joint i (of image n) between the back-projected prediction and target, in head lengths: one expression for
@@ -181,6 +182,130 @@ extern "C" int dsnt_score_hist(const float* pred, const float* target, const dou
     if (const int rc = ascending_arg("dsnt_score_hist", "score edge", score_edges_host, S, by.edges.e)) return rc;
     return joint_table_launch<DSNT_SCORE_HIST_LDS_CELLS>("dsnt_score_hist", "J * (S + 2) * (T + 1)", pred, target, m, b,
                                                          mask, head, by, thresholds, T, table, nullptr, B, J, stream);
+}
+
+// Poisson bootstrap over examples (include/dsnt_hip.h: dsnt_pckh_boot): R + 1 copies of the curve's table, copy 0 with
+// weight 1 and copy r with the weight w(id, r) of the example, a function of the example's id, the replicate and the seed
+// alone.  Integer adds only, so the table does not depend on the order of arrival, nor on how the examples are batched.
+static_assert(DSNT_PCKH_BOOT_LDS_CELLS * sizeof(unsigned) <= 64 * 1024, "the LDS table is a static allocation");
+static_assert(DSNT_PCKH_BOOT_CHUNK >= 1 && DSNT_PCKH_BOOT_SPAN >= 1, "a workgroup owns at least one copy and one joint");
+static_assert(DSNT_PCKH_HIST_MAX_T < 255, "a column fits a byte, 255 marks a joint that does not count");
+static_assert(12ull * DSNT_PCKH_BOOT_MAX_B <= 0xffffffffull && 12ull * (DSNT_PCKH_BOOT_MAX_B + 1ull) > 0xffffffffull,
+              "a u32 cell holds 12 from every example");
+// Weight of a 32-bit uniform: the number of c_k it reaches, Poisson(1) by inverse CDF.
+__device__ __forceinline__ unsigned boot_weight(uint32_t u) {
+    constexpr uint32_t cdf[12] = DSNT_PCKH_BOOT_CDF;
+    unsigned w = 0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) w += u >= cdf[k] ? 1u : 0u;
+    return w;
+}
+// Workgroup (x, y): the chunks x, x + gridDim.x, ... of `chunk` copies each, and for each of them the spans y,
+// y + gridDim.y, ... of DSNT_PCKH_BOOT_SPAN joints of the flat [B * J].  Per span: the column of every joint once, a byte
+// in LDS (255: mask != 1); then copy 0, one thread per joint; then the replicates, one thread per (example, Philox call):
+// the call's four words are the weights of the replicates 4q + 1 .. 4q + 4, of which those inside the chunk add the weight
+// to the cell of each of the example's joints inside the span.  A chunk begins at copy chunk * x, so its first and last
+// Philox call may be shared with a neighbour: both compute it, each uses its own words.
+__global__ __launch_bounds__(DSNT_PCKH_BOOT_BLOCK)
+void pckh_boot_kernel(const float* __restrict__ pred, const float* __restrict__ target, const double* __restrict__ m,
+                      const double* __restrict__ b, const float* __restrict__ mask, const double* __restrict__ head,
+                      const int64_t* __restrict__ ids, const pckh_thresholds thr, int T, uint64_t seed, int R,
+                      unsigned long long* table, int B, int J, int use_lds, int chunk) {
+    __shared__ unsigned cnt[DSNT_PCKH_BOOT_LDS_CELLS];
+    __shared__ unsigned char col[DSNT_PCKH_BOOT_SPAN];
+    constexpr int SPAN = DSNT_PCKH_BOOT_SPAN;
+    const int tid = threadIdx.x, per_copy = J * (T + 1);
+    const long total = (long)B * J;
+    const long spans = (total + SPAN - 1) / SPAN;
+    for (long s0 = (long)blockIdx.x * chunk; s0 <= R; s0 += (long)gridDim.x * chunk) {
+        const int s1 = (int)(s0 + chunk <= R ? s0 + chunk : (long)R + 1);         // copies [s0, s1)
+        const int cells = use_lds ? (s1 - (int)s0) * per_copy : 0;                // of the LDS table
+        // the Philox calls whose replicates 4q + 1 .. 4q + 4 meet [max(s0, 1), s1): none if the chunk is copy 0 alone
+        const int q0 = ((int)(s0 > 1 ? s0 : 1) - 1) >> 2;
+        const int nq = s1 > 1 ? ((s1 - 2) >> 2) - q0 + 1 : 0;
+        unsigned long long* out = table + (size_t)s0 * per_copy;
+        if (use_lds) {
+            for (int c = tid; c < cells; c += blockDim.x) cnt[c] = 0u;
+        }
+        for (long span = blockIdx.y; span < spans; span += gridDim.y) {
+            const long i0 = span * SPAN;
+            const int len = (int)(total - i0 < SPAN ? total - i0 : SPAN);
+            __syncthreads();                                   // the zeroes above, and the last span's readers of col
+            for (int t = tid; t < len; t += blockDim.x) {
+                const long i = i0 + t;
+                const double d = pckh_distance(pred, target, m, b, head, i, i / J);
+                col[t] = mask[i] == 1.f ? (unsigned char)pckh_column(thr, d, T) : (unsigned char)255;
+            }
+            __syncthreads();
+            if (s0 == 0) {
+                for (int t = tid; t < len; t += blockDim.x) {
+                    const int k = col[t];
+                    if (k == 255) continue;
+                    const int c = (int)((i0 + t) % J) * (T + 1) + k;
+                    if (use_lds) atomicAdd(cnt + c, 1u);
+                    else atomicAdd(out + c, 1ull);
+                }
+            }
+            const long n0 = i0 / J;
+            const int units = (int)((i0 + len - 1) / J - n0 + 1) * nq;         // at most SPAN examples x (CHUNK + 2) / 4 + 1
+            for (int u = tid; u < units; u += blockDim.x) {
+                const long n = n0 + u / nq;
+                const int q = q0 + u % nq;
+                const uint64_t id = (uint64_t)ids[n];
+                uint32_t word[4];
+                Philox::gen(word, seed, ((uint64_t)(uint32_t)q << 32) | (id >> 32), (uint32_t)id, DSNT_PCKH_BOOT_DOMAIN);
+                // the joints of example n inside the span, as offsets into col
+                const long lo = n * J > i0 ? n * J : i0, hi = (n + 1) * J < i0 + len ? (n + 1) * J : i0 + len;
+                const int j0 = (int)(lo - n * J), t0 = (int)(lo - i0), nj = (int)(hi - lo);
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const int s = 4 * q + w + 1;
+                    const unsigned weight = boot_weight(word[w]);
+                    if (s < s0 || s >= s1 || weight == 0u) continue;
+                    const int base = (s - (int)s0) * per_copy + j0 * (T + 1);
+                    for (int step = 0, t = u % nj; step < nj; ++step, t = t + 1 < nj ? t + 1 : 0) {   // (lanes start apart: banks)
+                        const int k = col[t0 + t];
+                        if (k == 255) continue;
+                        const int c = base + t * (T + 1) + k;
+                        if (use_lds) atomicAdd(cnt + c, weight);
+                        else atomicAdd(out + c, (unsigned long long)weight);
+                    }
+                }
+            }
+        }
+        if (use_lds) {
+            __syncthreads();
+            for (int c = tid; c < cells; c += blockDim.x) {
+                const unsigned v = cnt[c];
+                if (v) atomicAdd(out + c, (unsigned long long)v);
+            }
+            __syncthreads();                                   // before the next chunk zeroes the cells
+        }
+    }
+}
+extern "C" int dsnt_pckh_boot(const float* pred, const float* target, const double* m, const double* b,
+                              const float* mask, const double* head, const int64_t* ids, const double* thresholds, int T,
+                              uint64_t seed, int R, unsigned long long* table, int B, int J, void* stream) {
+    DSNT_REQUIRE(pred && target && m && b && mask && head && ids && thresholds && table && B > 0 && J > 0 && R > 0,
+                 DSNT_ERR_ARG, "dsnt_pckh_boot: bad argument");
+    DSNT_REQUIRE(T >= 1 && T <= DSNT_PCKH_HIST_MAX_T, DSNT_ERR_ARG, "dsnt_pckh_boot: T=%d outside 1..%d", T,
+                 DSNT_PCKH_HIST_MAX_T);
+    DSNT_REQUIRE(B <= DSNT_PCKH_BOOT_MAX_B, DSNT_ERR_ARG, "dsnt_pckh_boot: B=%d above %d", B, DSNT_PCKH_BOOT_MAX_B);
+    const long per_copy = (long)J * (T + 1);
+    DSNT_REQUIRE(per_copy <= 0x7fffffffL && ((long)R + 1) * per_copy <= 0x7fffffffL, DSNT_ERR_ARG,
+                 "dsnt_pckh_boot: (R + 1) * J * (T + 1) does not fit an int");
+    pckh_thresholds thr;
+    if (const int rc = ascending_arg("dsnt_pckh_boot", "threshold", thresholds, T, thr.t)) return rc;
+    const int use_lds = per_copy <= DSNT_PCKH_BOOT_LDS_CELLS ? 1 : 0;
+    const long fit = use_lds ? DSNT_PCKH_BOOT_LDS_CELLS / per_copy : DSNT_PCKH_BOOT_CHUNK;
+    const int chunk = (int)(fit < DSNT_PCKH_BOOT_CHUNK ? fit : DSNT_PCKH_BOOT_CHUNK);
+    const long chunks = ((long)R + chunk) / chunk;             // ceil((R + 1) / chunk)
+    const long spans = ((long)B * J + DSNT_PCKH_BOOT_SPAN - 1) / DSNT_PCKH_BOOT_SPAN;
+    const dim3 grid((unsigned)(chunks < DSNT_PCKH_BOOT_MAX_CHUNK_BLOCKS ? chunks : DSNT_PCKH_BOOT_MAX_CHUNK_BLOCKS),
+                    (unsigned)(spans < DSNT_PCKH_BOOT_MAX_SPAN_BLOCKS ? spans : DSNT_PCKH_BOOT_MAX_SPAN_BLOCKS));
+    DSNT_LAUNCH(pckh_boot_kernel, grid, dim3(DSNT_PCKH_BOOT_BLOCK), 0, (hipStream_t)stream, pred, target, m, b, mask,
+                head, ids, thr, T, seed, R, table, B, J, use_lds, chunk);
+    DSNT_CHECK_LAUNCH("dsnt_pckh_boot");
 }
 
 // out[i] = values[joint of i][row of score[i]] (include/dsnt_hip.h: dsnt_score_lookup): the calibration table applied to a

@@ -17,7 +17,11 @@ is a cumulative sum of that table taken when the user asks.
 score row against distance column (`dsnt_score_hist`), from which accuracy per score, risk against
 coverage, an operating point and a monotone `ScoreCalibration` (applied on the device by `dsnt_score_lookup`) are read.
 
-The three table evaluators keep their joint names and their state in `_JointTables`; all four prepare a batch with
+`PCKhBootstrap` asks how far a PCKh can be trusted and whether one model really beats another: one launch per batch adds
+into `R + 1` copies of the curve's table, copy `r` weighting every example by a Poisson(1) draw keyed on the example's id
+(`dsnt_pckh_boot`), from which standard errors, percentile intervals and a paired comparison are read.
+
+The four table evaluators keep their joint names and their state in `_JointTables`; all five prepare a batch with
 `_batch_args`.
 """
 import ctypes
@@ -345,6 +349,115 @@ class PCKhCurve(_ThresholdTables):
         self._take(table)
 
 
+class PCKhBootstrap(_ThresholdTables):
+    """How far a PCKh can be trusted, and whether one model beats another: a Poisson bootstrap over examples.
+
+    `table[r][j][k]`, int64 `[R + 1, J, T + 1]`: slice 0 is `PCKhCurve`'s table, and slice `r` in 1..R counts every example
+    `w(id, r)` times, `w` ~ Poisson(1) drawn by Philox from the example's id, `r` and `seed` alone (`dsnt_pckh_boot`).  The
+    example (a person) is what is resampled: all its joints share the weight.  Because the weight hangs on the id, the
+    table does not depend on batching, order or sharding, and two accumulators with one seed that were fed the same ids
+    resampled the same people, which is what `compare` needs.  `index` is the int64 `[B]` id of each example of a batch
+    (`EpochLoader`'s `sample['index']`).  `name` below is a joint name, a group name or a joint index."""
+
+    def __init__(self, replicates=1000, thresholds=(0.5,), seed=0, n_joints=16, joint_names=None, joint_groups=None):
+        self.R = int(replicates)
+        if self.R < 1:
+            raise ValueError('replicates must be positive')
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        super().__init__(n_joints, joint_names, joint_groups)
+        self._set_thresholds(thresholds)
+        self._host = (torch.zeros(self.R + 1, self.n_joints, self.T + 1, dtype=torch.int64),)
+
+    # ------------------------------------------------------------------ adding batches
+    def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b, index):
+        """Add a batch given in normalised coords (back-projected in fp64 as in `PCKhEvaluator.add_normalized`) with the
+        ids of its examples: one kernel, no reduction and no host synchronisation."""
+        B, J = norm_pred.shape[0], norm_pred.shape[1]
+        if J != self.n_joints:
+            raise ValueError('%d joints, the table has %d' % (J, self.n_joints))
+        index = torch.as_tensor(index)
+        if index.is_floating_point() or index.is_complex() or index.dtype == torch.bool:
+            raise ValueError('index must hold integers, got %s' % index.dtype)
+        if tuple(index.shape) != (B,):
+            raise ValueError('index of shape %s for %d examples' % (tuple(index.shape), B))
+        dev = norm_pred.device
+        args = _batch_args(norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b)
+        index = index.detach().to(device=dev, dtype=torch.int64).contiguous()
+        call('dsnt_pckh_boot', *map(ptr, args), ptr(index), self._thr_arg, self.T, ctypes.c_uint64(self.seed), self.R,
+             ptr(self._on(dev)[0]), B, J)
+
+    def add(self, pred, target, joint_mask, head_lengths, index):
+        """Add a batch whose coords are already in image space."""
+        self.add_normalized(pred, target, joint_mask, head_lengths, *self._identity_on(pred.device, pred.shape[0]), index)
+
+    # ------------------------------------------------------------------ reading results
+    def _hits(self, counts, threshold, name):
+        """(hits, valid) per slice, int64 numpy [R + 1], of the joints of `name` at one constructed threshold."""
+        k = self._index(threshold)
+        table = counts[:, self._rows(name)].sum(1).numpy()
+        return table[:, :k + 1].sum(1), table.sum(1)
+
+    def _replicates(self, counts, threshold, name):
+        hits, n = self._hits(counts, threshold, name)
+        return _ratio(hits[1:], n[1:])
+
+    def pckh(self, threshold=0.5, name='total_mpii'):
+        """The point estimate, from slice 0: `PCKhCurve.pckh` of the same feed."""
+        hits, n = self._hits(self.counts(), threshold, name)
+        return float(_ratio(hits[0], n[0]))
+
+    def replicates(self, threshold=0.5, name='total_mpii'):
+        """PCKh of every replicate, f64 [R]: weighted hits / weighted valid, NaN where nothing valid was drawn."""
+        return self._replicates(self.counts(), threshold, name)
+
+    def stderr(self, threshold=0.5, name='total_mpii'):
+        """Sample standard deviation (ddof 1) of the finite replicates."""
+        return _spread(self._replicates(self.counts(), threshold, name))
+
+    def interval(self, threshold=0.5, name='total_mpii', level=0.95):
+        """Percentile interval `(lo, hi)` of the finite replicates at `level`."""
+        return _percentiles(self._replicates(self.counts(), threshold, name), level)
+
+    def compare(self, other, threshold=0.5, name='total_mpii', level=0.95):
+        """Paired comparison with `other`, an accumulator of the same seed fed the same examples (another model's
+        predictions for them): a dict of `diff` (point estimate, self - other), `interval` and `stderr` of the
+        per-replicate differences, and `p_greater`, the share of replicates in which self is ahead plus half the ties."""
+        if (other.seed, other.R) != (self.seed, self.R):
+            raise ValueError('compare needs the same seed and replicates')
+        self._mergeable(other)
+        mine, theirs = self.counts(), other.counts()
+        # the weighted valid count of every replicate and joint agrees exactly when both saw the same examples
+        if not torch.equal(mine.sum(2), theirs.sum(2)):
+            raise ValueError('compare needs both accumulators fed the same examples')
+        d = self._replicates(mine, threshold, name) - other._replicates(theirs, threshold, name)
+        d = d[np.isfinite(d)]
+        a, b = self._hits(mine, threshold, name), other._hits(theirs, threshold, name)
+        return {'diff': float(_ratio(a[0][0], a[1][0]) - _ratio(b[0][0], b[1][0])), 'interval': _percentiles(d, level),
+                'stderr': _spread(d),
+                'p_greater': float(((d > 0).sum() + 0.5 * (d == 0).sum()) / d.size) if d.size else float('nan')}
+
+    # ------------------------------------------------------------------ combining and saving
+    def _mergeable(self, other):
+        if ((other.seed, other.R, other.n_joints) != (self.seed, self.R, self.n_joints)
+                or not torch.equal(other.thresholds, self.thresholds)):
+            raise ValueError('merge needs the same seed, replicates, joints and identical thresholds')
+
+    def state_dict(self):
+        return {'thresholds': self.thresholds.clone(), 'seed': self.seed, 'replicates': self.R, 'table': self.counts()}
+
+    def load_state_dict(self, state):
+        table, thresholds = state['table'], state['thresholds']
+        if int(state['seed']) != self.seed or int(state['replicates']) != self.R:
+            raise ValueError('state of seed %d and %d replicates, this bootstrap has seed %d and %d'
+                             % (state['seed'], state['replicates'], self.seed, self.R))
+        if table.dim() != 3 or tuple(table.shape) != (self.R + 1, self.n_joints, thresholds.numel() + 1):
+            raise ValueError('table of shape %s for %d replicates, %d joints and %d thresholds'
+                             % (tuple(table.shape), self.R, self.n_joints, thresholds.numel()))
+        self._set_thresholds(thresholds.cpu().numpy())
+        self._tables = {}                 # (their width may have changed)
+        self._take(table)
+
+
 class ErrorField(_JointTables):
     """Where in the frame joints miss PCKh@`threshold`, and in which direction (reference `bin/investigate.py`).
 
@@ -452,6 +565,25 @@ def _ratio(num, den):
     """num / den in fp64, NaN where den is 0."""
     with np.errstate(divide='ignore', invalid='ignore'):
         return np.where(den > 0, np.asarray(num, np.float64) / np.asarray(den, np.float64), np.nan)
+
+
+def _spread(values):
+    """Sample standard deviation (ddof 1) of the finite `values`; NaN with fewer than two."""
+    v = np.asarray(values, np.float64)
+    v = v[np.isfinite(v)]
+    return float(np.std(v, ddof=1)) if v.size > 1 else float('nan')
+
+
+def _percentiles(values, level):
+    """`(lo, hi)`: the `(1 - level) / 2` and `1 - (1 - level) / 2` quantiles (linear) of the finite `values`."""
+    if not 0 < level < 1:
+        raise ValueError('level must lie in (0, 1)')
+    v = np.asarray(values, np.float64)
+    v = v[np.isfinite(v)]
+    if not v.size:
+        return float('nan'), float('nan')
+    lo, hi = np.quantile(v, [(1 - level) / 2, 1 - (1 - level) / 2], method='linear')
+    return float(lo), float(hi)
 
 
 def _pav(hits, n, increasing):

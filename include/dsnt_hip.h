@@ -828,6 +828,42 @@ int dsnt_score_hist(const float* pred, const float* target, const double* m, con
 #define DSNT_SCORE_LOOKUP_MAX_BLOCKS 1024
 int dsnt_score_lookup(const float* score, const double* score_edges, int S, const float* values,
                       int per_joint, float* out, int64_t n, int J, void* stream);
+/* How far can a PCKh be trusted?  One launch ADDS a batch to R + 1 copies of dsnt_pckh_hist's table: copy 0 counts every
+ * example once, copy r in 1..R counts example n w(ids[n], r) times, a Poisson(1) bootstrap over examples (people: all the
+ * joints of an example share its weight).  pred, target, m, b, mask, head, thresholds and T are dsnt_pckh_hist's, with the
+ * same checks; d is dsnt_pckh's distance (same fp64 expression) and the column k is dsnt_pckh_hist's.  A joint with
+ * mask == 1 adds w(ids[n], r) to table[r][j][k] for every r in 0..R; other masks add nothing.  table[0] is
+ * dsnt_pckh_hist's table bit for bit.
+ * The weight.  w(id, 0) = 1.  For r in 1..R: u = word (r - 1) & 3 of Philox4x32-10 with key (seed lo, seed hi) and counter
+ * (id lo, id hi, (r - 1) >> 2, DSNT_PCKH_BOOT_DOMAIN), id being the int64 taken as its 64 bits (one Philox call serves four
+ * replicates; the domain word keeps the stream apart from the augmentation draw's 0, 1, 2 and the epoch order's
+ * 0x4F524400 + i), and w = the number of k in 0..11 with u >= c_k, c_k = floor(2^32 e^-1 sum_{i<=k} 1/i!) as listed in
+ * DSNT_PCKH_BOOT_CDF: the inverse CDF of Poisson(1) on 32 bits, w in 0..12, mean 1 + 2e-9.  The weight depends on the
+ * example's id, the replicate and the seed alone: not on the batch, its order or the rank that holds it, and two models
+ * fed the same ids resample the same people.
+ * ids: device i64 [B], any values.  table: device u64 [R + 1][J][T + 1]; the kernel only adds (64-bit integer atomics:
+ * order-independent, bit-reproducible), the caller zeroes.  R >= 1 and (R + 1) * J * (T + 1) fits an int.
+ * B <= DSNT_PCKH_BOOT_MAX_B = floor((2^32 - 1) / 12): a workgroup counts in 32 bits on chip, and one cell takes at most
+ * 12 from each of the at most B examples the workgroup sees.  DSNT_ERR_ARG otherwise, nothing launched.
+ * A workgroup of DSNT_PCKH_BOOT_BLOCK threads owns a chunk of min(DSNT_PCKH_BOOT_CHUNK, DSNT_PCKH_BOOT_LDS_CELLS /
+ * (J * (T + 1))) consecutive copies; grid.x = min(chunks, DSNT_PCKH_BOOT_MAX_CHUNK_BLOCKS) strides over the chunks.  It
+ * walks B * J in spans of DSNT_PCKH_BOOT_SPAN joints (grid.y = min(spans, DSNT_PCKH_BOOT_MAX_SPAN_BLOCKS) strides over
+ * them): the column of every joint of the span once, into LDS, then one thread per (example, four replicates).  While
+ * J * (T + 1) <= DSNT_PCKH_BOOT_LDS_CELLS the chunk is summed in a u32 LDS table and its non-zero cells are flushed with
+ * one 64-bit atomic each; above that every weight is added to `table` directly.  dsnt_version() >= 127. */
+#define DSNT_PCKH_BOOT_DOMAIN 0x424F4F54u
+#define DSNT_PCKH_BOOT_CDF { 1580030168u, 3160060337u, 3950075421u, 4213413783u, 4279248373u, 4292415291u, 4294609777u, 4294923276u, 4294962463u, 4294966817u, 4294967252u, 4294967292u }
+#define DSNT_PCKH_BOOT_MAX_B 357913941
+#define DSNT_PCKH_BOOT_LDS_CELLS 4096
+#define DSNT_PCKH_BOOT_BLOCK 256
+#define DSNT_PCKH_BOOT_CHUNK 32
+#define DSNT_PCKH_BOOT_SPAN 1024
+#define DSNT_PCKH_BOOT_MAX_CHUNK_BLOCKS 1024
+#define DSNT_PCKH_BOOT_MAX_SPAN_BLOCKS 16
+int dsnt_pckh_boot(const float* pred, const float* target, const double* m, const double* b,
+                   const float* mask, const double* head, const int64_t* ids,
+                   const double* thresholds, int T, uint64_t seed, int R,
+                   unsigned long long* table, int B, int J, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation
  * data.py:118-226 (MPIIDataset.__getitem__, use_aug) batched on the device; semantics in csrc/augment.hip.
