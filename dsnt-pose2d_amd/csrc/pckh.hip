@@ -18,6 +18,19 @@ __device__ __forceinline__ double pckh_distance(const float* __restrict__ pred, 
     const double gx = tx * mm[0] + ty * mm[2] + bb[0], gy = tx * mm[1] + ty * mm[3] + bb[1];
     return sqrt((ox - gx) * (ox - gx) + (oy - gy) * (oy - gy)) / head[n];
 }
+// The two-index form of that expression, for the kernels that hold one point against many: prediction j against the
+// target of every joint k of its person (joint_confusion_kernel), the centre of every pixel against a target
+// (target_mass_kernel).  It comes in the expression's two halves, so that a point is back-projected once and not once
+// per pair: pckh_distance(i, n) is pckh_between(pckh_project(pred i), pckh_project(target i), head[n]), operation for
+// operation and in the same order.
+struct pckh_point { double x, y; };
+__device__ __forceinline__ pckh_point pckh_project(double x, double y, const double* __restrict__ mm,
+                                                   const double* __restrict__ bb) {
+    return {x * mm[0] + y * mm[2] + bb[0], x * mm[1] + y * mm[3] + bb[1]};
+}
+__device__ __forceinline__ double pckh_between(const pckh_point o, const pckh_point g, double head) {
+    return sqrt((o.x - g.x) * (o.x - g.x) + (o.y - g.y) * (o.y - g.y)) / head;
+}
 __global__ void pckh_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                             const double* __restrict__ m, const double* __restrict__ b,
                             const float* __restrict__ mask, const double* __restrict__ head,
@@ -472,4 +485,215 @@ extern "C" int dsnt_error_field(const float* pred, const float* target, const do
     DSNT_LAUNCH(error_field_kernel, dim3(J), dim3(DSNT_ERROR_FIELD_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
                 mask, head, threshold, e, hi, bins, (long long*)counts, sums, B, J);
     DSNT_CHECK_LAUNCH("dsnt_error_field");
+}
+
+// ---------------------------------------------------------------- what kind of miss
+// What dsnt_joint_confusion and dsnt_target_mass refuse alike, and the mirror as their kernels take it: by value, a byte
+// per joint, checked here on the host.  0 or the error code; nothing has touched a device.
+struct joint_mirror { unsigned char p[DSNT_CONFUSION_MAX_J]; };
+static_assert(DSNT_CONFUSION_MAX_J < 255, "a joint fits a byte, 255 marks a joint that does not count");
+static int confusion_args(const char* who, bool pointers, int B, int J, float threshold, const int* mirror,
+                          joint_mirror& out) {
+    DSNT_REQUIRE(pointers, DSNT_ERR_ARG, "%s: null pointer", who);
+    DSNT_REQUIRE(B > 0, DSNT_ERR_ARG, "%s: B=%d out of range", who, B);
+    DSNT_REQUIRE(J >= 1 && J <= DSNT_CONFUSION_MAX_J, DSNT_ERR_ARG, "%s: J=%d outside 1..%d", who, J,
+                 DSNT_CONFUSION_MAX_J);
+    DSNT_REQUIRE(threshold >= 0.f && threshold - threshold == 0.f, DSNT_ERR_ARG,
+                 "%s: threshold %g is negative or not finite", who, (double)threshold);
+    for (int j = 0; j < DSNT_CONFUSION_MAX_J; ++j) out.p[j] = (unsigned char)j;
+    for (int j = 0; j < J; ++j) {
+        DSNT_REQUIRE(mirror[j] >= 0 && mirror[j] < J && mirror[mirror[j]] == j, DSNT_ERR_ARG,
+                     "%s: mirror is not an involution of 0..%d (mirror[%d] = %d)", who, J - 1, j, mirror[j]);
+        out.p[j] = (unsigned char)mirror[j];
+    }
+    return DSNT_OK;
+}
+
+// Joint confusion (include/dsnt_hip.h: dsnt_joint_confusion): every counted joint adds 1 to one cell of table[J][J + 1],
+// the joint whose target its prediction landed on (its own: the hit of pckh_kernel) or column J for none, and mutual[J]
+// counts the mirrored pairs that landed on each other.  Integer adds only, so the tables do not depend on the order of
+// arrival, nor on how the examples are batched.  The unit of work is the person: a pass of a workgroup takes
+// BLOCK / J of them, thread (p, j) back-projects target j of person p into LDS once, then holds its prediction against the
+// person's J targets there, and leaves its cell in LDS for its mirror to read.  At most DSNT_CONFUSION_MAX_BLOCKS
+// workgroups stride over the persons; each counts in a u32 LDS copy [J][J + 2] (the table's columns, then mutual: a cell
+// takes at most one from each person) and flushes its non-zero cells with one 64-bit atomic each.
+static_assert(DSNT_CONFUSION_BLOCK >= DSNT_CONFUSION_MAX_J && DSNT_CONFUSION_BLOCK % 64 == 0,
+              "a pass holds at least one person");
+__global__ __launch_bounds__(DSNT_CONFUSION_BLOCK)
+void joint_confusion_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                            const double* __restrict__ m, const double* __restrict__ b, const float* __restrict__ mask,
+                            const double* __restrict__ head, float thr, const joint_mirror mirror,
+                            unsigned long long* table, unsigned long long* mutual, int B, int J) {
+    constexpr int BLOCK = DSNT_CONFUSION_BLOCK, NONE = 255;
+    __shared__ unsigned cnt[DSNT_CONFUSION_MAX_J * (DSNT_CONFUSION_MAX_J + 2)];
+    __shared__ double gx[BLOCK], gy[BLOCK];                    // the back-projected targets of this pass
+    __shared__ unsigned char ann[BLOCK], cell[BLOCK];          // target annotated (mask == 1); the joint's column, or NONE
+    __shared__ unsigned char mir[DSNT_CONFUSION_MAX_J];
+    const int tid = threadIdx.x, stride = J + 2, cells = J * stride;
+    const int per = BLOCK / J;                                 // persons of a pass
+    const int p = tid / J, j = tid - p * J, base = p * J;      // this thread's person of the pass, joint, and slot of joint 0
+    const double t = (double)thr;
+    for (int c = tid; c < cells; c += BLOCK) cnt[c] = 0u;
+    if (tid < J) mir[tid] = mirror.p[tid];
+    for (long n0 = (long)blockIdx.x * per; n0 < B; n0 += (long)gridDim.x * per) {
+        __syncthreads();                                       // the zeroes above, and the last pass's readers of cell
+        const long n = n0 + p;
+        bool counted = false;
+        pckh_point o = {0.0, 0.0};
+        double hd = 1.0;
+        if (p < per && n < B) {
+            const long i = n * J + j;
+            const double* mm = m + (size_t)n * 4;
+            const double* bb = b + (size_t)n * 2;
+            const pckh_point g = pckh_project(target[2 * i], target[2 * i + 1], mm, bb);
+            gx[tid] = g.x;
+            gy[tid] = g.y;
+            counted = mask[i] == 1.f;
+            ann[tid] = counted ? 1 : 0;
+            o = pckh_project(pred[2 * i], pred[2 * i + 1], mm, bb);
+            hd = head[n];
+        }
+        __syncthreads();
+        int c = NONE;
+        if (counted) {
+            c = J;                                             // no comparison holds for a NaN: it stays here
+            if (pckh_between(o, {gx[tid], gy[tid]}, hd) <= t) {
+                c = j;
+            } else {
+                double best = (double)INFINITY;
+                for (int k = 0; k < J; ++k) {                  // ascending k and a strict <: an exact tie keeps the smaller
+                    if (k == j || !ann[base + k]) continue;
+                    const double d = pckh_between(o, {gx[base + k], gy[base + k]}, hd);
+                    if (d <= t && d < best) {
+                        best = d;
+                        c = k;
+                    }
+                }
+            }
+            atomicAdd(cnt + j * stride + c, 1u);
+        }
+        cell[tid] = (unsigned char)c;
+        __syncthreads();
+        if (counted) {
+            const int mj = mir[j];                             // (a partner that is not counted holds NONE, never j)
+            if (mj != j && c == mj && cell[base + mj] == j) atomicAdd(cnt + j * stride + J + 1, 1u);
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < cells; c += BLOCK) {
+        const unsigned v = cnt[c];
+        if (!v) continue;
+        const int row = c / stride, col = c - row * stride;
+        if (col <= J) atomicAdd(table + row * (J + 1) + col, (unsigned long long)v);
+        else atomicAdd(mutual + row, (unsigned long long)v);
+    }
+}
+extern "C" int dsnt_joint_confusion(const float* pred, const float* target, const double* m, const double* b,
+                                    const float* mask, const double* head, float threshold, const int* mirror,
+                                    unsigned long long* table, unsigned long long* mutual, int B, int J, void* stream) {
+    joint_mirror mir;
+    if (const int rc = confusion_args("dsnt_joint_confusion", pred && target && m && b && mask && head && mirror && table &&
+                                      mutual, B, J, threshold, mirror, mir)) return rc;
+    const int per = DSNT_CONFUSION_BLOCK / J;
+    const long want = ((long)B + per - 1) / per;
+    const int grid = (int)(want < DSNT_CONFUSION_MAX_BLOCKS ? want : DSNT_CONFUSION_MAX_BLOCKS);
+    DSNT_LAUNCH(joint_confusion_kernel, dim3(grid), dim3(DSNT_CONFUSION_BLOCK), 0, (hipStream_t)stream, pred, target, m, b,
+                mask, head, threshold, mir, table, mutual, B, J);
+    DSNT_CHECK_LAUNCH("dsnt_joint_confusion");
+}
+
+// Heat-map mass at the target (include/dsnt_hip.h: dsnt_target_mass): one workgroup per row (n, j) sums the pixels of
+// hm[n][j] whose centre, back-projected, lies within the threshold of the joint's target, and of its mirror's target.
+// Thread t takes the pixels 4q .. 4q + 3 for q = t, t + BLOCK, ... in ascending order, one 16-byte load each with VEC4
+// and four scalar loads without, so both forms add the same numbers in the same order: fp64 partial sums per thread,
+// the xor tree across the wave, then the waves in ascending order.  Every pixel is tested: no bounding box.
+static_assert(DSNT_TARGET_MASS_BLOCK % 64 == 0 && DSNT_TARGET_MASS_BLOCK >= 64, "whole waves");
+template <bool VEC4>
+__global__ __launch_bounds__(DSNT_TARGET_MASS_BLOCK)
+void target_mass_kernel(const float* __restrict__ hm, const float* __restrict__ target, const double* __restrict__ m,
+                        const double* __restrict__ b, const float* __restrict__ mask, const double* __restrict__ head,
+                        float thr, const joint_mirror mirror, float* __restrict__ out, int J, int h, int w) {
+    constexpr int BLOCK = DSNT_TARGET_MASS_BLOCK, WAVES = BLOCK / 64;
+    __shared__ double red[2 * WAVES];
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x, n = row / J;
+    const int j = (int)(row - n * J);
+    if (!(mask[row] == 1.f)) {                                 // the same for every thread of the row
+        if (tid == 0) out[2 * row] = out[2 * row + 1] = NAN;
+        return;
+    }
+    const int mj = mirror.p[j];
+    const long partner = n * J + mj;
+    const bool two = mj != j && mask[partner] == 1.f;
+    const double* mm = m + (size_t)n * 4;
+    const double* bb = b + (size_t)n * 2;
+    const pckh_point g = pckh_project(target[2 * row], target[2 * row + 1], mm, bb);
+    const pckh_point gm = pckh_project(target[2 * partner], target[2 * partner + 1], mm, bb);      // (unused unless `two`)
+    const double hd = head[n], t = (double)thr, dw = (double)w, dh = (double)h;
+    const int hw = h * w, groups = (hw + 3) >> 2;
+    const float* __restrict__ px = hm + (size_t)row * hw;
+    double s0 = 0.0, s1 = 0.0;
+    for (int q = tid; q < groups; q += BLOCK) {
+        const int i0 = 4 * q;
+        float v[4];
+        if (VEC4) {
+            const float4 f = *reinterpret_cast<const float4*>(px + i0);
+            v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = i0 + u < hw ? px[i0 + u] : 0.f;
+        }
+        int r = i0 / w, c = i0 - r * w;
+        double y = (double)(2 * r + 1 - h) / dh;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (!VEC4 && i0 + u >= hw) break;
+            const double x = (double)(2 * c + 1 - w) / dw;     // the centre of pixel (r, c) on dsnt.nn.generate_xy's grid
+            const pckh_point o = pckh_project(x, y, mm, bb);
+            if (pckh_between(o, g, hd) <= t) s0 += (double)v[u];
+            if (two && pckh_between(o, gm, hd) <= t) s1 += (double)v[u];
+            ++c;
+            if (!VEC4 && c == w) {                             // (w % 4 == 0 with VEC4: the four share a row)
+                c = 0;
+                y = (double)(2 * ++r + 1 - h) / dh;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s0 += __shfl_xor(s0, o, 64);
+        s1 += __shfl_xor(s1, o, 64);
+    }
+    if ((tid & 63) == 0) {
+        red[2 * (tid >> 6)] = s0;
+        red[2 * (tid >> 6) + 1] = s1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        s0 = red[0];
+        s1 = red[1];
+        for (int wv = 1; wv < WAVES; ++wv) {
+            s0 += red[2 * wv];
+            s1 += red[2 * wv + 1];
+        }
+        out[2 * row] = (float)s0;
+        out[2 * row + 1] = two ? (float)s1 : NAN;
+    }
+}
+extern "C" int dsnt_target_mass(const float* heatmaps, const float* target, const double* m, const double* b,
+                                const float* mask, const double* head, float threshold, const int* mirror, float* out,
+                                int B, int J, int h, int w, void* stream) {
+    joint_mirror mir;
+    if (const int rc = confusion_args("dsnt_target_mass", heatmaps && target && m && b && mask && head && mirror && out, B, J,
+                                      threshold, mirror, mir)) return rc;
+    DSNT_REQUIRE((long)B * J < (1L << 31), DSNT_ERR_ARG, "dsnt_target_mass: B=%d out of range", B);
+    DSNT_REQUIRE(h > 0 && w > 0 && (long)h * w < (1L << 24), DSNT_ERR_SHAPE, "dsnt_target_mass: bad map size %dx%d", h, w);
+    const dim3 grid((unsigned)(B * J)), block(DSNT_TARGET_MASS_BLOCK);
+    if (w % 4 == 0 && dsnt_aligned16(heatmaps))
+        DSNT_LAUNCH(target_mass_kernel<true>, grid, block, 0, (hipStream_t)stream, heatmaps, target, m, b, mask, head,
+                    threshold, mir, out, J, h, w);
+    else
+        DSNT_LAUNCH(target_mass_kernel<false>, grid, block, 0, (hipStream_t)stream, heatmaps, target, m, b, mask, head,
+                    threshold, mir, out, J, h, w);
+    DSNT_CHECK_LAUNCH("dsnt_target_mass");
 }

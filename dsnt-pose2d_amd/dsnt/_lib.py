@@ -168,6 +168,8 @@ SIGNATURES = {
     'dsnt_score_hist': [P, P, P, P, P, P, P, P, I, P, I, P, I, I, P],
     'dsnt_score_lookup': [P, P, I, P, I, P, L, I, P],
     'dsnt_pckh_boot': [P, P, P, P, P, P, P, P, I, C.c_uint64, I, P, I, I, P],
+    'dsnt_joint_confusion': [P, P, P, P, P, P, F, P, P, P, I, I, P],
+    'dsnt_target_mass': [P, P, P, P, P, P, F, P, P, I, I, I, I, P],
     'dsnt_augment_fwd': [P, I, I, I, P, P, P, P, I, C.c_uint64, C.c_uint64, P, P, P, P],
     'dsnt_augment_fwd_pair': [P, I, I, I, P, P, P, P, I, C.c_uint64, C.c_uint64, P, P, P, P],
     'dsnt_augment_keypoints': [P, P, P, I, I, P, P, P, P, I, P, P, P, P, P],

@@ -21,8 +21,14 @@ coverage, an operating point and a monotone `ScoreCalibration` (applied on the d
 into `R + 1` copies of the curve's table, copy `r` weighting every example by a Poisson(1) draw keyed on the example's id
 (`dsnt_pckh_boot`), from which standard errors, percentile intervals and a paired comparison are read.
 
-The four table evaluators keep their joint names and their state in `_JointTables`; all five prepare a batch with
-`_batch_args`.
+`JointConfusion` asks what kind of miss it was: one launch per batch adds every valid joint to the cell of the joint of the
+same person its prediction landed on, its own (a hit), its mirror, another or none, and counts the mirrored pairs that were
+exchanged (`dsnt_joint_confusion`).  `target_mass` asks whether the heat-map was right and the read-out
+wrong: the mass of each joint's map within the threshold of the truth and of the mirror joint's truth, one launch
+(`dsnt_target_mass`), a per-joint score that `Reliability` tabulates against PCKh like any other.
+
+The five table evaluators keep their joint names and their state in `_JointTables`; all of them, and `target_mass`,
+prepare a batch with `_batch_args`.
 """
 import ctypes
 
@@ -559,6 +565,189 @@ class ErrorField(_JointTables):
             raise ValueError('tables of shape %s and %s for %d joints and %d bins'
                              % (tuple(counts.shape), tuple(sums.shape), self.n_joints, self.bins))
         self._take(counts, sums)
+
+
+def _mirror_of(mirror, n_joints):
+    """`mirror` as a list of `n_joints` ints, an involution of `0..n_joints-1` (`mirror[j] == j`: no partner).  None is
+    the MPII left/right permutation for 16 joints and the identity otherwise."""
+    if mirror is None:
+        if n_joints == len(PCKhEvaluator.JOINT_NAMES):
+            from .inference import HFLIP_INDICES      # (imported here: dsnt.inference imports this module)
+            mirror = HFLIP_INDICES.tolist()
+        else:
+            mirror = range(n_joints)
+    mirror = [int(v) for v in mirror]
+    if len(mirror) != n_joints:
+        raise ValueError('%d mirror indices for %d joints' % (len(mirror), n_joints))
+    for j, v in enumerate(mirror):
+        if not 0 <= v < n_joints or mirror[v] != j:
+            raise ValueError('mirror is not an involution of 0..%d (mirror[%d] = %d)' % (n_joints - 1, j, v))
+    return mirror
+
+
+def _fp32_threshold(threshold):
+    """One threshold as the fp64 value of its fp32 rounding, as `dsnt_pckh` holds it: finite and not negative."""
+    t = float(np.float32(threshold))
+    if not (np.isfinite(t) and t >= 0):
+        raise ValueError('the threshold must be finite and not negative, got %r' % (threshold,))
+    return t
+
+
+class JointConfusion(_JointTables):
+    """What kind of miss it was: which joint of the same person a prediction landed on (`dsnt_joint_confusion`,
+    DESIGN.md §21).
+
+    `table[j][k]`, int64 `[J, J + 1]`: every valid joint `j` adds 1 to exactly one cell of its row.  Column `j` is a hit
+    within `threshold` head lengths of its own target, the very hit `PCKhEvaluator(threshold)` counts; otherwise column
+    `k` is the annotated joint `k != j` of the same person whose target is nearest to the prediction among those within
+    `threshold` (an exact tie goes to the smallest `k`); otherwise column `J`: it landed on no annotated joint, which is
+    also where a NaN prediction ends.  `mutual[j]`, int64 `[J]`, counts the joints that landed on their `mirror` joint
+    while that joint, valid itself, landed on them: the pair was exchanged, which both collapsing onto one of the two
+    targets is not.  `mirror` is an involution of the joints (`mirror[j] == j`: no partner), by default
+    `inference.HFLIP_INDICES` for 16 joints and the identity otherwise.  Integer tables: they do not depend on batching,
+    order or sharding.  `name` below is a joint name, a group name or a joint index."""
+
+    MAX_JOINTS = 64                       # DSNT_CONFUSION_MAX_J
+
+    def __init__(self, threshold=0.5, n_joints=16, joint_names=None, joint_groups=None, mirror=None):
+        super().__init__(n_joints, joint_names, joint_groups)
+        if self.n_joints > self.MAX_JOINTS:
+            raise ValueError('at most %d joints, got %d' % (self.MAX_JOINTS, self.n_joints))
+        self.threshold = _fp32_threshold(threshold)
+        self.mirror = _mirror_of(mirror, self.n_joints)
+        self._mirror_arg = (ctypes.c_int * self.n_joints)(*self.mirror)       # host array, passed by value to the kernel
+        self._host = (torch.zeros(self.n_joints, self.n_joints + 1, dtype=torch.int64),
+                      torch.zeros(self.n_joints, dtype=torch.int64))
+
+    # ------------------------------------------------------------------ adding batches
+    def add_normalized(self, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b):
+        """Add a batch given in normalised coords (back-projected in fp64 as in `PCKhEvaluator.add_normalized`): one
+        kernel, no reduction and no host synchronisation."""
+        B, J = norm_pred.shape[0], norm_pred.shape[1]
+        if J != self.n_joints:
+            raise ValueError('%d joints, the tables have %d' % (J, self.n_joints))
+        args = _batch_args(norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b)
+        table, mutual = self._on(norm_pred.device)
+        call('dsnt_joint_confusion', *map(ptr, args), self.threshold, self._mirror_arg, ptr(table), ptr(mutual), B, J)
+
+    def add(self, pred, target, joint_mask, head_lengths):
+        """Add a batch whose coords are already in image space."""
+        self.add_normalized(pred, target, joint_mask, head_lengths, *self._identity_on(pred.device, pred.shape[0]))
+
+    # ------------------------------------------------------------------ reading results
+    def counts(self):
+        """The table, int64 `[J, J + 1]` on the host."""
+        return self._total()[0]
+
+    def mutual(self):
+        """The exchanges, int64 `[J]` on the host."""
+        return self._total()[1]
+
+    def _kinds(self, state, name):
+        """(valid, hit, mirror, nowhere, mutual) of the joints of `name` as Python ints; every row reads its own mirror
+        column."""
+        table, mutual = state
+        rows = self._rows(name)
+        J = self.n_joints
+        return (int(table[rows].sum()), sum(int(table[j, j]) for j in rows),
+                sum(int(table[j, self.mirror[j]]) for j in rows if self.mirror[j] != j),
+                sum(int(table[j, J]) for j in rows), sum(int(mutual[j]) for j in rows))
+
+    def _rates(self, state, name):
+        n, hit, mirror, nowhere, mutual = self._kinds(state, name)
+        if not n:
+            return dict.fromkeys(('hit', 'mirror', 'other', 'nowhere', 'mutual'), float('nan'))
+        return {'hit': hit / n, 'mirror': mirror / n, 'other': (n - hit - mirror - nowhere) / n, 'nowhere': nowhere / n,
+                'mutual': mutual / n}
+
+    def valid(self, name='total_mpii'):
+        return self._kinds(self._total(), name)[0]
+
+    def pckh(self, name='total_mpii'):
+        """hits / valid: `PCKhEvaluator(threshold)`'s figure; NaN when nothing was valid."""
+        return self._rates(self._total(), name)['hit']
+
+    def rates(self, name='total_mpii'):
+        """Shares of the valid joints of `name`: `hit`, `mirror` (landed on the mirror joint), `other` (on any other
+        joint), `nowhere` (on no annotated joint), which sum to 1, and `mutual` (the part of `mirror` that was an
+        exchange).  NaN when nothing was valid."""
+        return self._rates(self._total(), name)
+
+    def matrix(self, normalize=False):
+        """The table as numpy `[J, J + 1]`: the counts, or with `normalize` every row over its sum (f64, NaN for a row
+        without a valid joint)."""
+        table = self.counts().numpy()
+        return _ratio(table, table.sum(1, keepdims=True)) if normalize else table
+
+    def top(self, n=10):
+        """The `n` largest confusions: `(from, onto, count, share of from's misses)` for the joint-to-joint cells off
+        the diagonal that are not empty, by count descending, then by the two indices.  Joints go by name where they
+        have one."""
+        table = self.counts()
+        J = self.n_joints
+        label = self.joint_names or list(range(J))
+        misses = [int(table[j].sum()) - int(table[j, j]) for j in range(J)]
+        cells = [(-int(table[j, k]), j, k) for j in range(J) for k in range(J) if k != j and table[j, k] > 0]
+        return [(label[j], label[k], -c, -c / misses[j]) for c, j, k in sorted(cells)[:n]]
+
+    def summary(self):
+        """`rates` of every joint and group."""
+        state = self._total()
+        return {name: self._rates(state, name) for name in self._names()}
+
+    # ------------------------------------------------------------------ combining and saving
+    def _mergeable(self, other):
+        if (other.n_joints, other.threshold, other.mirror) != (self.n_joints, self.threshold, self.mirror):
+            raise ValueError('merge needs the same joints, threshold and mirror')
+
+    def state_dict(self):
+        table, mutual = self._total()
+        return {'threshold': self.threshold, 'mirror': torch.tensor(self.mirror, dtype=torch.int64), 'table': table,
+                'mutual': mutual}
+
+    def load_state_dict(self, state):
+        table, mutual = state['table'], state['mutual']
+        J = self.n_joints
+        if float(state['threshold']) != self.threshold or [int(v) for v in state['mirror']] != self.mirror:
+            raise ValueError('state of threshold %g and mirror %s, this table has %g and %s'
+                             % (state['threshold'], [int(v) for v in state['mirror']], self.threshold, self.mirror))
+        if tuple(table.shape) != (J, J + 1) or tuple(mutual.shape) != (J,):
+            raise ValueError('tables of shape %s and %s for %d joints' % (tuple(table.shape), tuple(mutual.shape), J))
+        self._take(table, mutual)
+
+
+def target_mass(heatmaps, norm_target, joint_mask, head_lengths, transform_m, transform_b, threshold=0.5, mirror=None):
+    """How much of each joint's heat-map lies where the truth is (`dsnt_target_mass`): f32 `[B, J, 2]` on
+    the device of `heatmaps` `[B, J, h, w]`, one launch and no host synchronisation.
+
+    `[..., 0]` is the sum of the joint's map over the pixels whose centre (`dsnt.nn.generate_xy`'s grid, back-projected
+    in fp64 as a prediction is) lies within `threshold` head lengths of the joint's target, `[..., 1]` the same round the
+    target of its `mirror` joint (`JointConfusion`'s `mirror`), NaN where the joint has no partner or the partner is not
+    annotated.  Both are NaN where `joint_mask` is not 1.  They are sums of the values as given, so they are
+    probabilities only for a normalised map (the 'dsnt' heat-maps; not raw logits or 'gauss' maps).  Summed in fp64 in a
+    fixed order: bit-reproducible.
+
+    A miss that held most of its mass at the truth is a failure of the read-out, one whose mass sits on the mirror joint
+    a failure of the map.  As a score, `Reliability` tabulates it against PCKh:
+
+        mass = target_mass(heatmaps, target, mask, head, m, b)
+        rel = Reliability([0.5], thresholds=(0.5,))
+        rel.add_normalized(pred, target, mask, head, m, b, mass[..., 0])
+        rate, support = rel.accuracy(0.5)      # row 1: the joints with at least half their mass at the truth, of which
+                                               # support[1] * (1 - rate[1]) missed all the same"""
+    if heatmaps.dim() != 4:
+        raise ValueError('heat-maps [B, J, h, w], got %s' % (tuple(heatmaps.shape),))
+    B, J, h, w = heatmaps.shape
+    if not 1 <= J <= JointConfusion.MAX_JOINTS:
+        raise ValueError('between 1 and %d joints, got %d' % (JointConfusion.MAX_JOINTS, J))
+    if tuple(norm_target.shape) != (B, J, 2) or tuple(joint_mask.shape) != (B, J):
+        raise ValueError('targets of shape %s and a mask of shape %s for %d x %d joints'
+                         % (tuple(norm_target.shape), tuple(joint_mask.shape), B, J))
+    mirror, threshold = _mirror_of(mirror, J), _fp32_threshold(threshold)
+    args = _batch_args(heatmaps, norm_target, joint_mask, head_lengths, transform_m, transform_b)       # the maps: f32
+    out = torch.empty(B, J, 2, dtype=torch.float32, device=heatmaps.device)
+    call('dsnt_target_mass', *map(ptr, args), threshold, (ctypes.c_int * J)(*mirror), ptr(out), B, J, h, w)
+    return out
 
 
 def _ratio(num, den):

@@ -864,6 +864,57 @@ int dsnt_pckh_boot(const float* pred, const float* target, const double* m, cons
                    const float* mask, const double* head, const int64_t* ids,
                    const double* thresholds, int T, uint64_t seed, int R,
                    unsigned long long* table, int B, int J, void* stream);
+/* What kind of miss was it?  One launch ADDS a batch to a joint-confusion table: which joint of the same person a
+ * prediction landed on.  pred, target, m, b, mask, head and threshold are dsnt_pckh's.  With P_j the back-projected
+ * prediction of a counted joint j (mask[n][j] == 1), G_k the back-projected target of every annotated joint k of the same
+ * person (mask[n][k] == 1), d_jk = |P_j - G_k| / head[n] (dsnt_pckh's fp64 expression, which d_jj is) and t the threshold
+ * widened to fp64, the joint adds 1 to exactly one cell of table[j]:
+ *   d_jj <= t: column j, the very hit dsnt_pckh counts;
+ *   otherwise column k, the annotated k != j of smallest d_jk among those with d_jk <= t (an exact tie goes to the
+ *   smallest k);
+ *   otherwise column J: it landed on no annotated joint.  A NaN prediction ends here, as does an inf or NaN d from a zero
+ *   head length: no comparison holds.
+ * A joint that is not counted adds nothing, and a target that is not annotated attracts nothing: its coordinates may be
+ * NaN.  The row sums are dsnt_pckh's valid counts and the diagonal its hits.
+ * mirror: HOST int[J], an involution of 0..J-1 (mirror[mirror[j]] == j; mirror[j] == j: no partner), checked on the host
+ * and passed by value to the kernel, never read from device memory.  For m = mirror[j] != j, mutual[j] gets 1 when the
+ * cell of j is column m, m is counted and the cell of m is column j: the pair was exchanged, which a collapse of both
+ * onto one target is not.  mutual[j] == mutual[mirror[j]] always.
+ * table: device u64 [J][J + 1], mutual: device u64 [J]; the kernel only adds (64-bit integer atomics: order-independent,
+ * bit-reproducible, the same however the examples are batched), the caller zeroes.
+ * DSNT_ERR_ARG and nothing launched for, in this order: a null pointer, B <= 0, J outside 1..DSNT_CONFUSION_MAX_J, a
+ * threshold that is negative or not finite, a mirror that is not an involution (the message names the first j with
+ * mirror[j] outside 0..J-1 or mirror[mirror[j]] != j).
+ * The unit of work is the person: min(ceil(B / per), DSNT_CONFUSION_MAX_BLOCKS) workgroups of DSNT_CONFUSION_BLOCK
+ * threads stride over the persons, per = DSNT_CONFUSION_BLOCK / J at a time; the J targets of a person are back-projected
+ * once, into LDS.  Each workgroup counts in a u32 LDS copy [J][J + 2] (table, then mutual) and flushes its non-zero cells
+ * with one 64-bit atomic each.  dsnt_version() >= 128. */
+#define DSNT_CONFUSION_MAX_J 64
+#define DSNT_CONFUSION_BLOCK 256
+#define DSNT_CONFUSION_MAX_BLOCKS 64
+int dsnt_joint_confusion(const float* pred, const float* target, const double* m, const double* b,
+                         const float* mask, const double* head, float threshold, const int* mirror,
+                         unsigned long long* table, unsigned long long* mutual, int B, int J, void* stream);
+/* Was the heat-map right and the read-out wrong?  The mass of a joint's heat-map that lies within the threshold of the
+ * truth, and of the mirrored joint's truth.  heatmaps: device f32 [B][J][h][w]; target, m, b, mask, head, threshold and
+ * mirror are dsnt_joint_confusion's.  The centre of pixel (r, c) has the normalised coordinates x = (2c + 1 - w) / w,
+ * y = (2r + 1 - h) / h (fp64; dsnt.nn.generate_xy's grid); it is back-projected as a prediction is, and its distance to a
+ * target in head lengths is dsnt_pckh's expression with these fp64 coordinates in place of the prediction's.
+ * out: device f32 [B][J][2].  For a counted joint (mask[n][j] == 1) out[n][j][0] = the sum of hm[n][j] over the pixels
+ * within the threshold of G_j, and out[n][j][1] the same round G_mirror[j], or NaN when mirror[j] == j or the mirror joint
+ * is not annotated; both are NaN when the joint is not counted.  The sums are of the values as given: probabilities only
+ * for a normalised map.  0 when the disc holds no pixel centre.
+ * Summed in fp64 in a fixed order and rounded to f32 once: bit-reproducible, and the same for any alignment of
+ * `heatmaps`.  One workgroup of DSNT_TARGET_MASS_BLOCK threads per (n, j); thread t takes the pixels 4q .. 4q + 3 of the
+ * flat map for q = t, t + DSNT_TARGET_MASS_BLOCK, ... (one 16-byte load each when w % 4 == 0 and heatmaps is 16-byte
+ * aligned, scalar loads otherwise), then a xor tree across each wave and the waves in ascending order.  Every pixel is
+ * tested and the map is read once.
+ * Refuses what dsnt_joint_confusion refuses, with its own name in the message, then B * J >= 2^31 (DSNT_ERR_ARG) and maps
+ * dsnt_heatmap_stats refuses: h, w > 0 and h * w < 2^24 (DSNT_ERR_SHAPE).  dsnt_version() >= 128. */
+#define DSNT_TARGET_MASS_BLOCK 256
+int dsnt_target_mass(const float* heatmaps, const float* target, const double* m, const double* b,
+                     const float* mask, const double* head, float threshold, const int* mirror, float* out,
+                     int B, int J, int h, int w, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation
  * data.py:118-226 (MPIIDataset.__getitem__, use_aug) batched on the device; semantics in csrc/augment.hip.
