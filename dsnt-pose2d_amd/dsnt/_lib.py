@@ -170,6 +170,7 @@ SIGNATURES = {
     'dsnt_pckh_boot': [P, P, P, P, P, P, P, P, I, C.c_uint64, I, P, I, I, P],
     'dsnt_joint_confusion': [P, P, P, P, P, P, F, P, P, P, I, I, P],
     'dsnt_target_mass': [P, P, P, P, P, P, F, P, P, I, I, I, I, P],
+    'dsnt_map_modes': [P, L, I, I, I, I, I, P, P, P, P, P, P, P],
     'dsnt_augment_fwd': [P, I, I, I, P, P, P, P, I, C.c_uint64, C.c_uint64, P, P, P, P],
     'dsnt_augment_fwd_pair': [P, I, I, I, P, P, P, P, I, C.c_uint64, C.c_uint64, P, P, P, P],
     'dsnt_augment_keypoints': [P, P, P, I, I, P, P, P, P, I, P, P, P, P, P],

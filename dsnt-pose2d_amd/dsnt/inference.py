@@ -18,6 +18,10 @@ launch (`flip_merge_head`, `dsnt_flip_merge_head`) merges the last stack's logit
 
 `return_stats=True` on the three adds a confidence and a spread per joint, taken from the heat-map the coordinates come
 from (see `STATS_DOC`); `calibration=` (an `evaluator.ScoreCalibration`) turns one of them into `p_correct`.
+
+`readout='mode'` on the three replaces the global expectation (or, for 'gauss', the arg-max) by the centroid of the
+map's dominant mode (`nn.heatmap_modes`, `dsnt_map_modes`): the read-out that does not land between the
+two bumps of a bimodal map.  `return_modes=True` adds the two dominant modes per joint (see `MODES_DOC`).
 """
 import ctypes
 import time
@@ -110,6 +114,24 @@ better) and `sqrt(trace(cov_image))` (spread in pixels, lower is better) are the
 there) the dict gains
   * `p_correct` f32 `[B, J]`: `cal(stat_score(stats, cal.score))`, the validation set's P(joint within the PCKh threshold)
     at this score (`dsnt_score_lookup`; NaN for a `predict_boxes` sample without a crop)."""
+
+
+MODES_DOC = """The per-joint modes dict (`return_modes=True`): what `nn.heatmap_modes(map, mode_radius, 2, transform_m,
+transform_b)` gives on the map the prediction comes from, device tensors
+  * `coords` f32 `[B, J, 2, 2]`: the normalised centroid of the dominant mode (`[:, :, 0]`) and of the runner-up
+    (`[:, :, 1]`, typically the mirrored joint), and `image` f64 `[B, J, 2, 2]`: the same in original-image pixels;
+  * `mass` f32 `[B, J, 2]`: the map's sum over each mode's window.  It is a score like any other: `mass[..., 0]` goes into
+    `evaluator.Reliability` directly, as `evaluator.target_mass` does;
+  * `index` int32 `[B, J, 2]`: the windows' centres `y * w + x`; -1 (and NaN elsewhere) where the map has no second mode, and
+    for a `predict_boxes` sample without a crop."""
+
+
+def _check_readout(model, readout):
+    if readout not in ('mean', 'mode'):
+        raise ValueError("dsnt: readout must be 'mean' or 'mode', not %r" % (readout,))
+    if readout == 'mode' and model.output_strat == 'fc':
+        raise ValueError("dsnt: readout='mode' reads the heat-map; the 'fc' strategy predicts from its linear layer, not "
+                         'from the map')
 
 
 def _calibrate(st, return_stats, calibration):
@@ -211,7 +233,7 @@ def _set_heatmaps(model, hm):
 
 
 def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=False, return_normalized=False,
-            return_stats=False, calibration=None):
+            return_stats=False, calibration=None, readout='mean', mode_radius=3, return_modes=False):
     """Joint positions in original-image pixels for a batch, on the device: f64 `[B, J, 2]`.
 
     `inputs` f32 `[B, 3, S, S]` on the device, or with `paired=True` the `[2B, 3, S, S]` `input_pair` of
@@ -232,7 +254,15 @@ def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=Fa
       * no flip: `dsnt_heatmap_stats` on the last stack's heat-maps (for an hourglass NOT `model.heatmaps`, which is the
         first stack's) after the forward.
     `calibration` (with `return_stats=True`): the dict also holds `p_correct`, one more launch; everything else keeps its
-    bits."""
+    bits.
+    `readout='mode'`: the returned image and normalised coordinates are those of mode 0 of `nn.heatmap_modes(map,
+    mode_radius)` on the map the prediction comes from: the merged map the fused launch stores with flip,
+    `_predicted_map(model)` without.  One more launch (`dsnt_map_modes`), no host synchronisation; the statistics dict is
+    untouched.  'gauss' is allowed (the window centroid of the raw map is a sub-pixel decode); 'fc' raises `ValueError`.
+    `readout='mean'` (the default) is the behaviour described above, bit for bit.
+    `return_modes=True` appends the dict of `MODES_DOC` (the two dominant modes) after the statistics dict, if any; the
+    one launch then serves both (and the mode-0 read-out is copied out of it)."""
+    _check_readout(model, readout)
     model.eval()
     S = 2 if (use_flipped and paired) else 1
     if inputs.size(0) % S:
@@ -261,41 +291,56 @@ def predict(model, inputs, transform_m, transform_b, use_flipped=True, paired=Fa
             coords = dutil.decode_heatmaps(out) if model.output_strat == 'gauss' else out.detach().float()
             img = torch.baddbmm(tb, coords.double(), tm)
             st = [_map_stats(_predicted_map(model), tm, model.output_strat != 'gauss')] if return_stats else []
+        if readout == 'mode' or return_modes:
+            # (with flip, `_set_heatmaps` has put the merged map the fused launch stored there)
+            modes = dnn.heatmap_modes(_predicted_map(model), mode_radius, 2 if return_modes else 1, tm, tb)
+            if readout == 'mode':       # (with one mode the views are contiguous as they are: no copy)
+                img, coords = modes['image'][:, :, 0].contiguous(), modes['coords'][:, :, 0].contiguous()
     _calibrate(st, return_stats, calibration)
     res = (img, coords) if return_normalized else (img,)
     res += tuple(st)
+    if return_modes:
+        res += (modes,)
     return res if len(res) > 1 else res[0]
 
 
 def predict_dataset(model, dataset, use_flipped=True, batch_size=32, time_meter=None, return_stats=False,
-                    calibration=None):
+                    calibration=None, readout='mean', mode_radius=3, return_modes=False):
     """`generate_predictions` at any batch size: a CPU DoubleTensor `[len(dataset), J, 2]` of joint positions in
     original-image pixels, per sample what the batch-1 flip loop gives.  Predictions stay on the device until the
     one copy at the end; with a `time_meter` each batch is timed, which synchronises once per batch.
     `return_stats=True` returns `(predictions, stats)`: the statistics dict of `STATS_DOC` over the whole dataset as CPU
-    tensors, concatenated on the device and copied once like the predictions; with `calibration`, `p_correct` among them."""
+    tensors, concatenated on the device and copied once like the predictions; with `calibration`, `p_correct` among them.
+    `readout` and `mode_radius` are `predict`'s; `return_modes=True` appends the modes dict of `MODES_DOC` over the whole
+    dataset to the result, concatenated and copied the same way."""
+    _check_readout(model, readout)
     model.cuda()
     model.eval()
     loader = DataLoader(dataset, batch_size, num_workers=0)
-    preds, stats = [], []
+    preds, stats, modes = [], [], []
     for batch in loader:
         start = time.perf_counter()
         img = predict(model, batch['input'].cuda(), batch['transform_m'].cuda(), batch['transform_b'].cuda(),
-                      use_flipped=use_flipped, return_stats=return_stats, calibration=calibration)
-        if return_stats:
-            img, st = img
-            stats.append(st)
+                      use_flipped=use_flipped, return_stats=return_stats, calibration=calibration, readout=readout,
+                      mode_radius=mode_radius, return_modes=return_modes)
+        if return_stats or return_modes:
+            img, *extra = img
+            if return_stats:
+                stats.append(extra[0])
+            if return_modes:
+                modes.append(extra[-1])
         if time_meter is not None:
             torch.cuda.synchronize()
             time_meter.add(time.perf_counter() - start)
         preds.append(img)
     if not preds:
         empty = torch.zeros(0, 16, 2, dtype=torch.float64)
-        return (empty, {}) if return_stats else empty
-    out = torch.cat(preds, 0).cpu()
-    if not return_stats:
-        return out
-    return out, {k: torch.cat([s[k] for s in stats], 0).cpu() for k in stats[0]}
+        res = (empty,) + ({},) * (int(return_stats) + int(return_modes))
+        return res if len(res) > 1 else empty
+    res = (torch.cat(preds, 0).cpu(),)
+    for dicts in ([stats] if return_stats else []) + ([modes] if return_modes else []):
+        res += ({k: torch.cat([d[k] for d in dicts], 0).cpu() for k in dicts[0]},)
+    return res if len(res) > 1 else res[0]
 
 
 _box_augment = {}
@@ -315,7 +360,7 @@ def _box_augment_for(specs, mean, std, device):
 
 
 def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_size=384, return_normalized=False,
-                  return_stats=False, calibration=None):
+                  return_stats=False, calibration=None, readout='mean', mode_radius=3, return_modes=False):
     """Joint positions in original-image pixels for person boxes in full images: f64 `[B, J, 2]` on the device.
 
     `pool` a `data.ImagePool`; sample b is image `idx[b]` (int64 `[B]`) with the box matrix `matrix[b]` (f64
@@ -331,7 +376,10 @@ def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_si
     normalisation constants).  `return_normalized=True` returns `(image_coords, normalised f32 coords)`.
     `return_stats=True` appends the statistics dict of `STATS_DOC`; `cov_image` follows the transposed `transform_m`, so
     it is in the image's pixels for any invertible box matrix, and a sample without a crop has NaN statistics (its
-    `peak_index` is -1).  With `calibration` the dict also holds `p_correct`, NaN for such a sample."""
+    `peak_index` is -1).  With `calibration` the dict also holds `p_correct`, NaN for such a sample.
+    `readout`, `mode_radius` and `return_modes` are `predict`'s; the modes dict of a sample without a crop is NaN, its
+    `index` -1."""
+    _check_readout(model, readout)
     crops, valid = pool.crop(idx, matrix, crop_size)
     B, dev = crops.shape[0], crops.device
     aug = _box_augment_for(model.image_specs, mean, std, dev)
@@ -344,11 +392,12 @@ def predict_boxes(model, pool, idx, matrix, mean, std, use_flipped=True, crop_si
     tm = s['transform_m'].transpose(1, 2).contiguous()
     img, coords, *st = predict(model, s['input_pair'] if use_flipped else s['input'], tm, s['transform_b'],
                                use_flipped=use_flipped, paired=use_flipped, return_normalized=True,
-                               return_stats=return_stats, calibration=calibration)
+                               return_stats=return_stats, calibration=calibration, readout=readout,
+                               mode_radius=mode_radius, return_modes=return_modes)
     img = torch.where(valid.view(B, 1, 1), img, float('nan'))
     res = (img, torch.where(valid.view(B, 1, 1), coords, float('nan'))) if return_normalized else (img,)
-    if return_stats:
-        def mask(t):
-            return torch.where(valid.view(B, *([1] * (t.dim() - 1))), t, -1 if t.dtype == torch.int32 else float('nan'))
-        res += ({k: mask(v) for k, v in st[0].items()},)
+    def mask(t):
+        return torch.where(valid.view(B, *([1] * (t.dim() - 1))), t, -1 if t.dtype == torch.int32 else float('nan'))
+    for d in st:            # the statistics dict, then the modes dict
+        res += ({k: mask(v) for k, v in d.items()},)
     return res if len(res) > 1 else res[0]

@@ -101,6 +101,57 @@ def heatmap_stats(heatmaps):
     return _stats_dict(stats, index, hm.shape[:-2])
 
 
+# ------------------------------------------------------------------ mode-seeking read-out of heat-maps
+MODES_MAX_RADIUS, MODES_MAX_COUNT = 8, 4      # DSNT_MODES_MAX_RADIUS, DSNT_MODES_MAX_K of include/dsnt_hip.h
+
+
+def heatmap_modes(heatmaps, radius=3, count=2, transform_m=None, transform_b=None):
+    """The `count` dominant modes of heat-maps `[..., J, H, W]` as window centroids (`dsnt_map_modes`, one launch, DESIGN.md
+    §22): where a bimodal map's expectation lands between its modes, mode 0 is the heavier one and mode 1 the runner-up.
+
+    The window score of a pixel is the sum of the map over the `(2 radius + 1)^2` window about it, clipped to the map.
+    Mode 0 is the first pixel (row-major) with the largest score, mode k the same among the pixels further than
+    `2 radius` (Chebyshev) from every earlier mode, so the windows are disjoint.  The maps are used as given.  A dict of
+    device tensors:
+      * `coords` f32 `[..., J, K, 2]`: the centroid `(x, y)` of the map over the mode's window, on the DSNT grid;
+      * `mass` f32 `[..., J, K]`: the sum of the map over the window (a share of 1 for softmax maps);
+      * `index` int32 `[..., J, K]`: the window's centre `y * W + x`, -1 when there is no such mode (then `mass` and
+        `coords` are NaN; `coords` are also NaN when the window's sum is not positive);
+      * `image` f64 `[..., J, K, 2]` when `transform_m` `[B, 2, 2]` and `transform_b` `[B, 1, 2]` are given (both or
+        neither; `B` the product of the leading dimensions): `transform_b + coords @ transform_m`, as `predict` does.
+    `radius` 0..8, `count` 1..4, `H * W <= 8192`.  `radius=0` makes mode 0 the peak pixel of `heatmap_stats`; a radius
+    that covers the map makes it the global mean, with no mode 1.  Forward only.  Device tensors only."""
+    hm = f32(heatmaps.detach()).contiguous()
+    if hm.dim() < 3:
+        raise RuntimeError('dsnt: heatmap_modes needs [..., J, H, W], got %s' % (tuple(hm.shape),))
+    if (transform_m is None) != (transform_b is None):
+        raise ValueError('dsnt: heatmap_modes needs transform_m and transform_b together')
+    if not 0 <= int(radius) <= MODES_MAX_RADIUS:
+        raise ValueError('dsnt: heatmap_modes: radius=%r outside 0..%d' % (radius, MODES_MAX_RADIUS))
+    if not 1 <= int(count) <= MODES_MAX_COUNT:
+        raise ValueError('dsnt: heatmap_modes: count=%r outside 1..%d' % (count, MODES_MAX_COUNT))
+    J, h, w = hm.shape[-3:]
+    rows, K, lead = _rows(hm, 2), int(count), tuple(hm.shape[:-2])
+    coords = torch.empty(*lead, K, 2, device=hm.device, dtype=torch.float32)
+    mass = torch.empty(*lead, K, device=hm.device, dtype=torch.float32)
+    index = torch.empty(*lead, K, device=hm.device, dtype=torch.int32)
+    tm = tb = image = None
+    if transform_m is not None:
+        B = rows // max(J, 1)
+        tm = transform_m.to(device=hm.device, dtype=torch.float64).contiguous()
+        tb = transform_b.to(device=hm.device, dtype=torch.float64).contiguous()
+        if tm.numel() != 4 * B or tb.numel() != 2 * B:
+            raise RuntimeError('dsnt: heatmap_modes: transform_m %s / transform_b %s for %d samples'
+                               % (tuple(tm.shape), tuple(tb.shape), B))
+        image = torch.empty(*lead, K, 2, device=hm.device, dtype=torch.float64)
+    call('dsnt_map_modes', ptr(hm), rows, J, h, w, int(radius), K, ptr(tm), ptr(tb), ptr(coords), ptr(mass), ptr(index),
+         ptr(image))
+    out = {'coords': coords, 'mass': mass, 'index': index}
+    if image is not None:
+        out['image'] = image
+    return out
+
+
 # ------------------------------------------------------------------ 'fc' output strategy (model.py:222-223, 293-303)
 class _Fc2(Function):
     @staticmethod

@@ -915,6 +915,37 @@ int dsnt_joint_confusion(const float* pred, const float* target, const double* m
 int dsnt_target_mass(const float* heatmaps, const float* target, const double* m, const double* b,
                      const float* mask, const double* head, float threshold, const int* mirror, float* out,
                      int B, int J, int h, int w, void* stream);
+/* Mode-seeking read-out: the K dominant modes of each heat-map as window centroids (csrc/modes.hip).
+ * hm: device f32 [rows][h][w], one map p per row, used as given (nothing is normalised); rows = B J, sample b = row / J.
+ * radius r in map pixels, 0..DSNT_MODES_MAX_RADIUS; K modes, 1..DSNT_MODES_MAX_K.
+ * Window score S[y][x] = the sum of p over the (2r+1)^2 window centred on (y, x), clipped to the map, in fp32 in this
+ * order: s[y][x] = sum_{d=-r..r} p[y][x+d] in ascending d from +0, a pixel outside the map adding +0, then
+ * S[y][x] = sum_{d=-r..r} s[y+d][x] by the same rule; every add is rounded separately (no sliding window).
+ * Mode 0 is the centre with the largest S: scanning in row-major order from best = -inf a candidate wins only if
+ * S > best, so an exact tie goes to the smallest index y w + x, a NaN S never wins, and a row without a winner has index
+ * -1.  Mode k > 0 is chosen the same way among the centres whose Chebyshev distance from every earlier mode's centre
+ * exceeds 2r (its window is disjoint from theirs); -1 when there is none.
+ * Per mode, with the sums over its clipped window in fp64 (per window row in ascending x from +0, then the rows in
+ * ascending y from +0; X p and Y p rounded before they are added) on the grid X = (2x+1)/w - 1, Y = (2y+1)/h - 1 (fp64):
+ *   index  i32 [rows][K]     the centre y w + x, or -1
+ *   mass   f32 [rows][K]     (float) sum p
+ *   coords f32 [rows][K][2]  (float)(sum X p / sum p), (float)(sum Y p / sum p)
+ *   image  f64 [rows][K][2]  transform_b[b] + coords . transform_m[b] on row vectors (dsnt_flip_merge_head's convention),
+ *                            from the f32-rounded coordinates; transform_m f64 [B][2][2], transform_b f64 [B][2].
+ *                            Optional: transform_m, transform_b and image are all NULL or all non-NULL.
+ * When sum p is not > 0, coords and image are NaN and mass is as computed; for index -1 mass, coords and image are NaN.
+ * One workgroup of 256 threads per row, the row and its row sums in two LDS planes (h w <= DSNT_MODES_MAX_PIXELS: 64 KiB);
+ * plain stores, no atomics: bit-reproducible, and the same for any alignment of hm (16-byte loads when w % 4 == 0 and hm
+ * is 16-byte aligned, scalar loads otherwise).
+ * Refused, nothing launched, in this order: a null hm, coords, mass or index; rows outside 1..2^31-1, J < 1 or
+ * rows % J != 0; radius; K; inconsistent optional pointers (DSNT_ERR_ARG); h, w < 1 or h w > DSNT_MODES_MAX_PIXELS
+ * (DSNT_ERR_SHAPE: dsnt_heatmap_stats takes larger maps).  dsnt_version() >= 129. */
+#define DSNT_MODES_MAX_RADIUS 8
+#define DSNT_MODES_MAX_K 4
+#define DSNT_MODES_MAX_PIXELS 8192
+int dsnt_map_modes(const float* hm, int64_t rows, int J, int h, int w, int radius, int K,
+                   const double* transform_m, const double* transform_b,
+                   float* coords, float* mass, int* index, double* image, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation
  * data.py:118-226 (MPIIDataset.__getitem__, use_aug) batched on the device; semantics in csrc/augment.hip.
