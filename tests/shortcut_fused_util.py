@@ -57,8 +57,9 @@ def _bn_a_bound(o, M):
     return U.bmax(U.bn_bound(o['gamma'], o['beta'], M, DEV), U.dev_amax(act32.to(DEV), U.LOOSE_A))
 
 
-def forward(Cin, Cout, M):
-    """(pair, fused): out, statistics rows, both bound slots of the two existing launches and of the fused one."""
+def forward(Cin, Cout, M, flags=0):
+    """(pair, fused): out, statistics rows, both bound slots of the two existing launches and of the fused one.
+    flags: DSNT_CONV_SHARE_CHIP (2) on the conv3 launch of the pair and on the fused launch — the same plan for both."""
     from dsnt import _lib
     from dsnt._lib import ptr, call, BnTail
     o = operands(Cin, Cout, M)
@@ -68,7 +69,7 @@ def forward(Cin, Cout, M):
     p3, wb3 = U.prep_weights(d['w3'])
     pd, wbd = U.prep_weights(d['wd'])
     ab3, abd = _bn_a_bound(o, M), U.dev_amax(d['x'], U.LOOSE_A)
-    rows = _lib.fn('dsnt_conv1x1_fwd_stats_rows')(C.byref(g), 0)
+    rows = _lib.fn('dsnt_conv1x1_fwd_stats_rows')(C.byref(g), flags)
     asc, ash = d['gamma'][:1].expand(Cout).contiguous(), d['beta'][:1].expand(Cout).contiguous()
     n = d['w3'].numel()
 
@@ -85,12 +86,12 @@ def forward(Cin, Cout, M):
     call('dsnt_conv1x1_fwd_f16x3', ptr(d['x']), ptr(pd), n, ptr(wbd), ptr(abd), ptr(d['bd']), ptr(skip), None, None, 0, None, None,
          C.byref(g), None)
     y, stats, amax, amax_bn, tl = outputs()
-    call('dsnt_conv1x1_fwd_f16x3', ptr(d['y2']), ptr(p3), n, ptr(wb3), ptr(ab3), ptr(d['b3']), ptr(y), ptr(d['sc']), ptr(d['sh']), 1,
+    call('dsnt_conv1x1_fwd_f16x3', ptr(d['y2']), ptr(p3), n, ptr(wb3), ptr(ab3), ptr(d['b3']), ptr(y), ptr(d['sc']), ptr(d['sh']), 1 | flags,
          ptr(skip), ptr(stats), C.byref(g), C.byref(tl))
     pair = dict(out=y, stats=stats, amax=amax, amax_bn=amax_bn)
     y, stats, amax, amax_bn, tl = outputs()
     call('dsnt_conv1x1_fwd_ds_f16x3', ptr(d['y2']), ptr(d['x']), ptr(p3), ptr(pd), n, ptr(wb3), ptr(wbd), ptr(ab3), ptr(abd),
-         ptr(d['b3']), ptr(d['bd']), ptr(y), ptr(d['sc']), ptr(d['sh']), 1, ptr(stats), C.byref(g), C.byref(g), C.byref(tl))
+         ptr(d['b3']), ptr(d['bd']), ptr(y), ptr(d['sc']), ptr(d['sh']), 1 | flags, ptr(stats), C.byref(g), C.byref(g), C.byref(tl))
     torch.cuda.synchronize()
     return pair, dict(out=y, stats=stats, amax=amax, amax_bn=amax_bn), rows
 

@@ -10,18 +10,10 @@ import torch.nn.functional as F
 
 from dsnt import synthetic
 
+import conv_checks as K     # the comparisons of the fp16x3 streaming kernels, shared with tests/test_plan_edges_gpu.py
+from conv_checks import geom as _geom, nhwc as _nhwc
+
 pytestmark = pytest.mark.gpu
-
-
-def _nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-def _geom(N, H, W, Cin, Cout, R, S, stride, pad, dil):
-    from dsnt._lib import ConvGeom
-    Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
-    return ConvGeom(N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)
 
 
 CASES = [
@@ -445,49 +437,7 @@ def test_conv_f16x3_matches_fp32_accuracy(case, pro, loose):
     """fp16x3 (two fp16 planes after a power-of-two scale, three MFMAs): the same bars as bf16x6 — 2e-5 of the output
     scale vs torch fp32 and an fp64 check that its error is of fp32 size — with the exact operand bound and with a
     bound 64x too large (what the analytic BatchNorm bound typically is)."""
-    from dsnt import _lib
-    from dsnt._lib import ptr, call
-    N, H, W, Cin, Cout, k, stride, pad, dil = case
-    dev = torch.device('cuda:0')
-    tag = 'c' + '_'.join(map(str, case))
-    x = synthetic.tensor(tag + 'x', (N, Cin, H, W), seed=1)
-    w = synthetic.tensor(tag + 'w', (Cout, Cin, k, k), seed=1, scale=(2.0 / (Cin * k * k)) ** 0.5)
-    b = synthetic.tensor(tag + 'b', (Cout,), seed=1, scale=0.1)
-    sc = synthetic.tensor(tag + 's', (Cin,), seed=1, kind='uniform').abs() + 0.5
-    sh = synthetic.tensor(tag + 'h', (Cin,), seed=1, scale=0.3)
-    g = _geom(N, H, W, Cin, Cout, k, k, stride, pad, dil)
-    act = F.relu(x * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)) if pro else x
-    y32 = F.conv2d(act, w, b, stride=stride, padding=pad, dilation=dil)
-    y64 = F.conv2d(act.double(), w.double(), b.double(), stride=stride, padding=pad, dilation=dil)
-    res = synthetic.tensor(tag + 'r', tuple(y32.shape), seed=1)
-    xd = _nhwc(x).to(dev)
-    wd = w.permute(0, 2, 3, 1).contiguous().to(dev)
-    wb, ab = torch.zeros(64, device=dev), torch.zeros(64, device=dev)
-    call('dsnt_amax', ptr(wd), wd.numel(), ptr(wb))
-    assert wb.max().item() == wd.abs().max().item()
-    planes = torch.empty(2 * wd.numel(), dtype=torch.float16, device=dev)
-    call('dsnt_split_f16x2', ptr(wd), ptr(planes), wd.numel(), wd.numel(), ptr(wb))
-    # the two planes carry the scaled weights to ~2^-23 of the largest
-    import math
-    s_w = 2.0 ** (13 - math.floor(math.log2(wb.max().item())))
-    back = planes.view(2, -1).double().sum(0) / s_w
-    assert (back - wd.reshape(-1).double()).abs().max().item() <= 2.0 ** -22 * wd.abs().max().item()
-    ab[7] = act.abs().max().item() * loose            # any slot may hold the maximum
-    bd, scd, shd, resd = b.to(dev), sc.to(dev), sh.to(dev), _nhwc(res).to(dev)
-    y = torch.empty(N, g.Ho, g.Wo, Cout, device=dev)
-    M = N * g.Ho * g.Wo
-    stats = torch.zeros((M + 127) // 128, 2, Cout, device=dev)
-    call('dsnt_conv_fwd_f16x3_ex', ptr(xd), ptr(planes), wd.numel(), ptr(wb), ptr(ab), ptr(bd), ptr(y),
-         ptr(scd) if pro else None, ptr(shd) if pro else None, 1, ptr(resd), None, ptr(stats), C.byref(g), None, None)
-    got = y.cpu().permute(0, 3, 1, 2)
-    scale = y32.abs().max().item()
-    assert (got - (y32 + res)).abs().max().item() <= 2e-5 * scale
-    err16 = (got.double() - (y64 + res.double())).abs().max().item()
-    err32 = ((y32 + res).double() - (y64 + res.double())).abs().max().item()
-    assert err16 <= max(4 * err32, 2e-6 * scale), (err16, err32)
-    yd = (y32 + res).permute(0, 2, 3, 1).reshape(M, Cout).double()
-    s = stats.cpu().double().sum(0)
-    assert (s[0] - yd.sum(0)).abs().max().item() <= 1e-4 * max(1.0, yd.sum(0).abs().max().item())
+    K.conv_f16x3_vs_fp32_accuracy(case, pro, loose)
 
 
 @pytest.mark.parametrize('case', [c for c in CASES if c[3] % 4 == 0 and c[4] % 4 == 0])
@@ -549,69 +499,7 @@ def test_wgrad_halo_f16x3(case, pro, relu):
     """The halo weight gradient (every 3x3 Bottleneck conv2, hourglass.py:22-23) vs fp64 autograd, same bars as
     test_wgrad_f16x3, and its slab plan: dsnt_conv_wgrad_f16x3_splits slabs reduced by dsnt_wgrad_reduce_all equal
     the reduction inside the call bit for bit."""
-    from dsnt import _lib
-    from dsnt._lib import ptr, call
-    N, H, W, Cin, Cout = case
-    dev = torch.device('cuda:0')
-    tag = 'h' + '_'.join(map(str, case))
-    g = _geom(N, H, W, Cin, Cout, 3, 3, 1, 1, 1)
-    assert _lib.fn('dsnt_conv_wgrad_halo_ok')(C.byref(g)) == 1
-    x = synthetic.tensor(tag + 'x', (N, Cin, H, W), seed=1)
-    sc = synthetic.tensor(tag + 's', (Cin,), seed=1, kind='uniform').abs() + 0.5
-    sh = synthetic.tensor(tag + 'h', (Cin,), seed=1, scale=0.3)
-    act = x * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1) if pro else x
-    act = (F.relu(act) if relu else act).double()
-    w = torch.zeros(Cout, Cin, 3, 3, dtype=torch.float64, requires_grad=True)
-    b = torch.zeros(Cout, dtype=torch.float64, requires_grad=True)
-    y = F.conv2d(act, w, b, padding=1)
-    gy = synthetic.tensor(tag + 'g', tuple(y.shape), seed=2) * 1e-4
-    y.backward(gy.double())
-    xd, gyd, scd, shd = _nhwc(x).to(dev), _nhwc(gy).to(dev), sc.to(dev), sh.to(dev)
-    ab, gb = torch.zeros(64, device=dev), torch.zeros(64, device=dev)
-    ab.fill_(act.abs().max().item() * 16.0)
-    call('dsnt_amax', ptr(gyd), gyd.numel(), ptr(gb))
-    nws = _lib.fn('dsnt_conv_wgrad_f16x3_ws_floats')(C.byref(g), 0)
-    splits = _lib.fn('dsnt_conv_wgrad_f16x3_splits')(C.byref(g), 0)
-    assert nws == splits * Cout * (9 * Cin + 1)
-    ws = torch.full((nws,), float('nan'), device=dev)
-    dw16, dw32 = torch.empty(Cout, 3, 3, Cin, device=dev), torch.empty(Cout, 3, 3, Cin, device=dev)
-    db16, db32 = torch.empty(Cout, device=dev), torch.empty(Cout, device=dev)
-    args = (ptr(xd), ptr(scd) if pro else None, ptr(shd) if pro else None, relu, ptr(gyd))
-    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws), ptr(dw16), ptr(db16), 0, ptr(ab), ptr(gb), C.byref(g))
-    assert bool(torch.isfinite(ws).all()), 'a slab element was never written'
-    ws32 = torch.empty(_lib.fn('dsnt_conv_wgrad_ws_floats')(C.byref(g)), device=dev)
-    call('dsnt_conv_wgrad', *args, ptr(ws32), ptr(dw32), ptr(db32), 0, C.byref(g))
-    ref = w.grad.permute(0, 2, 3, 1)
-    scale = ref.abs().max().item()
-    e16 = (dw16.cpu().double() - ref).abs().max().item()
-    e32 = (dw32.cpu().double() - ref).abs().max().item()
-    assert e16 <= 3e-5 * scale and e16 <= max(4 * e32, 2e-6 * scale), (e16, e32)
-    assert (db16.cpu().double() - b.grad).abs().max().item() <= 3e-5 * b.grad.abs().max().item()
-    # slabs only + the table-driven reduction: the same bits; accumulate adds
-    ws2 = torch.empty(nws, device=dev)
-    dw2, db2 = torch.zeros_like(dw16), torch.zeros_like(db16)
-    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws2), None, None, 0, ptr(ab), ptr(gb), C.byref(g))
-    assert torch.equal(ws, ws2)
-    # DSNT_WGRAD_SHARE_CHIP (bit 1): four-wave workgroups of 32 input channels that leave half of every CU to the
-    # other streams, over its own plan of (at most as many) slabs: every slab element written, the same gradient
-    nws_s = _lib.fn('dsnt_conv_wgrad_f16x3_ws_floats')(C.byref(g), 2)
-    splits_s = _lib.fn('dsnt_conv_wgrad_f16x3_splits')(C.byref(g), 2)
-    assert nws_s == splits_s * Cout * (9 * Cin + 1) and splits_s <= splits
-    ws3 = torch.full((nws_s,), float('nan'), device=dev)
-    dw3, db3 = torch.empty_like(dw16), torch.empty_like(db16)
-    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws3), ptr(dw3), ptr(db3), 2, ptr(ab), ptr(gb), C.byref(g))
-    assert bool(torch.isfinite(ws3).all())
-    e3 = (dw3.cpu().double() - ref).abs().max().item()
-    assert e3 <= 3e-5 * scale and e3 <= max(4 * e32, 2e-6 * scale), (e3, e32)
-    assert (db3.cpu().double() - b.grad).abs().max().item() <= 3e-5 * b.grad.abs().max().item()
-    if splits_s == splits:
-        assert torch.equal(ws, ws3)      # same slabs: the two workgroup shapes add in the same order, bit for bit
-    table = torch.tensor([[ws2.data_ptr(), dw2.data_ptr(), db2.data_ptr(), splits, Cout * 9 * Cin, Cout, 0]],
-                         dtype=torch.int64).to(dev)
-    call('dsnt_wgrad_reduce_all', ptr(table), 1, (Cout * 9 * Cin // 4 + (Cout + 3) // 4 + 63) // 64)
-    assert torch.equal(dw2, dw16) and torch.equal(db2, db16)
-    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws), ptr(dw16), ptr(db16), 1, ptr(ab), ptr(gb), C.byref(g))
-    assert (dw16.cpu().double() - 2 * ref).abs().max().item() <= 6e-5 * scale
+    K.wgrad_halo_f16x3(case, pro, relu)
 
 
 W1_CASES = [
@@ -623,7 +511,8 @@ W1_CASES = [
     (2, 128, 128, 64, 64),     # stem Bottleneck
     (2, 128, 128, 64, 128),
     (2, 128, 128, 128, 64),
-    (5, 64, 64, 128, 256),     # 20480 rows: the last slab is shorter
+    (5, 64, 64, 128, 256),     # 20480 rows: 160 slabs of 128 rows (8 stages), all equal, like every case here; the ragged plans
+                               # (a shorter last slab, 9 / 13 / 17 stages, several chunks) are tests/test_plan_edges_gpu.py's
 ]
 
 
@@ -633,61 +522,7 @@ def test_wgrad_1x1_f16x3(case, pro, relu):
     """The four-wave 1x1 weight gradient (conv1 / conv3 of every Bottleneck, hourglass.py:20-25) vs fp64 autograd, the
     bars of test_wgrad_f16x3, every slab element written, slabs-only + table-driven reduction bit-identical to the
     reduction inside the call, and the DSNT_WGRAD_SHARE_CHIP launch (same kernel) bit-identical too."""
-    from dsnt import _lib
-    from dsnt._lib import ptr, call
-    N, H, W, Cin, Cout = case
-    dev = torch.device('cuda:0')
-    tag = 'w1' + '_'.join(map(str, case))
-    g = _geom(N, H, W, Cin, Cout, 1, 1, 1, 0, 1)
-    x = synthetic.tensor(tag + 'x', (N, Cin, H, W), seed=1)
-    sc = synthetic.tensor(tag + 's', (Cin,), seed=1, kind='uniform').abs() + 0.5
-    sh = synthetic.tensor(tag + 'h', (Cin,), seed=1, scale=0.3)
-    act = x * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1) if pro else x
-    act = (F.relu(act) if relu else act).double()
-    gy = synthetic.tensor(tag + 'g', (N, Cout, H, W), seed=2) * 1e-4
-    a2 = act.permute(0, 2, 3, 1).reshape(-1, Cin)
-    g2 = gy.double().permute(0, 2, 3, 1).reshape(-1, Cout)
-    ref = (g2.t() @ a2).view(Cout, 1, 1, Cin)
-    bref = g2.sum(0)
-    xd, gyd, scd, shd = _nhwc(x).to(dev), _nhwc(gy).to(dev), sc.to(dev), sh.to(dev)
-    ab, gb = torch.zeros(64, device=dev), torch.zeros(64, device=dev)
-    ab.fill_(act.abs().max().item() * 16.0)
-    call('dsnt_amax', ptr(gyd), gyd.numel(), ptr(gb))
-    nws = _lib.fn('dsnt_conv_wgrad_f16x3_ws_floats')(C.byref(g), 0)
-    splits = _lib.fn('dsnt_conv_wgrad_f16x3_splits')(C.byref(g), 0)
-    assert nws == splits * Cout * (Cin + 1)
-    ws = torch.full((nws,), float('nan'), device=dev)
-    dw16, dw32 = torch.empty(Cout, 1, 1, Cin, device=dev), torch.empty(Cout, 1, 1, Cin, device=dev)
-    db16, db32 = torch.empty(Cout, device=dev), torch.empty(Cout, device=dev)
-    args = (ptr(xd), ptr(scd) if pro else None, ptr(shd) if pro else None, relu, ptr(gyd))
-    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws), ptr(dw16), ptr(db16), 0, ptr(ab), ptr(gb), C.byref(g))
-    assert bool(torch.isfinite(ws).all()), 'a slab element was never written'
-    ws32 = torch.empty(_lib.fn('dsnt_conv_wgrad_ws_floats')(C.byref(g)), device=dev)
-    call('dsnt_conv_wgrad', *args, ptr(ws32), ptr(dw32), ptr(db32), 0, C.byref(g))
-    scale = ref.abs().max().item()
-    e16 = (dw16.cpu().double() - ref).abs().max().item()
-    e32 = (dw32.cpu().double() - ref).abs().max().item()
-    assert e16 <= 3e-5 * scale and e16 <= max(4 * e32, 2e-6 * scale), (e16, e32)
-    assert (db16.cpu().double() - bref).abs().max().item() <= 3e-5 * bref.abs().max().item()
-    ws2 = torch.empty(nws, device=dev)
-    dw2, db2 = torch.zeros_like(dw16), torch.zeros_like(db16)
-    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws2), None, None, 0, ptr(ab), ptr(gb), C.byref(g))      # slabs only
-    assert torch.equal(ws, ws2)
-    table = torch.tensor([[ws2.data_ptr(), dw2.data_ptr(), db2.data_ptr(), splits, Cout * Cin, Cout, 0]],
-                         dtype=torch.int64).to(dev)
-    call('dsnt_wgrad_reduce_all', ptr(table), 1, (Cout * Cin // 4 + (Cout + 3) // 4 + 63) // 64)
-    assert torch.equal(dw2, dw16) and torch.equal(db2, db16)
-    # DSNT_WGRAD_SHARE_CHIP: half as many (longer) slabs on half the CUs — its own plan, the same gradient
-    nws_s = _lib.fn('dsnt_conv_wgrad_f16x3_ws_floats')(C.byref(g), 2)
-    splits_s = _lib.fn('dsnt_conv_wgrad_f16x3_splits')(C.byref(g), 2)
-    assert nws_s == splits_s * Cout * (Cin + 1) and splits_s <= splits
-    ws3 = torch.full((nws_s,), float('nan'), device=dev)
-    dw3, db3 = torch.empty_like(dw16), torch.empty_like(db16)
-    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws3), ptr(dw3), ptr(db3), 2, ptr(ab), ptr(gb), C.byref(g))
-    assert bool(torch.isfinite(ws3).all())
-    e3 = (dw3.cpu().double() - ref).abs().max().item()
-    assert e3 <= 3e-5 * scale and e3 <= max(4 * e32, 2e-6 * scale), (e3, e32)
-    assert (db3.cpu().double() - bref).abs().max().item() <= 3e-5 * bref.abs().max().item()
+    K.wgrad_1x1_f16x3(case, pro, relu)
 
 
 def test_f16x3_preparation_launches():
@@ -764,101 +599,7 @@ def test_conv3_stream_kernel(case, mode):
     outputs of the 32x32x16 form are bit-identical (same K order, same MFMA order, same epilogue arithmetic), those of the
     16x16x32 form (Cout 128, 4 x 32 patches) agree to fp32 rounding of the sum; with a residual to an ulp of the sum; per-patch statistics add up to the same column sums; the BatchNorm-backward epilogue masks identically; and
     the result holds the fp32 bar against torch fp64."""
-    from dsnt import _lib
-    from dsnt._lib import ptr, call, BnBwdEpilogue
-    N, H, W, Cin, Cout = case
-    dev = torch.device('cuda:0')
-    tag = 's3' + '_'.join(map(str, case))
-    g = _geom(N, H, W, Cin, Cout, 3, 3, 1, 1, 1)
-    assert _lib.fn('dsnt_conv_fwd_stream_ok')(C.byref(g)) == 1
-    M = N * H * W
-    x = synthetic.tensor(tag + 'x', (N, Cin, H, W), seed=1)
-    w = synthetic.tensor(tag + 'w', (Cout, Cin, 3, 3), seed=1, scale=(2.0 / (Cin * 9)) ** 0.5)
-    b = synthetic.tensor(tag + 'b', (Cout,), seed=1, scale=0.1)
-    sc = synthetic.tensor(tag + 's', (Cin,), seed=1, kind='uniform').abs() + 0.5
-    sh = synthetic.tensor(tag + 'h', (Cin,), seed=1, scale=0.3)
-    res = synthetic.tensor(tag + 'r', (N, Cout, H, W), seed=1)
-    relu = 0 if mode.endswith('_norelu') else 1
-    mode = mode.replace('_norelu', '')
-    pro = mode in ('pro', 'pro_res')
-    xd = _nhwc(x).to(dev)
-    wd = w.permute(0, 2, 3, 1).contiguous().to(dev)
-    n = wd.numel()
-    plain = torch.empty(2 * n, dtype=torch.float16, device=dev)
-    strm = torch.full((2 * n,), float('nan'), dtype=torch.float16, device=dev)
-    wb, wb2 = torch.zeros(64, device=dev), torch.zeros(64, device=dev)
-    table = torch.tensor([[wd.data_ptr(), plain.data_ptr(), wb.data_ptr(), n, n, 0, 0],
-                          [wd.data_ptr(), strm.data_ptr(), wb2.data_ptr(), n, n, Cout, Cin]], dtype=torch.int64).to(dev)
-    call('dsnt_f16_prep_weights', ptr(table), 2, 7)
-    assert torch.equal(wb, wb2)
-    want = plain.view(2, Cout, 9, Cin // 16, 16).permute(0, 3, 2, 1, 4).contiguous().view(-1)
-    assert torch.equal(want.view(torch.int16), strm.view(torch.int16))
-    bd, scd, shd, resd = b.to(dev), sc.to(dev), sh.to(dev), _nhwc(res).to(dev)
-    tiles = M // 128
-    if mode == 'bnb':
-        # the launch as a data gradient: A = a gradient tensor, epilogue = ReLU mask of bn(xin) + the two BN-backward sums
-        xin = _nhwc(synthetic.tensor(tag + 'xin', (N, Cout, H, W), seed=3)).to(dev)
-        mean = synthetic.tensor(tag + 'm', (Cout,), seed=4, scale=0.2).to(dev)
-        invstd = (synthetic.tensor(tag + 'i', (Cout,), seed=5, kind='uniform').abs() + 0.5).to(dev)
-        bsc = (synthetic.tensor(tag + 'bs', (Cout,), seed=6, kind='uniform') + 0.2).to(dev)
-        bsh = synthetic.tensor(tag + 'bh', (Cout,), seed=7, scale=0.3).to(dev)
-        bnb = BnBwdEpilogue(ptr(xin), ptr(bsc), ptr(bsh), ptr(mean), ptr(invstd), relu)
-    ab = torch.zeros(64, device=dev)
-    act = x * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1) if pro else x
-    if pro and relu:
-        act = F.relu(act)
-    ab[11] = act.abs().max().item() * 3.0
-    outs = []
-    for fn, planes in (('dsnt_conv_fwd_f16x3_ex', plain), ('dsnt_conv_fwd_f16x3_stream', strm)):
-        y = torch.full((N, H, W, Cout), float('nan'), device=dev)
-        stats = torch.full((tiles, 2, Cout), float('nan'), device=dev)
-        amax = torch.zeros(64, device=dev)
-        tail = _lib.BnTail()
-        if mode != 'bnb':
-            tail.amax = amax.data_ptr()
-        call(fn, ptr(xd), ptr(planes), n, ptr(wb), ptr(ab), None if mode == 'bnb' else ptr(bd), ptr(y),
-             ptr(scd) if pro else None, ptr(shd) if pro else None, relu,
-             ptr(resd) if mode in ('res', 'pro_res') else None, None, ptr(stats), C.byref(g),
-             C.byref(bnb) if mode == 'bnb' else None, C.byref(tail))
-        outs.append((y, stats, amax))
-    if mode == 'pro':       # DSNT_CONV_SHARE_CHIP (bit 1 of in_relu): fewer persistent workgroups, the same result bit for bit
-        y2 = torch.full((N, H, W, Cout), float('nan'), device=dev)
-        st2 = torch.full((tiles, 2, Cout), float('nan'), device=dev)
-        call('dsnt_conv_fwd_f16x3_stream', ptr(xd), ptr(strm), n, ptr(wb), ptr(ab), ptr(bd), ptr(y2), ptr(scd), ptr(shd), relu | 2,
-             None, None, ptr(st2), C.byref(g), None, None)
-        assert torch.equal(y2, outs[1][0]) and torch.equal(st2, outs[1][1])
-    torch.cuda.synchronize()
-    (y0, st0, am0), (y1, st1, am1) = outs
-    assert not bool(torch.isnan(y1).any()) and not bool(torch.isnan(st1).any())
-    scale = y0.abs().max().item()
-    # Cout 128 on 32-pixel-wide patches runs on v_mfma_f32_16x16x32_f16 (csrc/conv3s.hip MF16): an MFMA sums BOTH K-steps of a
-    # pair, so the same products are added in another association — fp32 rounding of the 1152..3456-term sums, not bit identity
-    mf16 = Cout == 128 and W % 32 == 0 and H % 4 == 0 and M // 128 > 128
-    if mode in ('plain', 'pro', 'bnb') and H % 8 == 0 and not mf16:   # (H % 8 != 0: _ex runs the implicit-GEMM kernel, K order (tap, channel))
-        assert torch.equal(y0, y1)
-    else:
-        assert (y0 - y1).abs().max().item() <= (5e-7 if H % 8 == 0 else 2e-6) * scale
-        if mode == 'bnb':        # the ReLU mask comes from the residual operand, not from the sums: the same zeros
-            assert torch.equal(y0 == 0, y1 == 0)
-    if mode == 'bnb':
-        assert float((y1 == 0).float().mean()) > (0.2 if relu else -1.0)
-    else:
-        assert am1.max().item() == y1.abs().max().item()
-    # statistics: other tiles, other order — the column sums agree to fp32 rounding of a 128-term sum
-    for k in range(2):
-        a0, a1 = st0[:, k].double().sum(0), st1[:, k].double().sum(0)
-        assert (a0 - a1).abs().max().item() <= 2e-6 * max(1.0, st0[:, k].double().abs().sum(0).max().item())
-    if mode != 'bnb':
-        y64 = F.conv2d(act.double(), w.double(), b.double(), padding=1)
-        if mode in ('res', 'pro_res'):
-            y64 = y64 + res.double()
-        y32 = F.conv2d(act, w, b, padding=1) + (res if mode in ('res', 'pro_res') else 0)
-        got = y1.cpu().permute(0, 3, 1, 2).double()
-        err16, err32 = (got - y64).abs().max().item(), (y32.double() - y64).abs().max().item()
-        assert err16 <= max(4 * err32, 2e-6 * y64.abs().max().item()), (err16, err32)
-        cols = y1.double().reshape(M, Cout)
-        assert (st1[:, 0].double().sum(0) - cols.sum(0)).abs().max().item() <= 1e-4 * max(1.0, cols.sum(0).abs().max().item())
-        assert (st1[:, 1].double().sum(0) - (cols * cols).sum(0)).abs().max().item() <= 1e-4 * (cols * cols).sum(0).max().item()
+    K.conv3_stream_kernel(case, mode)
 
 
 @pytest.mark.parametrize('case', [(20, 64, 64, 128, 128), (3, 64, 64, 64, 128)])
@@ -925,82 +666,7 @@ def test_conv3_stream_data_gradient_with_the_batchnorm_backward_folded_in(case, 
       * the launch's own output (masked dz of the BatchNorm in front, its two sums per patch, max |dz|) equals the
         two-launch path's to the same rounding carried through the convolution;
       * DSNT_CONV_SHARE_CHIP changes no bit."""
-    from dsnt import _lib
-    from dsnt._lib import ptr, call, BnBwdEpilogue, BnBwdApply
-    N, H, W, Cin, Cout = case            # of the data-gradient launch: Cin = channels of dL/dy, Cout = channels of dL/dx
-    dev = torch.device('cuda:0')
-    tag = 's4' + '_'.join(map(str, case)) + str(relu) + str(big_mean)
-    g = _geom(N, H, W, Cin, Cout, 3, 3, 1, 1, 1)
-    M = N * H * W
-    w = synthetic.tensor(tag + 'w', (Cout, Cin, 3, 3), seed=1, scale=(2.0 / (Cin * 9)) ** 0.5)
-    wd = w.permute(0, 2, 3, 1).contiguous().to(dev)
-    n = wd.numel()
-    strm = torch.empty(2 * n, dtype=torch.float16, device=dev)
-    wb = torch.zeros(64, device=dev)
-    table = torch.tensor([[wd.data_ptr(), strm.data_ptr(), wb.data_ptr(), n, n, Cout, Cin]], dtype=torch.int64).to(dev)
-    call('dsnt_f16_prep_weights', ptr(table), 1, 7)
-    # the BatchNorm behind the convolution: its input y, its vectors, the reduced coefficients; dz behind it (ReLU-masked)
-    mu = synthetic.tensor(tag + 'mu', (Cin,), seed=2, scale=20.0 if big_mean else 0.5).to(dev)
-    std = (synthetic.tensor(tag + 'sd', (Cin,), seed=3, kind='uniform').abs() + 0.5).to(dev)
-    yin = (_nhwc(synthetic.tensor(tag + 'y', (N, Cin, H, W), seed=4)).to(dev) * std + mu).contiguous()
-    dz = _nhwc(synthetic.tensor(tag + 'dz', (N, Cin, H, W), seed=5)).to(dev)
-    dz = (dz * (_nhwc(synthetic.tensor(tag + 'mk', (N, Cin, H, W), seed=6)).to(dev) > 0)).contiguous()
-    invstd = (1.0 / std).contiguous()
-    gamma = (synthetic.tensor(tag + 'ga', (Cin,), seed=7, kind='uniform') + 0.3).to(dev)
-    scale = (gamma * invstd).contiguous()
-    shift = torch.zeros(Cin, device=dev)
-    xhat = (yin.view(M, Cin) - mu) * invstd
-    coef = torch.cat([dz.view(M, Cin).mean(0), (dz.view(M, Cin) * xhat).mean(0)]).contiguous()
-    # the BatchNorm in front of the convolution (the epilogue)
-    xin = _nhwc(synthetic.tensor(tag + 'xin', (N, Cout, H, W), seed=8)).to(dev)
-    mean = synthetic.tensor(tag + 'm', (Cout,), seed=9, scale=0.2).to(dev)
-    istd = (synthetic.tensor(tag + 'i', (Cout,), seed=10, kind='uniform').abs() + 0.5).to(dev)
-    bsc = (synthetic.tensor(tag + 'bs', (Cout,), seed=11, kind='uniform') + 0.2).to(dev)
-    bsh = synthetic.tensor(tag + 'bh', (Cout,), seed=12, scale=0.3).to(dev)
-    bnb = BnBwdEpilogue(ptr(xin), ptr(bsc), ptr(bsh), ptr(mean), ptr(istd), relu)
-    tiles = M // 128
-    # reference: the apply launch, then the stream kernel on its output
-    dy = torch.full((N, H, W, Cin), float('nan'), device=dev)
-    call('dsnt_bn_act_bwd_apply', ptr(dz), ptr(yin), ptr(scale), ptr(shift), ptr(mu), ptr(invstd), ptr(coef), 0, ptr(dy), 0, M, Cin)
-    dy64 = (scale.double() * (dz.view(M, Cin).double() - coef[:Cin].double() -
-                              (yin.view(M, Cin).double() - mu.double()) * invstd.double() * coef[Cin:].double())).view(N, H, W, Cin)
-    ab = torch.zeros(64, device=dev)
-    ab[5] = float(dy64.abs().max()) * 2.5
-    outs = []
-    for fold, flags in ((False, 0), (True, 0), (True, 2)):
-        out = torch.full((N, H, W, Cout), float('nan'), device=dev)
-        stats = torch.full((tiles, 2, Cout), float('nan'), device=dev)
-        amax = torch.zeros(64, device=dev)
-        tail = _lib.BnTail()
-        tail.amax = amax.data_ptr()
-        dyo = torch.full((N, H, W, Cin), float('nan'), device=dev)
-        if fold:
-            ap = BnBwdApply(ptr(yin), ptr(scale), ptr(mu), ptr(invstd), ptr(coef))
-            call('dsnt_conv_dgrad_f16x3_stream_apply', ptr(dz), C.byref(ap), ptr(dyo), ptr(strm), n, ptr(wb), ptr(ab), ptr(out),
-                 ptr(stats), flags, C.byref(g), C.byref(bnb), C.byref(tail))
-        else:
-            call('dsnt_conv_fwd_f16x3_stream', ptr(dy), ptr(strm), n, ptr(wb), ptr(ab), None, ptr(out), None, None, 0, None, None,
-                 ptr(stats), C.byref(g), C.byref(bnb), C.byref(tail))
-        outs.append((out, stats, amax, dyo))
-    torch.cuda.synchronize()
-    (o0, s0, a0, _), (o1, s1, a1, d1), (o2, s2, a2, d2) = outs
-    assert torch.equal(o1, o2) and torch.equal(d1, d2) and torch.equal(a1.max(), a2.max())      # the share flag changes no bit
-    assert not bool(torch.isnan(d1).any()) and not bool(torch.isnan(o1).any()) and not bool(torch.isnan(s1).any())
-    # dy_out against fp64, held to the apply kernel's own distance (x 4) plus the affine form's conditioning
-    sc_dy = float(dy64.abs().max())
-    e_ref, e_new = float((dy.double() - dy64).abs().max()), float((d1.double() - dy64).abs().max())
-    cond = float((mu.abs() * invstd).max())
-    assert e_new <= max(4 * e_ref, 2e-7 * (1 + cond) * sc_dy), (e_new, e_ref, cond)
-    # the convolution's output: same mask, values to the rounding of dy carried through 9 Cin products
-    so = float(o0.abs().max())
-    tol = (4e-7 * (1 + cond)) * so
-    assert (o0 - o1).abs().max().item() <= tol, ((o0 - o1).abs().max().item(), tol)
-    if relu:
-        assert float((o1 == 0).float().mean()) > 0.2 and float(((o0 == 0) != (o1 == 0)).float().mean()) <= 1e-5
-    assert abs(a0.max().item() - a1.max().item()) <= tol
-    for k in range(2):
-        b0, b1 = s0[:, k].double().sum(0), s1[:, k].double().sum(0)
-        assert (b0 - b1).abs().max().item() <= 4e-6 * (1 + cond) * max(1.0, s0[:, k].double().abs().sum(0).max().item())
+    K.conv3_stream_dgrad_apply(case, relu, big_mean)
 
 
 def test_share_chip_flag_of_the_streaming_1x1_kernel_changes_no_bit():
@@ -1044,6 +710,10 @@ def test_conv3_stream_refusals():
     ok = _lib.fn('dsnt_conv_fwd_stream_ok')
     assert ok(C.byref(_geom(2, 16, 32, 64, 64, 3, 3, 1, 1, 1))) == 1
     assert ok(C.byref(_geom(2, 16, 16, 64, 64, 3, 3, 1, 1, 1))) == 1          # 8 x 16 patches
+    assert ok(C.byref(_geom(2, 8, 32, 96, 64, 3, 3, 1, 1, 1))) == 1 and ok(C.byref(_geom(3, 4, 32, 64, 64, 3, 3, 1, 1, 1))) == 1
+    for bad in [(2, 4, 16, 64, 64, 3, 3, 1, 1, 1), (2, 8, 32, 160, 64, 3, 3, 1, 1, 1), (2, 8, 32, 16, 64, 3, 3, 1, 1, 1),
+                (2, 2, 32, 64, 64, 3, 3, 1, 1, 1)]:        # one 8 x 16 patch row needs H % 8; Cin above 128, below 32; half a patch row
+        assert ok(C.byref(_geom(*bad))) == 0 and _lib.fn('dsnt_conv_fwd_stream_form')(C.byref(_geom(*bad)), 0) == -1, bad
     for bad in [(2, 12, 16, 64, 64, 3, 3, 1, 1, 1), (2, 6, 32, 64, 64, 3, 3, 1, 1, 1), (2, 16, 32, 48, 64, 3, 3, 1, 1, 1), (2, 16, 24, 64, 64, 3, 3, 1, 1, 1),
                 (2, 16, 32, 64, 96, 3, 3, 1, 1, 1), (2, 16, 32, 64, 64, 1, 1, 1, 0, 1), (2, 16, 32, 256, 64, 3, 3, 1, 1, 1),
                 (2, 16, 32, 64, 64, 3, 3, 1, 2, 2)]:
