@@ -90,10 +90,10 @@ __device__ __forceinline__ void split4(const float4 v, uint2& p1, uint2& p2, uin
 // fp16x3: the same idea on TWO fp16 planes after a power-of-two scale: x * s = h1 + h2 with h1 = fp16(x * s),
 // h2 = fp16(x * s - h1) keeps 22+ significand bits, the product needs h1 g1 + h1 g2 + h2 g1 = THREE MFMAs (dropped
 // term <= 2^-24 |x g|), two thirds of the LDS traffic and about half the split arithmetic of bf16x6.  Error against
-// fp64 (K = 1152, tools/split_numerics.py): 7.7e-8 of the output scale — a plain fp32 GEMM has 2.7e-7, bf16x6 5.8e-9.
+// fp64 (K = 1152): 7.7e-8 of the output scale — a plain fp32 GEMM has 2.7e-7, bf16x6 5.8e-9.
 // The price is fp16's exponent range: s = pow2_scale(bound) keeps |x * s| < 2^14 for any bound >= max|x| (a bound
 // 64x too large costs nothing measurable; overflow would be fatal, underflow only costs absolute error
-// <= 2^-40 * bound).  Bounds live in device memory: BN+ReLU operands from the BN parameters (|gamma| sqrt(M) + |beta|),
+// <= 2^-38 * bound: the low plane is a multiple of 2^-24, so 2^-25 / s — attained, tests/split_ref.py).  Bounds live in device memory: BN+ReLU operands from the BN parameters (|gamma| sqrt(M) + |beta|),
 // weights and BN-backward outputs from an amax their producer wrote.
 // the MFMAs of one 32x32 accumulator and one 16-wide K step, smallest terms first
 template <bool F16>

@@ -272,7 +272,7 @@ int dsnt_conv_fwd_bf16x6_ex(const float* x, const void* w_planes, int64_t plane_
                             void* stream);
 
 /* fp16x3 variant: x * s = h1 + h2 on TWO fp16 planes after a power-of-two scale, three MFMAs per product (error vs
- * fp64 below a plain fp32 GEMM's: conv_split.h, tools/split_numerics.py).  a_bound / w_bound are DEVICE scalars >= the
+ * fp64 below a plain fp32 GEMM's: conv_split.h; the split bit for bit: tests/split_ref.py).  a_bound / w_bound are DEVICE scalars >= the
  * largest |value| of the A operand AFTER its BN+ReLU prologue (or of x when there is none) and of the weights; the
  * kernels derive the scales from them (pow2: bound * scale in [2^13, 2^14)), so a loose bound is fine and a bound
  * that is too SMALL overflows fp16.  w_planes: two fp16 planes made by dsnt_split_f16x2 with the SAME w_bound.
