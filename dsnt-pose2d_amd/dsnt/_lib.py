@@ -179,6 +179,9 @@ SIGNATURES = {
     'dsnt_augment_fwd_pair_gather': [P, L, P, I, I, I, P, P, P, P, I, C.c_uint64, C.c_uint64, C.c_uint32, P, P, P, P],
     'dsnt_augment_keypoints_gather': [P, P, P, P, L, P, I, I, P, P, P, P, I, P, P, P, P, P, P],
     'dsnt_epoch_indices': [L, C.c_uint64, C.c_uint64, L, L, I, P, P],
+    'dsnt_sample_cdf': [P, L, P, P, P],
+    'dsnt_sample_indices': [P, L, C.c_uint64, C.c_uint64, L, L, P, P],
+    'dsnt_example_scores': [P, P, P, P, P, P, P, L, C.c_uint32, P, P, I, I, P],
     'dsnt_crop_affine': [P, L, P, P, L, P, P, I, I, P, P, P],
     'dsnt_render_pose': [P, I, P, P, I, I, I, I, P, I, I, P, L, P, F, P, P, I, P, P, I, F, F, P, P],
 }

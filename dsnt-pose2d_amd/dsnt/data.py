@@ -17,11 +17,20 @@ needs no host work (the reference's `DataLoader(train_data, batch_size, shuffle=
 `ImagePool` keeps full decoded images on the device and crops person boxes from them (`dsnt_crop_affine`, Pillow's
 affine bilinear sampler bit for bit); `box_matrix` builds the box matrices, and `DeviceDataset.from_pool` builds a
 training set from the crops.
+
+`ExampleScores` keeps, per dataset row, how badly the row was predicted the last time it was seen (one launch per batch,
+`dsnt_example_scores`), and `WeightedLoader` runs epochs that draw rows with replacement in proportion to arbitrary
+weights, those of `ExampleScores.weights_from_table` for one: an exact fixed-point CDF built on the device once per
+re-weighting (`dsnt_sample_cdf`) and one counter-based draw per batch (`dsnt_sample_indices`) in front of the same gather
+kernels (`csrc/sampler.hip`).
 """
+import math
+
 import numpy as np
 import torch
 
 from . import _lib
+from .evaluator import _batch_args
 from .inference import HFLIP_INDICES
 
 
@@ -451,7 +460,8 @@ class EpochLoader:
             raise RuntimeError('dsnt: EpochLoader needs a DeviceDataset, got %s' % type(dataset))
         if not isinstance(augment, DeviceAugment):
             raise RuntimeError('dsnt: EpochLoader needs a DeviceAugment, got %s' % type(augment))
-        B, W, r, n = int(batch_size), int(world_size), int(rank), len(dataset)
+        self.dataset = dataset
+        B, W, r, n = int(batch_size), int(world_size), int(rank), self._positions()
         if B < 1 or B > 65535:
             raise RuntimeError('dsnt: batch_size must be in [1, 65535], got %d' % B)
         if W < 1 or not 0 <= r < W:
@@ -464,15 +474,19 @@ class EpochLoader:
         if r * B >= 2 ** 32:
             raise RuntimeError('dsnt: rank * batch_size must be < 2^32 (the draw offset)')
         augment._flip_table(dataset.keypoints.shape[1], augment.use_aug, dataset.device)    # refuses J != 16 with flips
-        self.dataset, self.batch_size, self.augment = dataset, B, augment
+        self.batch_size, self.augment = B, augment
         self.seed, self.shuffle, self.drop_last = int(seed), bool(shuffle), bool(drop_last)
         self.rank, self.world_size, self.flip_pair = r, W, bool(flip_pair)
         self.epoch, self.batch = 0, 0
         self._identity = {}
 
+    def _positions(self):
+        """Positions of one epoch over all ranks (a subclass may run epochs of another length)."""
+        return len(self.dataset)
+
     def __len__(self):
         """Batches per epoch of this rank."""
-        n, B = len(self.dataset), self.batch_size
+        n, B = self._positions(), self.batch_size
         return n // (B * self.world_size) if self.drop_last else (n + B - 1) // B
 
     def set_epoch(self, epoch):
@@ -510,7 +524,7 @@ class EpochLoader:
     def _batch(self, epoch, s):
         d, B, W, r = self.dataset, self.batch_size, self.world_size, self.rank
         first = (s * W + r) * B
-        count = min(B, len(d) - first)
+        count = min(B, self._positions() - first)
         idx = self._order(epoch, first, count)
         p = self._params(count, d.device)
         sample = self.augment._launch(d.crops, d.keypoints, d.keypoint_mask, d.matrix, count, epoch * len(self) + s, p,
@@ -526,6 +540,179 @@ class EpochLoader:
             self.batch = s + 1
             yield sample
         self.epoch, self.batch = self.epoch + 1, 0
+
+
+_SAMPLE_MAX_N = 1 << 24    # DSNT_SAMPLE_MAX_N
+_SAMPLE_TILE = 1024        # DSNT_SAMPLE_TILE
+
+
+class ExampleScores:
+    """Per dataset row, how badly the row was predicted the last time it was seen.
+
+    `ExampleScores(n, device='cuda')` owns `table`, int64 `[n]` on the device: `(stamp << 32) | bits(score)` of the row's
+    latest batch, 0 for a row never seen.  The score of an example is the mean over its joints with mask 1 of the PCKh
+    distance (`PCKhEvaluator`'s, in head lengths), fp32.  `stamp` is the caller's clock, an integer in [1, 2^31) that does
+    not decrease (the epoch number plus one, or the global step): the newest stamp owns a row, and within one stamp the
+    larger score, so a row drawn twice in a batch ends the same way whatever the order of arrival.
+    """
+
+    def __init__(self, n, device='cuda'):
+        n, device = int(n), torch.device(device)
+        if n < 1:
+            raise RuntimeError('dsnt: ExampleScores needs n >= 1 rows, got %d' % n)
+        if device.type != 'cuda':
+            raise RuntimeError('dsnt: ExampleScores lives on a HIP device, not %s (no CPU fallback)' % device)
+        self.table = torch.zeros(n, dtype=torch.int64, device=device)
+
+    def __len__(self):
+        return self.table.shape[0]
+
+    def add(self, index, norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b, stamp):
+        """Score a batch given in normalised coords (back-projected in fp64 as in `PCKhEvaluator.add_normalized`) and leave
+        the scores in the rows `index` (int64 `[B]`, `EpochLoader`'s `sample['index']`; a row outside the table, such as the
+        -1 of an all-zero weighting, and an example with no valid joint or a non-finite score write nothing).  Returns the
+        scores, f32 `[B]`, NaN with no valid joint.  One launch; nothing is read back to the host."""
+        B, J = norm_pred.shape[0], norm_pred.shape[1]
+        stamp = int(stamp)
+        if not 1 <= stamp < 2 ** 31:
+            raise RuntimeError('dsnt: stamp must lie in [1, 2^31), got %d' % stamp)
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or tuple(index.shape) != (B,):
+            raise RuntimeError('dsnt: index must be an int64 [%d] tensor' % B)
+        dev = self.table.device
+        if norm_pred.device != dev or index.device != dev:
+            raise RuntimeError('dsnt: the batch must be on the table\'s device %s' % dev)
+        args = _batch_args(norm_pred, norm_target, joint_mask, head_lengths, transform_m, transform_b)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        _lib.call('dsnt_example_scores', *map(_lib.ptr, args), _lib.ptr(index.contiguous()), len(self), stamp,
+                  _lib.ptr(self.table), _lib.ptr(score), B, J)
+        return score
+
+    @staticmethod
+    def _split(table):
+        """(seen bool, score f32, stamp int64) of a table, on the table's device."""
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.dim() != 1:
+            raise RuntimeError('dsnt: a score table is an int64 [n] tensor')
+        return table != 0, (table & 0xFFFFFFFF).to(torch.int32).view(torch.float32), table >> 32
+
+    def scores(self):
+        """f32 `[n]`: the latest score of every row, NaN for a row never seen."""
+        seen, score, _ = self._split(self.table)
+        return torch.where(seen, score, torch.full_like(score, float('nan')))
+
+    def last_seen(self):
+        """int64 `[n]`: the stamp of every row's latest score, 0 for a row never seen."""
+        return self._split(self.table)[2]
+
+    def merge(self, other_table):
+        """Take the element-wise maximum with another table (an `ExampleScores` or its `table`): per row the newer stamp,
+        the larger score within one stamp.  This is how the tables of two ranks combine."""
+        other = other_table.table if isinstance(other_table, ExampleScores) else other_table
+        if not isinstance(other, torch.Tensor) or other.dtype != torch.int64 or other.shape != self.table.shape:
+            raise RuntimeError('dsnt: merge needs an int64 [%d] table' % len(self))
+        torch.maximum(self.table, other.to(self.table.device), out=self.table)
+
+    def state_dict(self):
+        return {'table': self.table.clone()}
+
+    def load_state_dict(self, state):
+        table = state['table']
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.shape != self.table.shape:
+            raise RuntimeError('dsnt: the state holds no int64 [%d] table' % len(self))
+        self.table.copy_(table)
+
+    @staticmethod
+    def weights_from_table(table, power=1.0, floor=0.1, unseen='max'):
+        """Row weights from a score table (int64 `[n]`, on any device): f32 `[n]`.  A seen row gets
+        `floor + (score / mean seen score) ** power` (the ratio reads as 1 while the mean is 0: nothing to tell rows
+        apart by), an unseen row the largest weight of a seen row (`unseen='max'`: see everything before trusting the
+        scores) or 1 (`unseen='mean'`); with no row seen every weight is 1.  Plain torch ops on the table's device, once
+        per re-weighting, without a host synchronisation."""
+        power, floor = float(power), float(floor)
+        if not (math.isfinite(power) and math.isfinite(floor) and floor >= 0):
+            raise RuntimeError('dsnt: weights_from_table needs a finite power and a finite floor >= 0, got %r and %r'
+                               % (power, floor))
+        if unseen not in ('max', 'mean'):
+            raise RuntimeError("dsnt: unseen must be 'max' or 'mean', got %r" % (unseen,))
+        seen, score, _ = ExampleScores._split(table)
+        one = torch.ones_like(score)
+        count = seen.sum()
+        mean = (torch.where(seen, score, torch.zeros_like(score)).double().sum() / count).float()
+        w = floor + torch.where(mean > 0, score / mean, one) ** power
+        rest = torch.where(seen, w, torch.full_like(w, float('-inf'))).max() if unseen == 'max' else one
+        return torch.where(count > 0, torch.where(seen, w, rest), one)
+
+
+class WeightedLoader(EpochLoader):
+    """Epochs that draw rows with replacement in proportion to row weights, with no host work per batch.
+
+    `WeightedLoader(dataset, batch_size, augment, weights, seed=0, samples_per_epoch=None, drop_last=False, rank=0,
+    world_size=1, flip_pair=False)`: an `EpochLoader` whose position p of epoch e is a weighted draw keyed by (`seed`, e,
+    p) alone (`dsnt_sample_indices`), not a permutation: a row may come twice in a batch, and a row may not come at all.
+    An epoch is `samples_per_epoch` positions (default `len(dataset)`, at most 2^32); batches, ranks, `drop_last`, the
+    augmentation's steps and draw offsets are `EpochLoader`'s, with that number in the place of the dataset's length.
+
+    `weights`: f32 `[len(dataset)]` on the dataset's device, any scale.  NaN, infinite, negative and zero weights count as
+    0, and so does a weight below about 2^-32 of the largest: such rows are never drawn (the CDF is exact fixed point at 32
+    bits below the largest weight's binade, `dsnt_sample_cdf`).  If no weight counts every index is -1 and every sample
+    NaN with mask 0.  `set_weights(w)` rebuilds the CDF in place (five small launches, nothing allocated but the call's
+    own temporaries); between epochs or mid-epoch, the next batch draws from it.  `state_dict()` carries the CDF, so a
+    resumed loader repeats the uninterrupted batches exactly.
+    """
+
+    def __init__(self, dataset, batch_size, augment, weights, seed=0, samples_per_epoch=None, drop_last=False, rank=0,
+                 world_size=1, flip_pair=False):
+        self._samples = None if samples_per_epoch is None else int(samples_per_epoch)
+        if self._samples is not None and not 1 <= self._samples <= 2 ** 32:
+            raise RuntimeError('dsnt: samples_per_epoch must lie in [1, 2^32], got %d' % self._samples)
+        super().__init__(dataset, batch_size, augment, seed=seed, shuffle=True, drop_last=drop_last, rank=rank,
+                         world_size=world_size, flip_pair=flip_pair)
+        n = len(dataset)
+        if n > _SAMPLE_MAX_N:
+            raise RuntimeError('dsnt: WeightedLoader takes at most 2^24 rows, got %d' % n)
+        self._check_weights(weights)
+        self._cdf = torch.empty(n, dtype=torch.int64, device=dataset.device)
+        self._scratch = torch.empty(1 + (n + _SAMPLE_TILE - 1) // _SAMPLE_TILE, dtype=torch.int64, device=dataset.device)
+        self.set_weights(weights)
+
+    def _check_weights(self, w):
+        n, dev = len(self.dataset), self.dataset.device
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32:
+            raise RuntimeError('dsnt: weights must be a float32 tensor, got %s'
+                               % (w.dtype if isinstance(w, torch.Tensor) else type(w),))
+        if tuple(w.shape) != (n,):
+            raise RuntimeError('dsnt: weights must have shape %s (one per dataset row), got %s' % ((n,), tuple(w.shape)))
+        if w.device != dev:
+            raise RuntimeError('dsnt: weights must be on the dataset\'s device %s, got %s' % (dev, w.device))
+
+    def _positions(self):
+        return len(self.dataset) if self._samples is None else self._samples
+
+    def set_weights(self, weights):
+        """Draw from `weights` (f32 `[len(dataset)]` on the dataset's device) from the next batch on."""
+        self._check_weights(weights)
+        _lib.call('dsnt_sample_cdf', _lib.ptr(weights.detach()), len(self.dataset), _lib.ptr(self._cdf),
+                  _lib.ptr(self._scratch))
+
+    def state_dict(self):
+        """`EpochLoader`'s state and the CDF the next batch draws from."""
+        return dict(super().state_dict(), cdf=self._cdf.clone())
+
+    def load_state_dict(self, state):
+        cdf = state['cdf']
+        if not isinstance(cdf, torch.Tensor) or cdf.dtype != torch.int64 or cdf.shape != self._cdf.shape:
+            raise RuntimeError('dsnt: the state holds no int64 [%d] CDF' % self._cdf.shape[0])
+        super().load_state_dict(state)
+        self._cdf.copy_(cdf)
+
+    def _order(self, epoch, first, count):
+        idx = torch.empty(count, dtype=torch.int64, device=self.dataset.device)
+        _lib.call('dsnt_sample_indices', _lib.ptr(self._cdf), len(self.dataset), self.seed & (2 ** 64 - 1),
+                  int(epoch) & (2 ** 64 - 1), first, count, _lib.ptr(idx))
+        return idx
+
+    def indices(self, epoch=None):
+        """The draws of `epoch` (default: the current one) over all ranks, int64 `[samples_per_epoch]` on the device."""
+        return self._order(self.epoch if epoch is None else epoch, 0, self._positions())
 
 
 _MAX_SIDE = 16384          # dsnt_crop_affine's bound on an image side

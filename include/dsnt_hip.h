@@ -993,6 +993,46 @@ int dsnt_augment_keypoints_gather(const double* matrix_pool, const double* kp_po
  * identity.  Needs 0 <= first, 0 < count <= n - first. */
 int dsnt_epoch_indices(int64_t n, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int shuffle, int64_t* out,
                        void* stream);
+/* Importance-sampled epochs (dsnt.data.ExampleScores / WeightedLoader; csrc/sampler.hip).  dsnt_version() >= 130.
+ *
+ * dsnt_sample_cdf: cdf u64 [n] = an exact fixed-point CDF of weights f32 [n], 1 <= n <= DSNT_SAMPLE_MAX_N.  A weight that
+ * is NaN, +-inf, negative or zero counts as 0 (a positive subnormal counts).  wmax = the largest counted weight = f 2^e
+ * with f in [0.5, 1) (frexp); q[i] = floor(w[i] 2^(32 - e)), an integer below 2^32 (scaling by a power of two is exact:
+ * nothing is rounded); cdf[i] = q[0] + .. + q[i], below 2^56, so exact and independent of the order of summation.  The
+ * resolution is 2^-32 of the binade of the largest weight: a weight below 2^(e - 32), i.e. less than about 2^-31 .. 2^-32
+ * of the largest, has q = 0, and SUCH A ROW IS NEVER DRAWN, like a row of weight 0.  If no weight counts, cdf is all
+ * zero.  scratch: DSNT_SAMPLE_CDF_SCRATCH_BYTES(n) bytes of device memory, 8-byte aligned, initialised by the call
+ * (contents on return unspecified).  Five stream-ordered launches: zero the maximum; an integer atomic max over the bit
+ * patterns of the counted weights (order-independent); a scan inside every tile of DSNT_SAMPLE_TILE weights; one
+ * workgroup scans the tile totals; every tile adds its offset.  No workgroup waits on another workgroup of its launch.
+ * Bit-reproducible.  DSNT_ERR_ARG: a null pointer; DSNT_ERR_SHAPE: n out of range; nothing launched. */
+#define DSNT_SAMPLE_MAX_N (1 << 24)
+#define DSNT_SAMPLE_TILE 1024
+#define DSNT_SAMPLE_CDF_SCRATCH_BYTES(n) (8 * (1 + ((int64_t)(n) + DSNT_SAMPLE_TILE - 1) / DSNT_SAMPLE_TILE))
+int dsnt_sample_cdf(const float* weights, int64_t n, uint64_t* cdf, void* scratch, void* stream);
+/* out int64 [count] = the weighted draws, with replacement, of positions first .. first + count - 1 of an epoch from the
+ * cdf u64 [n] of dsnt_sample_cdf (any non-decreasing u64 [n] serves).  Position p: (o0, o1, ., .) =
+ * Philox4x32-10 with key (seed lo, seed hi) and counter (p, epoch lo, epoch hi, DSNT_SAMPLE_DOMAIN), a domain word apart
+ * from the augmentation draw's 0, 1, 2, the epoch order's 0x4F524400 + 0..7 and DSNT_PCKH_BOOT_DOMAIN; u = o0 2^32 + o1;
+ * T = cdf[n - 1]; t = floor(u T / 2^64); out = the smallest j with cdf[j] > t, so row j is drawn with probability q[j] / T
+ * to within 2^-64.  T == 0: out = -1, which the gather kernels turn into a NaN sample with mask 0.  The draw depends on
+ * (seed, epoch, p) alone: not on count, on the sub-range or on who asks.  One launch, one thread per position, a bisection
+ * of ceil(log2 n) loads.  Needs 1 <= n <= DSNT_SAMPLE_MAX_N, 0 <= first, 0 < count, first + count <= 2^32 (DSNT_ERR_SHAPE
+ * otherwise), non-null pointers (DSNT_ERR_ARG); nothing launched on an error. */
+#define DSNT_SAMPLE_DOMAIN 0x57534D50u
+int dsnt_sample_indices(const uint64_t* cdf, int64_t n, uint64_t seed, uint64_t epoch, int64_t first, int64_t count,
+                        int64_t* out, void* stream);
+/* Per-row error table.  pred .. head: dsnt_pckh's arguments; idx int64 [B]: the dataset row of each example.  score f32
+ * [B] = the mean of dsnt_pckh's distance (same fp64 expression) over the joints of the example with mask == 1, summed in
+ * fp64 in joint order, divided by their number and rounded to fp32; NaN with no such joint.  table u64 [N] (0 = never
+ * seen): when score[b] is finite and 0 <= idx[b] < N, one 64-bit atomic max of (stamp << 32) | bits(score[b]) into
+ * table[idx[b]]; nothing is written otherwise.  Head lengths are positive, so scores are non-negative and their bit order
+ * is their order: the newest stamp wins, and within a stamp the larger score, whatever the order of arrival (a row drawn
+ * twice in a batch is deterministic).  One thread per example: it is not a hot kernel.  DSNT_ERR_ARG and nothing
+ * launched: a null pointer, B <= 0, J <= 0, N < 1, stamp outside [1, 2^31). */
+int dsnt_example_scores(const float* pred, const float* target, const double* m, const double* b, const float* mask,
+                        const double* head, const int64_t* idx, int64_t N, uint32_t stamp, unsigned long long* table,
+                        float* score, int B, int J, void* stream);
 /* Person crops of full images (dsnt.data.ImagePool.crop).  dsnt_version() >= 119.  pool: N RGB images, uint8 HWC, image i
  * at byte offset[i] (int64 [N]) with hw[i] = (h, w) (int32 [N][2]), pool_bytes the size of the buffer.  Sample b < B crops
  * image idx[b] (int64 [B]) with matrix[b] (f64 [B][3][3], image pixels -> [-1, 1]^2 crop coordinates) into out uint8

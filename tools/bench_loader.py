@@ -1,8 +1,10 @@
-"""Time the three ways of feeding a training batch on the GPU (R = 384 uint8 crops -> S = 256 inputs, drawn augmentation):
+"""Time the ways of feeding a training batch on the GPU (R = 384 uint8 crops -> S = 256 inputs, drawn augmentation):
 
     python tools/bench_loader.py [--batches 32,256] [--iters 40] [--pool 1024]
 
 - `loader`: `EpochLoader` over a resident `DeviceDataset` of `pool` crops (order + gather + augmentation, 3 launches);
+- `weighted`: `WeightedLoader` over the same set with log-uniform row weights (weighted draw + gather + augmentation, 3
+  launches); `reweight_us` is one `set_weights` (the CDF build, 5 launches) over the pool's rows and over 25,000 rows;
 - `augment`: `DeviceAugment` on one batch already gathered on the device (2 launches), the same batch every time (its
   crops stay in cache); `augment_cold`: the same on a different pre-gathered batch each time, read from HBM as the
   loader's rows are;
@@ -54,13 +56,22 @@ def main():
     ap.add_argument('--pool', type=int, default=1024)
     a = ap.parse_args()
     from dsnt import synthetic
-    from dsnt.data import DeviceAugment, DeviceDataset, EpochLoader, ImageSpecs
+    from dsnt import _lib
+    from dsnt.data import DeviceAugment, DeviceDataset, EpochLoader, ImageSpecs, WeightedLoader
     assert torch.cuda.is_available(), 'bench_loader times the GPU path: no GPU here'
     dev = torch.device('cuda:0')
     host = host_set(a.pool)
     ds = DeviceDataset.from_arrays(*host, device=dev)
     aug = DeviceAugment(ImageSpecs(S, True, False), synthetic.IMAGE_MEAN, (1, 1, 1), seed=0)
     out = {'metric': 'training batch feed R=%d -> S=%d, pool %d' % (R, S, a.pool), 'device': torch.cuda.get_device_name(0)}
+    weights = torch.exp2(torch.rand(a.pool, device=dev) * 8 - 4)
+
+    def cdf_build(n):
+        w = torch.exp2(torch.rand(n, device=dev) * 8 - 4)
+        cdf = torch.empty(n, dtype=torch.int64, device=dev)
+        scratch = torch.empty(1 + (n + 1023) // 1024, dtype=torch.int64, device=dev)
+        return lambda: _lib.call('dsnt_sample_cdf', _lib.ptr(w), n, _lib.ptr(cdf), _lib.ptr(scratch))
+    out['reweight_us'] = {str(n): round(timed(cdf_build(n), a.iters), 1) for n in (a.pool, 25000)}
     for B in [int(b) for b in a.batches.split(',')]:
         res = {}
         ld = EpochLoader(ds, B, aug, drop_last=True)
@@ -73,6 +84,17 @@ def main():
                 state['it'] = iter(ld)
                 return next(state['it'])
         res['loader'] = timed(loader, a.iters)
+
+        wl = WeightedLoader(ds, B, aug, weights, drop_last=True)
+        wstate = {'it': iter(wl)}
+
+        def weighted():
+            try:
+                return next(wstate['it'])
+            except StopIteration:
+                wstate['it'] = iter(wl)
+                return next(wstate['it'])
+        res['weighted'] = timed(weighted, a.iters)
 
         idx = torch.randperm(a.pool, device=dev)[:B]
         batch = [ds.crops[idx], ds.keypoints[idx], ds.keypoint_mask[idx], ds.matrix[idx], ds.head_lengths[idx]]
