@@ -17,7 +17,7 @@ NO_SLP = ('conv_f32.hip', 'conv_split6.hip', 'conv_wgrad.hip', 'conv_prep.hip')
 # (longest compiles first: four run at a time; the short element-wise units last)
 SOURCES = ['api.cpp', 'conv3s.hip', 'head_loss.hip', 'head_fwd.hip', 'head_ops.hip', 'gemm1.hip', 'conv_split6.hip',
            'conv_f32.hip', 'wgrad3.hip', 'bwd1.hip', 'fwd1.hip', 'conv_wgrad.hip', 'wgrad1.hip', 'augment.hip', 'conv_prep.hip', 'stem4.hip',
-           'heatmap.hip', 'dgrad_up.hip', 'render.hip', 'bn.hip', 'resample.hip', 'flat.hip', 'optim.hip', 'pckh.hip', 'modes.hip', 'sampler.hip']
+           'heatmap.hip', 'dgrad_up.hip', 'render.hip', 'bn.hip', 'resample.hip', 'flat.hip', 'optim.hip', 'pckh.hip', 'modes.hip', 'sampler.hip', 'occlude.hip']
 FLAGS = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wno-unused-value',
          '-Wno-unused-result']
 # kernel experiments: extra compiler flags and another output name (load it with DSNT_HIP_LIB=<path>), e.g.
@@ -48,7 +48,7 @@ def build(force=False, verbose=True):
             # CUs; the same source built without the vectoriser was bit-reproducible in 80 of 80 passes
             # (tools/determinism_fwd.py, DESIGN.md "round 2").
             extra = ['-fno-slp-vectorize'] if (src in NO_SLP or not os.environ.get('DSNT_SLP')) else []   # DSNT_SLP=1: A/B only
-            if src in ('heatmap.hip', 'augment.hip', 'render.hip', 'modes.hip', 'sampler.hip'):   # separately rounded steps (the reference's fp32 coordinates; Pillow's and ATen's sampling and pooling; unconvert's bytes; the window sums of dsnt_map_modes; the fp64 mean of dsnt_example_scores): no FMA contraction
+            if src in ('heatmap.hip', 'augment.hip', 'render.hip', 'modes.hip', 'sampler.hip', 'occlude.hip'):   # separately rounded steps (the reference's fp32 coordinates; Pillow's and ATen's sampling and pooling; unconvert's bytes; the window sums of dsnt_map_modes; the fp64 mean of dsnt_example_scores; the noise fill's (u - mean) / std of dsnt_occlude): no FMA contraction
                 extra = extra + ['-ffp-contract=off']
             cmd = [hipcc] + FLAGS + extra + (['-x', 'hip'] if src.endswith('.cpp') else []) + ['-c', s, '-o', o]
             jobs.append(cmd)

@@ -182,6 +182,7 @@ SIGNATURES = {
     'dsnt_sample_cdf': [P, L, P, P, P],
     'dsnt_sample_indices': [P, L, C.c_uint64, C.c_uint64, L, L, P, P],
     'dsnt_example_scores': [P, P, P, P, P, P, P, L, C.c_uint32, P, P, I, I, P],
+    'dsnt_occlude': [P, P, I, I, I, I, I, C.c_uint32, I, I, P, P, P, P, P, I, P, P, P, I, C.c_uint64, C.c_uint64, C.c_uint32, P],
     'dsnt_crop_affine': [P, L, P, P, L, P, P, I, I, P, P, P],
     'dsnt_render_pose': [P, I, P, P, I, I, I, I, P, I, I, P, L, P, F, P, P, I, P, P, I, F, F, P, P],
 }

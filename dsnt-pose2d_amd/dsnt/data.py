@@ -23,6 +23,11 @@ training set from the crops.
 weights, those of `ExampleScores.weights_from_table` for one: an exact fixed-point CDF built on the device once per
 re-weighting (`dsnt_sample_cdf`) and one counter-based draw per batch (`dsnt_sample_indices`) in front of the same gather
 kernels (`csrc/sampler.hip`).
+
+`Occlude` hides parts of a finished batch: per sample up to `max_rects` rectangles, placed uniformly or on a visible
+joint, filled with a constant, with noise or with the same pixels of another sample of the batch, in one launch keyed by
+(seed, step, sample) like the augmentation (`dsnt_occlude`, `csrc/occlude.hip`).  Both loaders take
+one as `occlude=`.
 """
 import math
 
@@ -238,6 +243,143 @@ class DeviceAugment:
         return sample
 
 
+_OCC_FILLS = {'value': 0, 'noise': 1, 'paste': 2}       # DSNT_OCCLUDE_FILL_*
+_OCC_CENTRES = {'uniform': 0, 'joint': 1}                # DSNT_OCCLUDE_CENTRE_*
+_OCC_MAX_RECTS = 8                                       # DSNT_OCCLUDE_MAX_RECTS
+_OCC_MAX_JOINTS = 256                                    # DSNT_OCCLUDE_MAX_JOINTS
+
+
+def _triple(name, v):
+    v = [float(x) for x in v]
+    if len(v) != 3:
+        raise RuntimeError('dsnt: %s needs one value per channel, got %d' % (name, len(v)))
+    return v
+
+
+class Occlude:
+    """Synthetic occlusion of a batch that `DeviceAugment` or a loader made: rectangles of the input are replaced.
+
+    `Occlude(p=0.5, max_rects=2, side=(0.1, 0.4), fill='value', centre='uniform', fill_value=(0, 0, 0), mean=(0, 0, 0),
+    std=(1, 1, 1), mask_covered=False, seed=0)`; `Occlude.like(augment, **kw)` takes the resolved `mean` / `std` and the
+    seed of a `DeviceAugment`.  A sample is occluded with probability `p` and then gets 1..`max_rects` (at most 8)
+    rectangles whose sides are drawn independently from `side`, a range of fractions of the input's side S turned into
+    pixels as `max(1, round(f * S))`; a rectangle is centred on a uniformly drawn pixel (`centre='uniform'`) or on the
+    pixel of a joint with a non-zero `part_mask` that lies in the image (`'joint'`; with no such joint, uniformly) and
+    clipped to the image.  `fill`: `'value'`, channel c becomes `fill_value[c]` (a value of the normalised input: 0 is the
+    dataset mean where the specs subtract it); `'noise'`, uniform noise in (0, 1] normalised with `mean` / `std` as the
+    augmentation normalises pixels; `'paste'`, the same pixels of another sample of the batch (the identity in a batch
+    of one).
+
+        out = occ(sample, step, draw_offset=0, rects=None, donor=None)
+
+    returns a shallow copy of the sample dict in which `input` is a new, occluded tensor, `occluded` uint8 `[B, J]` says
+    which joints' pixels were covered (whatever their mask; a joint outside the image is never covered), and `params`
+    (a copy) gains `occ_rects` int32 `[B, max_rects, 4]`, rows `(x0, y0, x1, y1)` half-open and zero where unused, and
+    `occ_donor` int32 `[B]`.  Covered joints stay supervised unless `mask_covered=True`, which replaces `part_mask` by
+    `part_mask * (1 - occluded)`.  The sample passed in and its tensors are not modified.  The draw is counter-based,
+    keyed by (`seed`, `step`, `draw_offset` + sample) with no state between calls, in Philox domains of its own: the same
+    key gives the same bits, and a loader's rank r passes r * B as it does to the augmentation.  Given `rects` (int32
+    `[B, max_rects, 4]` on the device) nothing is drawn; `donor` (int32 `[B]`) then defaults to the next sample,
+    `(b + 1) % B`.  Their values are not checked on the host (that would synchronise): the kernel clamps every coordinate
+    into `[0, S]` and every donor into `[0, B)`, and a rectangle with `x1 <= x0` or `y1 <= y0` is empty.  A sample with
+    `input_pair` is refused: flip evaluation is not training.  One launch on the current stream; nothing synchronises.
+    """
+
+    def __init__(self, p=0.5, max_rects=2, side=(0.1, 0.4), fill='value', centre='uniform', fill_value=(0, 0, 0),
+                 mean=(0, 0, 0), std=(1, 1, 1), mask_covered=False, seed=0):
+        p, K = float(p), int(max_rects)
+        if not 0.0 <= p <= 1.0:
+            raise RuntimeError('dsnt: Occlude needs 0 <= p <= 1, got %r' % (p,))
+        if not 1 <= K <= _OCC_MAX_RECTS:
+            raise RuntimeError('dsnt: max_rects must lie in [1, %d], got %d' % (_OCC_MAX_RECTS, K))
+        lo, hi = (float(v) for v in side)
+        if not 0.0 < lo <= hi <= 1.0:
+            raise RuntimeError('dsnt: side must be fractions 0 < min <= max <= 1 of the input, got %r' % (tuple(side),))
+        if fill not in _OCC_FILLS:
+            raise RuntimeError("dsnt: fill must be 'value', 'noise' or 'paste', got %r" % (fill,))
+        if centre not in _OCC_CENTRES:
+            raise RuntimeError("dsnt: centre must be 'uniform' or 'joint', got %r" % (centre,))
+        self.p, self.max_rects, self.side, self.fill, self.centre = p, K, (lo, hi), fill, centre
+        self.fill_value, self.mean, self.std = _triple('fill_value', fill_value), _triple('mean', mean), _triple('std', std)
+        self.mask_covered, self.seed = bool(mask_covered), int(seed)
+        self._dev = {}        # device -> (fill_value, mean, std) on that device
+
+    @classmethod
+    def like(cls, augment, **kw):
+        """An `Occlude` with the resolved `mean` / `std` and the seed of `augment`, a `DeviceAugment`."""
+        if not isinstance(augment, DeviceAugment):
+            raise RuntimeError('dsnt: Occlude.like needs a DeviceAugment, got %s' % type(augment))
+        return cls(**dict(dict(mean=augment.mean, std=augment.std, seed=augment.seed), **kw))
+
+    def sides(self, S):
+        """`side` in pixels of an S x S input: `(side_min, side_max)`."""
+        lo, hi = (min(int(S), max(1, int(round(f * S)))) for f in self.side)
+        return lo, hi
+
+    def _consts(self, device):
+        c = self._dev.get(device)
+        if c is None:
+            c = self._dev[device] = tuple(torch.tensor(v, dtype=torch.float32, device=device)
+                                          for v in (self.fill_value, self.mean, self.std))
+        return c
+
+    def __call__(self, sample, step, draw_offset=0, rects=None, donor=None):
+        if not isinstance(sample, dict) or 'input' not in sample:
+            raise RuntimeError('dsnt: Occlude takes the sample dict of DeviceAugment or a loader')
+        if 'input_pair' in sample:
+            raise RuntimeError('dsnt: Occlude refuses a flip_pair sample (input_pair): flip evaluation is not training')
+        draw_offset = int(draw_offset)
+        if not 0 <= draw_offset < 2 ** 32:
+            raise RuntimeError('dsnt: draw_offset must lie in [0, 2^32), got %d' % draw_offset)
+        x = sample['input']
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise RuntimeError('dsnt: input must be [B, 3, S, S], got %s'
+                               % (tuple(x.shape) if isinstance(x, torch.Tensor) else type(x),))
+        B, S, K = x.shape[0], x.shape[2], self.max_rects
+        if not (1 <= B <= 65535 and 1 <= S <= 4096):
+            raise RuntimeError('dsnt: Occlude takes 1 <= B <= 65535 and 1 <= S <= 4096, got B=%d S=%d' % (B, S))
+        _check('input', x, torch.float32, (B, 3, S, S))
+        dev = x.device
+        pc, pm = sample.get('part_coords'), sample.get('part_mask')
+        J = pc.shape[1] if isinstance(pc, torch.Tensor) and pc.dim() == 3 else 0
+        if J > _OCC_MAX_JOINTS:
+            raise RuntimeError('dsnt: Occlude takes at most %d joints, got %d' % (_OCC_MAX_JOINTS, J))
+        if pc is not None:
+            _check('part_coords', pc, torch.float32, (B, J, 2))
+            _check('part_mask', pm, torch.float32, (B, J))
+            if pc.device != dev or pm.device != dev:
+                raise RuntimeError('dsnt: Occlude inputs must be on one device')
+        if rects is None:
+            if donor is not None:
+                raise RuntimeError('dsnt: a given donor needs given rects')
+            draw = 1
+            rects = torch.empty(B, K, 4, dtype=torch.int32, device=dev)
+            donor = torch.empty(B, dtype=torch.int32, device=dev)
+        else:
+            draw = 0
+            rects = _check('rects', rects, torch.int32, (B, K, 4))
+            donor = (torch.arange(1, B + 1, dtype=torch.int32, device=dev) % B if donor is None
+                     else _check('donor', donor, torch.int32, (B,)))
+            if rects.device != dev or donor.device != dev:
+                raise RuntimeError('dsnt: Occlude inputs must be on one device')
+        lo, hi = self.sides(S)
+        fv, mean, std = self._consts(dev)
+        out = torch.empty_like(x)
+        occluded = torch.empty(B, J, dtype=torch.uint8, device=dev)
+        _lib.call('dsnt_occlude', _lib.ptr(x), _lib.ptr(out), B, S, K, lo, hi, int(round(self.p * 2 ** 24)),
+                  _OCC_FILLS[self.fill], _OCC_CENTRES[self.centre], _lib.ptr(fv), _lib.ptr(mean), _lib.ptr(std),
+                  _lib.ptr(pc) if J else None, _lib.ptr(pm) if J else None, J, _lib.ptr(rects), _lib.ptr(donor),
+                  _lib.ptr(occluded) if J else None, draw, self.seed & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                  draw_offset)
+        res = dict(sample)
+        res['input'] = out
+        res['occluded'] = occluded
+        if self.mask_covered and pm is not None:
+            res['part_mask'] = pm * (1 - occluded.to(torch.float32))
+        res['params'] = dict(sample.get('params') or {}, occ_rects=rects, occ_donor=donor)
+        return res
+
+
 _FIELDS = ('crops', 'keypoints', 'keypoint_mask', 'matrix', 'head_lengths')
 _DTYPES = (torch.uint8, torch.float64, torch.float32, torch.float64, torch.float64)
 _STAGE_BYTES = 64 << 20
@@ -439,7 +581,7 @@ class EpochLoader:
     """Epochs of `DeviceAugment` samples gathered from a `DeviceDataset`, with no host work per batch.
 
     `EpochLoader(dataset, batch_size, augment, seed=0, shuffle=True, drop_last=False, rank=0, world_size=1,
-    flip_pair=False)`.  Iterating yields the rest of the current epoch (then moves to the next), as the reference's
+    flip_pair=False, occlude=None)`.  Iterating yields the rest of the current epoch (then moves to the next), as the reference's
     `DataLoader(..., shuffle=True)` does.  Each sample is `DeviceAugment`'s dict (same keys and dtypes; `input_pair`
     with `flip_pair`) plus `index`, int64 `[B]`, the dataset rows used.  A batch is three launches on the current
     stream: the indices (`dsnt_epoch_indices`), the image and the keypoints (the `_gather` kernels, which read the
@@ -451,15 +593,21 @@ class EpochLoader:
     partial batch.  With `world_size` W > 1 (`drop_last` required), rank r takes positions
     `[(s*W + r)*B, (s*W + r + 1)*B)` of the epoch's order at its batch s and draws with sample offset r*B: the ranks
     shard one epoch without communicating.  With `use_aug=False` the identity parameters are shared read-only
-    tensors.
+    tensors.  `occlude`: an `Occlude` applied to every batch (one more launch) with the batch's own step and the rank's
+    draw offset, so resuming and rank sharding reproduce the occlusions as they reproduce the augmentation; not with
+    `flip_pair`.  `None`: the batches are exactly those of a loader without the argument.
     """
 
     def __init__(self, dataset, batch_size, augment, seed=0, shuffle=True, drop_last=False, rank=0, world_size=1,
-                 flip_pair=False):
+                 flip_pair=False, occlude=None):
         if not isinstance(dataset, DeviceDataset):
             raise RuntimeError('dsnt: EpochLoader needs a DeviceDataset, got %s' % type(dataset))
         if not isinstance(augment, DeviceAugment):
             raise RuntimeError('dsnt: EpochLoader needs a DeviceAugment, got %s' % type(augment))
+        if occlude is not None and not isinstance(occlude, Occlude):
+            raise RuntimeError('dsnt: occlude must be an Occlude or None, got %s' % type(occlude))
+        if occlude is not None and flip_pair:
+            raise RuntimeError('dsnt: occlude does not go with flip_pair (flip evaluation is not training)')
         self.dataset = dataset
         B, W, r, n = int(batch_size), int(world_size), int(rank), self._positions()
         if B < 1 or B > 65535:
@@ -477,6 +625,7 @@ class EpochLoader:
         self.batch_size, self.augment = B, augment
         self.seed, self.shuffle, self.drop_last = int(seed), bool(shuffle), bool(drop_last)
         self.rank, self.world_size, self.flip_pair = r, W, bool(flip_pair)
+        self.occlude = occlude
         self.epoch, self.batch = 0, 0
         self._identity = {}
 
@@ -531,6 +680,8 @@ class EpochLoader:
                                       self.flip_pair, False, gather=(idx, d.head_lengths, r * B))
         sample['hflip'] = p[3].view(torch.bool)
         sample['index'] = idx
+        if self.occlude is not None:
+            sample = self.occlude(sample, epoch * len(self) + s, draw_offset=r * B)
         return sample
 
     def __iter__(self):
@@ -646,7 +797,7 @@ class WeightedLoader(EpochLoader):
     """Epochs that draw rows with replacement in proportion to row weights, with no host work per batch.
 
     `WeightedLoader(dataset, batch_size, augment, weights, seed=0, samples_per_epoch=None, drop_last=False, rank=0,
-    world_size=1, flip_pair=False)`: an `EpochLoader` whose position p of epoch e is a weighted draw keyed by (`seed`, e,
+    world_size=1, flip_pair=False, occlude=None)`: an `EpochLoader` whose position p of epoch e is a weighted draw keyed by (`seed`, e,
     p) alone (`dsnt_sample_indices`), not a permutation: a row may come twice in a batch, and a row may not come at all.
     An epoch is `samples_per_epoch` positions (default `len(dataset)`, at most 2^32); batches, ranks, `drop_last`, the
     augmentation's steps and draw offsets are `EpochLoader`'s, with that number in the place of the dataset's length.
@@ -660,12 +811,12 @@ class WeightedLoader(EpochLoader):
     """
 
     def __init__(self, dataset, batch_size, augment, weights, seed=0, samples_per_epoch=None, drop_last=False, rank=0,
-                 world_size=1, flip_pair=False):
+                 world_size=1, flip_pair=False, occlude=None):
         self._samples = None if samples_per_epoch is None else int(samples_per_epoch)
         if self._samples is not None and not 1 <= self._samples <= 2 ** 32:
             raise RuntimeError('dsnt: samples_per_epoch must lie in [1, 2^32], got %d' % self._samples)
         super().__init__(dataset, batch_size, augment, seed=seed, shuffle=True, drop_last=drop_last, rank=rank,
-                         world_size=world_size, flip_pair=flip_pair)
+                         world_size=world_size, flip_pair=flip_pair, occlude=occlude)
         n = len(dataset)
         if n > _SAMPLE_MAX_N:
             raise RuntimeError('dsnt: WeightedLoader takes at most 2^24 rows, got %d' % n)

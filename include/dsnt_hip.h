@@ -1033,6 +1033,47 @@ int dsnt_sample_indices(const uint64_t* cdf, int64_t n, uint64_t seed, uint64_t 
 int dsnt_example_scores(const float* pred, const float* target, const double* m, const double* b, const float* mask,
                         const double* head, const int64_t* idx, int64_t N, uint32_t stamp, unsigned long long* table,
                         float* score, int B, int J, void* stream);
+/* Synthetic occlusion of a batch of model inputs (dsnt.data.Occlude; csrc/occlude.hip).  dsnt_version() >= 131.
+ * in f32 [B][3][S][S] -> out f32 [B][3][S][S]: out = in outside the sample's rectangles (bits copied: NaN, infinities
+ * and -0 pass through), the fill inside them.  One launch.  Out of place: the paste fill reads another sample of `in`,
+ * which in place might already hold that sample's own occlusion; in == out or overlapping ranges: DSNT_ERR_ARG.
+ * Small outputs: rects int32 [B][K][4] = (x0, y0, x1, y1), half-open, unused rows all zero; donor int32 [B]; occluded
+ * uint8 [B][J] (J > 0) = 1 iff joint j's pixel lies in some rectangle of sample b, whatever its mask.  coords f32
+ * [B][J][2] normalised; a joint's pixel is (int)floorf((c + 1.f) * (0.5f * S)) per coordinate in fp32; NaN or outside
+ * [0, S): the joint has no pixel, centres nothing and is never covered.  mask f32 [B][J] is read by joint centring only.
+ * draw != 0, integers only: u24(x) = x >> 8; pick(x, n) = (u24(x) * n) >> 24 in 64 bits; P(k) = the four words of
+ * Philox4x32-10 with key (seed lo, seed hi) and counter (g, step lo, step hi, DSNT_OCCLUDE_DOMAIN + k), g = draw_offset
+ * + b; the domain words DSNT_OCCLUDE_DOMAIN + 0..10 lie apart from the augmentation draw's 0, 1, 2, the epoch order's
+ * 0x4F524400 + 0..7, DSNT_PCKH_BOOT_DOMAIN and DSNT_SAMPLE_DOMAIN.  A = P(0): occluded iff u24(A0) < p24 (the host passes
+ * p24 = round(p 2^24) <= 2^24); count = 1 + pick(A1, K) if so, else 0; donor = (b + 1 + pick(A2, B - 1)) % B for B > 1,
+ * else b.  Rectangle r < count, Rr = P(1 + r): w = side_min + pick(Rr0, side_max - side_min + 1), h likewise from Rr1;
+ * centre DSNT_OCCLUDE_CENTRE_UNIFORM: cx = pick(Rr2, S), cy = pick(Rr3, S); DSNT_OCCLUDE_CENTRE_JOINT: with nv = the
+ * number of joints with mask != 0 that have a pixel, nv > 0: the pixel of the pick(Rr2, nv)-th such joint in index
+ * order, nv == 0: the uniform rule; x0 = max(cx - w/2, 0), x1 = min(cx - w/2 + w, S) (integer division), y alike.
+ * draw == 0: rects and donor are inputs; the kernel clamps every coordinate into [0, S] and the donor into [0, B) (the
+ * clamp is the contract: nothing a device tensor holds addresses outside the batch); x1 <= x0 or y1 <= y0 is empty.
+ * Fills (overlapping rectangles agree by construction): DSNT_OCCLUDE_FILL_VALUE, channel c = fill_value[c];
+ * DSNT_OCCLUDE_FILL_NOISE, Nw = P(9), ns = Nw0 | Nw1 << 32, pixel q = y S + x takes the words of Philox4x32-10 with key
+ * ns and counter (q, step lo, step hi, DSNT_OCCLUDE_DOMAIN + 10), u = (float)(u24(word c) + 1) * 2^-24 (exact), value =
+ * (u - mean[c]) / stdv[c], each step rounded to fp32; DSNT_OCCLUDE_FILL_PASTE, the pixel of sample donor at the same
+ * position of `in` (B == 1: the identity).  fill_value, mean, stdv: device f32 [3], all three always given.
+ * Refused, nothing launched: a null in, out, fill_value, mean, stdv, rects or donor (DSNT_ERR_ARG); B outside 1..65535,
+ * S outside 1..4096, K outside 1..DSNT_OCCLUDE_MAX_RECTS, J outside 0..DSNT_OCCLUDE_MAX_JOINTS, not 1 <= side_min <=
+ * side_max <= S (DSNT_ERR_SHAPE); an unknown fill or centre, p24 > 2^24, J > 0 without coords or occluded, joint centring
+ * of J > 0 joints without mask, in and out overlapping (DSNT_ERR_ARG).  S % 4 == 0 with 16-byte aligned tensors moves 16
+ * bytes per access, anything else single floats.  Bit-reproducible (no atomics). */
+#define DSNT_OCCLUDE_DOMAIN 0x4F43434Cu
+#define DSNT_OCCLUDE_MAX_RECTS 8
+#define DSNT_OCCLUDE_MAX_JOINTS 256
+#define DSNT_OCCLUDE_FILL_VALUE 0
+#define DSNT_OCCLUDE_FILL_NOISE 1
+#define DSNT_OCCLUDE_FILL_PASTE 2
+#define DSNT_OCCLUDE_CENTRE_UNIFORM 0
+#define DSNT_OCCLUDE_CENTRE_JOINT 1
+int dsnt_occlude(const float* in, float* out, int B, int S, int K, int side_min, int side_max, uint32_t p24, int fill,
+                 int centre, const float* fill_value, const float* mean, const float* stdv, const float* coords,
+                 const float* mask, int J, int32_t* rects, int32_t* donor, uint8_t* occluded, int draw, uint64_t seed,
+                 uint64_t step, uint32_t draw_offset, void* stream);
 /* Person crops of full images (dsnt.data.ImagePool.crop).  dsnt_version() >= 119.  pool: N RGB images, uint8 HWC, image i
  * at byte offset[i] (int64 [N]) with hw[i] = (h, w) (int32 [N][2]), pool_bytes the size of the buffer.  Sample b < B crops
  * image idx[b] (int64 [B]) with matrix[b] (f64 [B][3][3], image pixels -> [-1, 1]^2 crop coordinates) into out uint8
