@@ -6,7 +6,6 @@
 #include <string.h>
 #include "bn_pro.h"
 #include "ew_bodies.h"
-#include "stage.h"
 
 // ---------------------------------------------------------------- per-channel tile reductions
 // MODE 0: (sum x, sum x^2)          MODE 1: (sum dz, sum dz*xhat) for y = relu?(bn(x))
@@ -112,7 +111,7 @@ extern "C" int dsnt_bn_act_fwd_stats(const float* x, const float* scale, const f
     // rows are flat here: N = 1, Ho = 1, Wo = M would overflow int for nothing — the kernel only needs M = N*Ho*Wo
     DSNT_REQUIRE(M < (1ll << 31), DSNT_ERR_SHAPE, "dsnt_bn_act_fwd_stats: M too large");
     const TileOpP q{x, nullptr, y, nullptr, partial, 1, 1, (int)M, C, tile_cgs(tiles, C / 4), tail, scale, shift, relu};
-    DSNT_LAUNCH_OP(DSNT_ST_NONE, tile_op_stats_kernel<2>, dim3((unsigned)tiles, tile_grid_y(tiles, C / 4)), dim3(256), 0, stream, q);
+    DSNT_LAUNCH(tile_op_stats_kernel<2>, dim3((unsigned)tiles, tile_grid_y(tiles, C / 4)), dim3(256), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_bn_act_fwd_stats");
 }
 
@@ -144,6 +143,117 @@ extern "C" int dsnt_bn_add_act_bwd_reduce(const float* da, const float* y, const
     DSNT_CHECK_LAUNCH("dsnt_bn_add_act_bwd_reduce");
 }
 
+// Combine tile partials: 16 channels x 64 tile-lanes per 1024-thread block (the kernel is pure
+// latency: many independent loads in flight matter, not bandwidth), fp64 accumulation.
+// MODE 0: forward statistics.  MODE 1: backward sums.
+#define FIN_T 1024
+#define FIN_P (FIN_T / 16)
+// MODE 1, optional: the bound of dx = scale (dz - coef0 - xhat coef1) for a consumer that forms dx in registers
+// (dsnt_conv1x1_bwd_f16x3): max_c |scale_c| (max|dz| + |coef0_c| + |coef1_c| sqrt(M)), |xhat| <= sqrt(M) for the batch
+// statistics of M samples; raised into the 64 slots of `out` like every other bound
+struct BnBoundP { const float* scale; const float* dz_amax; float sqrtM; unsigned* out; };
+struct BnFinP {
+    const float* partial; int ntiles; double invM, unbias; int C;
+    const float* gamma; const float* beta; float* running_mean; float* running_var;
+    float momentum, eps; int training; float* o0; float* o1; float* o2; float* o3; int accumulate; BnBoundP bp;
+};
+// One workgroup per 16 channels.
+template <int MODE>
+__global__ __launch_bounds__(FIN_T) void bn_finalize_kernel(BnFinP q) {
+    __shared__ double r0[256], r1[256];
+    const float* __restrict__ partial = q.partial; const int ntiles = q.ntiles; const double invM = q.invM, unbias = q.unbias;
+    const int C = q.C; const float* __restrict__ gamma = q.gamma; const float* __restrict__ beta = q.beta;
+    float* running_mean = q.running_mean; float* running_var = q.running_var; const float momentum = q.momentum, eps = q.eps;
+    const int training = q.training; float* o0 = q.o0; float* o1 = q.o1; float* o2 = q.o2; float* o3 = q.o3;
+    const int accumulate = q.accumulate; const BnBoundP bp = q.bp;
+    const int tid = threadIdx.x, cl = tid & 15;
+    const int wg = blockIdx.x;
+    const int c = wg * 16 + cl;
+    // everything the last step needs besides the sums is fetched NOW, under the row loop: the kernel's length is what a BatchNorm
+    // costs the dependency chain, and a load issued behind the reduction is a microsecond of it (round 5, box N)
+    const bool lead = tid < 16 && c < C;
+    float pg = 1.f, pb = 0.f, prm = 0.f, prv = 0.f, po0 = 0.f, po1 = 0.f, psc = 0.f, pdz = 0.f;
+    if (MODE == 0 && lead) {
+        if (gamma) pg = gamma[c];
+        if (beta) pb = beta[c];
+        if (running_mean) { prm = running_mean[c]; prv = running_var[c]; }
+    }
+    if (MODE == 1) {
+        if (lead && accumulate) { if (o0) po0 = o0[c]; if (o1) po1 = o1[c]; }
+        if (bp.out) { pdz = bp.dz_amax[tid & 63]; if (lead) psc = bp.scale[c]; }
+    }
+    // (VP = 1: the sums as one-element arrays under one-trip loops.  As plain scalars the same row loop compiles to 6 / 16 more
+    // instructions and two more SGPRs (MODE 0 / 1); this form is instruction for instruction no larger than before)
+    constexpr int VP = 1;
+    double a0[VP], a1[VP];
+#pragma unroll
+    for (int v = 0; v < VP; ++v) {
+        a0[v] = 0.0; a1[v] = 0.0;
+        const int part = (tid + v * FIN_T) >> 4;
+        if (c < C && (MODE == 1 || training)) {
+#pragma unroll 4
+            for (int t = part; t < ntiles; t += FIN_P) {
+                a0[v] += (double)partial[((size_t)t * 2 + 0) * C + c];
+                a1[v] += (double)partial[((size_t)t * 2 + 1) * C + c];
+            }
+        }
+    }
+    // the four tile-lanes of a wave by shuffles, the waves through LDS, summed by the block's first 16 threads in a fixed order
+    // (deterministic; ONE barrier — a seven-level tree over 1024 threads cost the chain ~0.5 us per BatchNorm, round 5)
+#pragma unroll
+    for (int v = 0; v < VP; ++v) {
+        a0[v] += __shfl_xor(a0[v], 16, 64); a1[v] += __shfl_xor(a1[v], 16, 64);
+        a0[v] += __shfl_xor(a0[v], 32, 64); a1[v] += __shfl_xor(a1[v], 32, 64);
+        if ((tid & 63) < 16) { r0[((tid + v * FIN_T) >> 6) * 16 + cl] = a0[v]; r1[((tid + v * FIN_T) >> 6) * 16 + cl] = a1[v]; }
+    }
+    __syncthreads();
+    double s0 = 0.0, s1 = 0.0;
+    if (tid < 16) {
+#pragma unroll
+        for (int w = 0; w < FIN_T / 64; ++w) { s0 += r0[w * 16 + cl]; s1 += r1[w * 16 + cl]; }
+    }
+    if (tid < 16 && c < C) {
+        if (MODE == 0) {
+            double mean, var;
+            if (training) {
+                mean = s0 * invM;
+                var = s1 * invM - mean * mean;
+                if (var < 0.0) var = 0.0;
+                if (running_mean) {
+                    running_mean[c] = (float)((1.0 - momentum) * prm + momentum * mean);
+                    running_var[c] = (float)((1.0 - momentum) * prv + momentum * var * unbias);
+                }
+            } else {
+                mean = prm;
+                var = prv;
+            }
+            const float is = (float)(1.0 / sqrt(var + (double)eps));
+            const float mu = (float)mean;
+            const float sc = gamma ? pg * is : is;
+            o0[c] = mu; o1[c] = is; o2[c] = sc;
+            o3[c] = (beta ? pb : 0.f) - mu * sc;
+        } else {
+            // o0 = dgamma, o1 = dbeta, o2 = coef [2][C]
+            const float sdz = (float)s0, sdzx = (float)s1;
+            if (o0) o0[c] = accumulate ? po0 + sdzx : sdzx;
+            if (o1) o1[c] = accumulate ? po1 + sdz : sdz;
+            o2[c] = (float)(s0 * invM);
+            o2[C + c] = (float)(s1 * invM);
+        }
+    }
+    if (MODE == 1 && bp.out) {
+        float dzmax = pdz;                                       // (every thread: the shuffles need whole waves)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) dzmax = fmaxf(dzmax, __shfl_xor(dzmax, o, 64));
+        float b = 0.f;
+        if (tid < 16 && c < C)
+            b = fabsf(psc) * (dzmax + fabsf((float)(s0 * invM)) + fabsf((float)(s1 * invM)) * bp.sqrtM);
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) b = fmaxf(b, __shfl_xor(b, o, 64));
+        if (tid == 0 && b > 0.f) atomicMax(bp.out + (wg & 63), __float_as_uint(b));
+    }
+}
+
 extern "C" int dsnt_bn_finalize(const float* partial, int ntiles, int64_t M, int C,
                                 const float* gamma, const float* beta, float* running_mean,
                                 float* running_var, float momentum, float eps, int training,
@@ -158,7 +268,7 @@ extern "C" int dsnt_bn_finalize(const float* partial, int ntiles, int64_t M, int
     const double unbias = M > 1 ? (double)M / (double)(M - 1) : 1.0;
     const BnFinP q{partial, ntiles, 1.0 / (double)M, unbias, C, gamma, beta, running_mean, running_var, momentum, eps, training,
                    mean, invstd, scale, shift, 0, BnBoundP{nullptr, nullptr, 0.f, nullptr}};
-    DSNT_LAUNCH_OP(DSNT_ST_FIN_FWD, bn_finalize_kernel<0>, dim3((C + 15) / 16), dim3(FIN_T), 0, stream, q);
+    DSNT_LAUNCH(bn_finalize_kernel<0>, dim3((C + 15) / 16), dim3(FIN_T), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_bn_finalize");
 }
 
@@ -202,7 +312,7 @@ extern "C" int dsnt_bn_bwd_finalize(const float* partial, int ntiles, int64_t M,
     const double invM = (accumulate & DSNT_BN_FROZEN) ? 0.0 : 1.0 / (double)M;
     const BnFinP q{partial, ntiles, invM, 1.0, C, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 1, dgamma, dbeta, coef, nullptr,
                    accumulate & 1, BnBoundP{nullptr, nullptr, 0.f, nullptr}};
-    DSNT_LAUNCH_OP(DSNT_ST_FIN_BWD, bn_finalize_kernel<1>, dim3((C + 15) / 16), dim3(FIN_T), 0, stream, q);
+    DSNT_LAUNCH(bn_finalize_kernel<1>, dim3((C + 15) / 16), dim3(FIN_T), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_bn_bwd_finalize");
 }
 
@@ -218,7 +328,7 @@ extern "C" int dsnt_bn_bwd_finalize_bound(const float* partial, int ntiles, int6
     DSNT_REQUIRE(!(accumulate & DSNT_BN_FROZEN), DSNT_ERR_ARG, "dsnt_bn_bwd_finalize_bound: DSNT_BN_FROZEN has no bound form");
     const BnFinP q{partial, ntiles, 1.0 / (double)M, 1.0, C, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 1, dgamma, dbeta, coef, nullptr,
                    accumulate & 1, BnBoundP{scale, dz_amax, sqrtf((float)M), reinterpret_cast<unsigned*>(bound_out)}};
-    DSNT_LAUNCH_OP(DSNT_ST_FIN_BWD, bn_finalize_kernel<1>, dim3((C + 15) / 16), dim3(FIN_T), 0, stream, q);
+    DSNT_LAUNCH(bn_finalize_kernel<1>, dim3((C + 15) / 16), dim3(FIN_T), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_bn_bwd_finalize_bound");
 }
 
@@ -293,6 +403,85 @@ extern "C" int dsnt_relu_bwd(const float* dy, const float* y, float* dz, int64_t
 }
 
 // ---------------------------------------------------------------- apply, backward
+// FIXED: the grid stride is a multiple of C/4, so a thread stays on ONE channel group — its six per-channel vectors are
+// loaded once instead of with every element (they were two thirds of the kernel's load instructions), and two elements are
+// in flight per iteration.  Same arithmetic, element for element.
+struct BnApplyVec { float4 sc, sh, mu, is, c0, c1; };
+__device__ __forceinline__ float4 bn_apply_one(const float4 g, const float4 xv, const BnApplyVec& v, int relu) {
+    float4 dz = g;
+    if (relu) {
+        if (fmaf(xv.x, v.sc.x, v.sh.x) <= 0.f) dz.x = 0.f;
+        if (fmaf(xv.y, v.sc.y, v.sh.y) <= 0.f) dz.y = 0.f;
+        if (fmaf(xv.z, v.sc.z, v.sh.z) <= 0.f) dz.z = 0.f;
+        if (fmaf(xv.w, v.sc.w, v.sh.w) <= 0.f) dz.w = 0.f;
+    }
+    float4 o;
+    o.x = v.sc.x * (dz.x - v.c0.x - (xv.x - v.mu.x) * v.is.x * v.c1.x);
+    o.y = v.sc.y * (dz.y - v.c0.y - (xv.y - v.mu.y) * v.is.y * v.c1.y);
+    o.z = v.sc.z * (dz.z - v.c0.z - (xv.z - v.mu.z) * v.is.z * v.c1.z);
+    o.w = v.sc.w * (dz.w - v.c0.w - (xv.w - v.mu.w) * v.is.w * v.c1.w);
+    return o;
+}
+struct BnApplyP {
+    const float4* da; const float4* x; const float4* scale; const float4* shift; const float4* mean; const float4* invstd;
+    const float4* coef; int relu; float4* dx; const float4* base; long n4; int C4; unsigned* amax; BnBwdProP pro;
+};
+template <bool FIXED>
+__global__ void bn_act_bwd_apply_kernel(BnApplyP q) {
+    __shared__ double pro_sh[512];
+    const float4* __restrict__ da = q.da; const float4* __restrict__ x = q.x; const float4* __restrict__ scale = q.scale;
+    const float4* __restrict__ shift = q.shift; const float4* __restrict__ mean = q.mean; const float4* __restrict__ invstd = q.invstd;
+    const float4* coef = q.coef; const int relu = q.relu; float4* dx = q.dx; const float4* base = q.base;
+    const long n4 = q.n4; const int C4 = q.C4; unsigned* __restrict__ amax = q.amax; const BnBwdProP pro = q.pro;
+    // base: what the result is added to — null (dx = value), dx itself (accumulate in place) or ANOTHER tensor (dx = base + value:
+    // the gradient it continues stays intact for a reader that comes later, dsnt_bn_act_bwd_apply_base)
+    const bool accumulate = base != nullptr;
+    const int wg = blockIdx.x, nwg = gridDim.x;
+    if (pro.partial) {                   // dsnt_bn_act_bwd_apply_pro: coef / dgamma / dbeta from the tile sums, here
+        bn_pro_backward<256>(pro, pro_sh, wg == 0);
+        __syncthreads();                 // this workgroup's stores to coef are visible to its loads below
+    }
+    float am = 0.f;
+    const long stride = (long)nwg * 256;
+    // (256 threads per workgroup: the select always takes its first arm.  Without it <true> needs 4 more VGPRs, <false> 3 more instructions)
+    long i = threadIdx.x < 256 ? (long)wg * 256 + threadIdx.x : n4;
+    auto vec = [&](int cg) {
+        BnApplyVec v;
+        v.sc = scale[cg]; v.sh = shift[cg]; v.mu = mean[cg]; v.is = invstd[cg]; v.c0 = coef[cg]; v.c1 = coef[C4 + cg];
+        return v;
+    };
+    auto amx = [&](const float4 o) { am = fmaxf(fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))), am); };
+    if (FIXED) {
+        const BnApplyVec v = vec((int)((i < n4 ? i : 0) % C4));
+        for (; i + stride < n4; i += 2 * stride) {
+            const float4 g0 = da[i], x0 = x[i], g1 = da[i + stride], x1 = x[i + stride];
+            float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0;
+            if (accumulate) { p0 = base[i]; p1 = base[i + stride]; }
+            float4 o0 = bn_apply_one(g0, x0, v, relu), o1 = bn_apply_one(g1, x1, v, relu);
+            if (accumulate) {
+                o0.x += p0.x; o0.y += p0.y; o0.z += p0.z; o0.w += p0.w;
+                o1.x += p1.x; o1.y += p1.y; o1.z += p1.z; o1.w += p1.w;
+            }
+            dx[i] = o0; dx[i + stride] = o1;
+            amx(o0); amx(o1);
+        }
+        if (i < n4) {
+            float4 o = bn_apply_one(da[i], x[i], v, relu);
+            if (accumulate) { const float4 p = base[i]; o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
+            dx[i] = o;
+            amx(o);
+        }
+    } else {
+        for (; i < n4; i += stride) {
+            float4 o = bn_apply_one(da[i], x[i], vec((int)(i % C4)), relu);
+            if (accumulate) { const float4 p = base[i]; o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
+            dx[i] = o;
+            amx(o);
+        }
+    }
+    if (amax) amax_commit(am, amax);             // max |dx| for the fp16x3 consumers
+}
+
 static int bn_act_bwd_apply_impl(const float* da, const float* x, const float* scale, const float* shift,
                                  const float* mean, const float* invstd, const float* coef, int relu, float* dx,
                                  int accumulate, int64_t M, int C, float* amax, void* stream, const BnBwdProP* pro, const float* base) {
@@ -313,9 +502,9 @@ static int bn_act_bwd_apply_impl(const float* da, const float* x, const float* s
     const BnApplyP ap{(const float4*)da, (const float4*)x, (const float4*)scale, (const float4*)shift, (const float4*)mean,
                       (const float4*)invstd, (const float4*)coef, relu, (float4*)dx, (const float4*)base, n4, C / 4, (unsigned*)amax, q};
     if (((long)grid * 256) % (C / 4) == 0)
-        DSNT_LAUNCH_OP(DSNT_ST_APPLY_FIXED, bn_act_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, stream, ap);
+        DSNT_LAUNCH(bn_act_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, stream, ap);
     else
-        DSNT_LAUNCH_OP(DSNT_ST_APPLY, bn_act_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, stream, ap);
+        DSNT_LAUNCH(bn_act_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, stream, ap);
     DSNT_CHECK_LAUNCH("dsnt_bn_act_bwd_apply");
 }
 

@@ -88,7 +88,7 @@ __device__ __forceinline__ void bn_pro_sums(const float* __restrict__ partial, i
 template <int NT>
 __device__ __forceinline__ void bn_pro_forward(const BnProP& q, double* sh, bool writer) {
     // (the affine parameters and the running statistics are fetched BEFORE the sums: behind them a load is a microsecond of every
-    // workgroup's prologue, i.e. of the dependency chain — ew_bodies.h bn_finalize_kernel, round 5)
+    // workgroup's prologue, i.e. of the dependency chain — bn.hip bn_finalize_kernel, round 5)
     const int c = threadIdx.x;
     float pg = 1.f, pb = 0.f, prm = 0.f, prv = 0.f;
     if (c < q.C) {

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void bwd1_kernel(Bwd1P p) {
             float4 d = make_float4(__uint_as_float(R.z[i].x), __uint_as_float(R.z[i].y), __uint_as_float(R.z[i].z), __uint_as_float(R.z[i].w));
             if (MODE == 0) {
                 const float4 y = make_float4(__uint_as_float(R.y[i].x), __uint_as_float(R.y[i].y), __uint_as_float(R.y[i].z), __uint_as_float(R.y[i].w));
-                // the arithmetic of bn_act_bwd_apply (ew_bodies.h), element for element
+                // the arithmetic of bn_act_bwd_apply (bn.hip), element for element
                 d.x = vs.x * (d.x - v0.x - (y.x - vm.x) * vi.x * v1.x);
                 d.y = vs.y * (d.y - v0.y - (y.y - vm.y) * vi.y * v1.y);
                 d.z = vs.z * (d.z - v0.z - (y.z - vm.z) * vi.z * v1.z);

@@ -5,7 +5,6 @@
 #include "common.h"
 #include "bn_pro.h"
 #include "ew_bodies.h"
-#include "stage.h"
 
 // ---------------------------------------------------------------- pooling / upsampling
 __global__ void maxpool2_fwd_kernel(const float4* __restrict__ x, float4* __restrict__ y,
@@ -65,11 +64,41 @@ extern "C" int dsnt_maxpool2_fwd_stats(const float* x, float* y, uint8_t* idx, f
     const long M = (long)N * (H / 2) * (W / 2);
     const long tiles = (M + TILE_ROWS - 1) / TILE_ROWS;
     const TileOpP q{x, nullptr, y, idx, partial, N, H / 2, W / 2, C, tile_cgs(tiles, C / 4), tail, nullptr, nullptr, 0};
-    DSNT_LAUNCH_OP(DSNT_ST_TILE_POOL, tile_op_stats_kernel<0>, dim3((unsigned)tiles, tile_grid_y(tiles, C / 4)), dim3(256), 0, stream, q);
+    DSNT_LAUNCH(tile_op_stats_kernel<0>, dim3((unsigned)tiles, tile_grid_y(tiles, C / 4)), dim3(256), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_maxpool2_fwd_stats");
 }
 
-__global__ void maxpool2_bwd_kernel(PoolBwdP q) { maxpool2_bwd_body(q, blockIdx.x, gridDim.x); }
+// (`extra`, optional: a second gradient of x — same layout as dx — added in the same pass: dx (+)= extra + the routed dy)
+struct PoolBwdP { const float4* dy; const uchar4* idx; float4* dx; int accumulate; const float4* extra; int N, H, W, C4; unsigned* amax; };
+__global__ void maxpool2_bwd_kernel(PoolBwdP q) {
+    const float4* __restrict__ dy = q.dy; const uchar4* __restrict__ idx = q.idx; float4* dx = q.dx; const int accumulate = q.accumulate;
+    const float4* __restrict__ extra = q.extra; const int H = q.H, W = q.W, C4 = q.C4, N = q.N; unsigned* amax = q.amax;
+    const int Ho = H >> 1, Wo = W >> 1;
+    const long total = (long)N * Ho * Wo * C4;
+    const int wg = blockIdx.x, nwg = gridDim.x;
+    float am = 0.f;
+    for (long i = (long)wg * 256 + threadIdx.x; i < total; i += (long)nwg * 256) {
+        const int cg = (int)(i % C4);
+        long t = i / C4;
+        const int ow = (int)(t % Wo); t /= Wo;
+        const int oh = (int)(t % Ho);
+        const int n = (int)(t / Ho);
+        const float4 g = dy[i];
+        const uchar4 k = idx[i];
+        float4* base = dx + (((long)n * H + 2 * oh) * W + 2 * ow) * C4 + cg;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            float4* q = base + (p >> 1) * (long)W * C4 + (p & 1) * C4;
+            float4 o = make_float4(k.x == p ? g.x : 0.f, k.y == p ? g.y : 0.f, k.z == p ? g.z : 0.f,
+                                   k.w == p ? g.w : 0.f);
+            if (accumulate) { const float4 c = *q; o.x += c.x; o.y += c.y; o.z += c.z; o.w += c.w; }
+            if (extra) { const float4 e = extra[q - dx]; o.x += e.x; o.y += e.y; o.z += e.z; o.w += e.w; }
+            *q = o;
+            am = fmaxf(fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))), am);
+        }
+    }
+    if (amax) amax_commit(am, amax);
+}
 
 static int maxpool2_bwd_impl(const float* dy, const uint8_t* idx, float* dx, int accumulate, const float* extra, int N, int H, int W,
                              int C, float* amax, void* stream) {
@@ -78,7 +107,7 @@ static int maxpool2_bwd_impl(const float* dy, const uint8_t* idx, float* dx, int
     DSNT_REQUIRE(C % 4 == 0 && dsnt_aligned16(dy) && dsnt_aligned16(dx), DSNT_ERR_ALIGN, "dsnt_maxpool2_bwd: alignment");
     const long total = (long)N * (H / 2) * (W / 2) * (C / 4);
     const PoolBwdP q{(const float4*)dy, (const uchar4*)idx, (float4*)dx, accumulate, (const float4*)extra, N, H, W, C / 4, (unsigned*)amax};
-    DSNT_LAUNCH_OP(DSNT_ST_POOL_BWD, maxpool2_bwd_kernel, dim3(flat_grid(total, 256)), dim3(256), 0, stream, q);
+    DSNT_LAUNCH(maxpool2_bwd_kernel, dim3(flat_grid(total, 256)), dim3(256), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_maxpool2_bwd");
 }
 extern "C" int dsnt_maxpool2_bwd(const float* dy, const uint8_t* idx, float* dx, int accumulate,
@@ -135,11 +164,35 @@ extern "C" int dsnt_upsample2_add_fwd_stats(const float* up, const float* low, f
     const long M = (long)N * H * W;
     const long tiles = (M + TILE_ROWS - 1) / TILE_ROWS;
     const TileOpP q{up, low, out, nullptr, partial, N, H, W, C, tile_cgs(tiles, C / 4), tail, nullptr, nullptr, 0};
-    DSNT_LAUNCH_OP(DSNT_ST_TILE_UPADD, tile_op_stats_kernel<1>, dim3((unsigned)tiles, tile_grid_y(tiles, C / 4)), dim3(256), 0, stream, q);
+    DSNT_LAUNCH(tile_op_stats_kernel<1>, dim3((unsigned)tiles, tile_grid_y(tiles, C / 4)), dim3(256), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_upsample2_add_fwd_stats");
 }
 
-__global__ void upsample2_bwd_kernel(UpBwdP q) { upsample2_bwd_body(q, blockIdx.x, gridDim.x); }
+struct UpBwdP { const float4* dout; float4* dlow; int accumulate; int N, H, W, C4; unsigned* amax; };
+__global__ void upsample2_bwd_kernel(UpBwdP q) {
+    const float4* __restrict__ dout = q.dout; float4* dlow = q.dlow; const int accumulate = q.accumulate;
+    const int N = q.N, H = q.H, W = q.W, C4 = q.C4; unsigned* amax = q.amax;
+    const int Hl = H >> 1, Wl = W >> 1;
+    const long total = (long)N * Hl * Wl * C4;
+    const int wg = blockIdx.x, nwg = gridDim.x;
+    float am = 0.f;
+    // (256 threads per workgroup: the select always takes its first arm; without it the kernel needs one more SGPR)
+    for (long i = threadIdx.x < 256 ? (long)wg * 256 + threadIdx.x : total; i < total; i += (long)nwg * 256) {
+        const int cg = (int)(i % C4);
+        long t = i / C4;
+        const int w = (int)(t % Wl); t /= Wl;
+        const int h = (int)(t % Hl);
+        const int n = (int)(t / Hl);
+        const float4* b = dout + (((long)n * H + 2 * h) * W + 2 * w) * C4 + cg;
+        const float4 v0 = b[0], v1 = b[C4], v2 = b[(long)W * C4], v3 = b[(long)W * C4 + C4];
+        float4 o = make_float4((v0.x + v1.x) + (v2.x + v3.x), (v0.y + v1.y) + (v2.y + v3.y),
+                               (v0.z + v1.z) + (v2.z + v3.z), (v0.w + v1.w) + (v2.w + v3.w));
+        if (accumulate) { const float4 c = dlow[i]; o.x += c.x; o.y += c.y; o.z += c.z; o.w += c.w; }
+        dlow[i] = o;
+        am = fmaxf(fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))), am);
+    }
+    if (amax) amax_commit(am, amax);
+}
 
 static int upsample2_bwd_impl(const float* dout, float* dlow, int accumulate, int N, int H, int W, int C, float* amax,
                               void* stream) {
@@ -148,7 +201,7 @@ static int upsample2_bwd_impl(const float* dout, float* dlow, int accumulate, in
     DSNT_REQUIRE(C % 4 == 0 && dsnt_aligned16(dout) && dsnt_aligned16(dlow), DSNT_ERR_ALIGN, "dsnt_upsample2_bwd: alignment");
     const long total = (long)N * (H / 2) * (W / 2) * (C / 4);
     const UpBwdP q{(const float4*)dout, (float4*)dlow, accumulate, N, H, W, C / 4, (unsigned*)amax};
-    DSNT_LAUNCH_OP(DSNT_ST_UP_BWD, upsample2_bwd_kernel, dim3(flat_grid(total, 256)), dim3(256), 0, stream, q);
+    DSNT_LAUNCH(upsample2_bwd_kernel, dim3(flat_grid(total, 256)), dim3(256), 0, stream, q);
     DSNT_CHECK_LAUNCH("dsnt_upsample2_bwd");
 }
 extern "C" int dsnt_upsample2_bwd(const float* dout, float* dlow, int accumulate, int N, int H, int W,

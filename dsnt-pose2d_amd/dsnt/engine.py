@@ -137,9 +137,8 @@ class Tape:
         self.nbytes = 0
         self._read_switches()
         # the two launch lists (dsnt.launchlist), replayed from C: recorded once into the library, then issued by ONE call per segment
-        stage = (device, self.stage_min_run, self.stage_max_vgrid, self.stage_grid) if (self.stage and device.type == 'cuda') else None
         lanes = Lanes(self.use_lanes, self.n_lanes)
-        self.fwd, self.bwd = (LaunchList(self.lib, lanes, self._keep, stage) for _ in range(2))
+        self.fwd, self.bwd = (LaunchList(self.lib, lanes, self._keep) for _ in range(2))
         self.bounds = Bounds(self)          # fp16x3 operand bounds and the per-step preparation (dsnt.bounds)
         self.wgrads = WgradQueue(self)      # weight gradients held back, grouped and reduced per bucket (dsnt.wgrad_queue)
         self.lane = 0           # the lane being traced onto
@@ -200,14 +199,6 @@ class Tape:
         # 128 x 128 and 64 x 64 levels from batch 4 and 16 on.
         self.ds_fuse = 'dsfuse' not in off
         self.ds_fuse_rows = int(os.environ.get('DSNT_X_DS_FUSE_ROWS', '65536'))
-        # round 6: runs of small dependent launches of one lane as ONE persistent launch (csrc/stage.h).  OFF by default — built,
-        # bit-identical to the launches it replaces (tests/test_stage_gpu.py), and measured SLOWER: hg2 batch 32 11.06 -> 11.97 ms,
-        # hg8 batch 16 24.1 -> 25.7 ms with every run fused; 11.17 / 24.04 (no gain) with only the <= 64-workgroup launches of the
-        # 4 x 4 level inside (profiles/r06_stage_ab.txt).  DSNT_STAGE=1 turns it on (A/B, tests).
-        self.stage = os.environ.get('DSNT_STAGE', '0') == '1'
-        self.stage_min_run = int(os.environ.get('DSNT_X_STAGE_MIN_RUN', '3'))
-        self.stage_max_vgrid = int(os.environ.get('DSNT_X_STAGE_MAX_VGRID', '512'))
-        self.stage_grid = int(os.environ.get('DSNT_X_STAGE_GRID', '64'))
         # DSNT_X=<name>=<value>,...: A/B overrides of scheduling constants (tools/ab_env.sh); not product switches
         self._x = dict(kv.split('=') for kv in os.environ.get('DSNT_X', '').split(',') if '=' in kv)
         self.wgrad_narrow = self._x.get('wgrad_narrow', '1')      # DSNT_WGRAD_NARROW: 0 never, 1 always, 2 stem bucket only, 3 stacks only
@@ -378,14 +369,6 @@ class Tape:
         profiles/r05_ab_switches.txt box B.)"""
         if self.record and self.defer_reduce and self.flush_points:
             self.on_backward(self.wgrads.flush)
-
-    stage_census = property(lambda self: self.fwd.stage_census + self.bwd.stage_census)
-
-    def stage_errors(self):
-        """Persistent stages of this tape's compiled lists whose barrier gave up (a workgroup never arrived) since they were
-        built: 0 in a healthy process.  Synchronises the device (diagnostic / tests)."""
-        torch.cuda.synchronize()
-        return self.fwd.stage_errors() + self.bwd.stage_errors()
 
     def run(self, lst, bucket_hook=None, probe=None):
         """Replay one of the tape's lists.  `probe(entry)` (diagnostics / tests) is called before every launch."""

@@ -35,16 +35,14 @@ class Lanes:
 class LaunchList(list):
     """Entries (cfunc, converted args, name, lane); cfunc None: ('sync', (src, dst, event)) or ('bucket', k).
 
-    keep: where structs (and a fused list's workspace) are kept alive — the owner's list, or one of its own.
-    stage: (device, min_run, max_vgrid, grid) to fuse runs of small launches into persistent stages when compiled."""
+    keep: where structs are kept alive — the owner's list, or one of its own."""
 
-    def __init__(self, lib, lanes, keep=None, stage=None):
+    def __init__(self, lib, lanes, keep=None):
         super().__init__()
-        self.lib, self.lanes, self.stage = lib, lanes, stage
+        self.lib, self.lanes = lib, lanes
         self.keep = [] if keep is None else keep
         self.nbytes, self.bytes_by_name = 0, {}
         self.workspace = set()      # data pointers of tensors that are workspace, not algorithm: left out of the byte counts
-        self.stage_census = []      # (stage launches, recorded launches inside) once compiled
         self._into = self           # where new entries go (`into`)
         self._compiled = None
 
@@ -117,7 +115,6 @@ class LaunchList(list):
                 lib.dsnt_list_end()
             for lane in range(1, lanes.n) if lanes.use else ():
                 check(lib, lib.dsnt_list_sync(h, lane, 0), 'dsnt_list_sync')
-            self._fuse_stages(h)
         except Exception:
             lib.dsnt_list_destroy(h)
             raise
@@ -128,28 +125,6 @@ class LaunchList(list):
         if self._compiled is None:
             self._compiled = self.record()
         return self._compiled
-
-    def _fuse_stages(self, h):
-        """Runs of small dependent launches of one lane (the 8 x 8 / 4 x 4 hourglass levels) -> persistent stage launches
-        (include/dsnt_hip.h: dsnt_list_fuse).  The tables and counters live in a tensor kept with the list's structs."""
-        if self.stage is None:
-            return
-        lib, (device, min_run, max_vgrid, grid) = self.lib, self.stage
-        need = lib.dsnt_list_fuse_bytes(h, min_run, max_vgrid)
-        if need <= 0:
-            return
-        ws = torch.zeros((need + 63) // 64 * 64, dtype=torch.uint8, device=device)
-        self.keep.append(ws)
-        rc = lib.dsnt_list_fuse(h, C.c_void_p(ws.data_ptr()), ws.numel(), min_run, max_vgrid, grid)
-        if rc < 0:
-            check(lib, rc, 'dsnt_list_fuse')
-        inside = C.c_int(0)
-        n = lib.dsnt_list_stages(h, C.byref(inside))
-        self.stage_census.append((n, inside.value))
-
-    def stage_errors(self):
-        """Persistent stages of the compiled list whose barrier gave up since they were built (blocking device reads)."""
-        return max(0, self.lib.dsnt_list_stage_errors(self._compiled[0])) if self._compiled is not None else 0
 
     def __del__(self):
         try:

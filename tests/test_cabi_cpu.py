@@ -11,6 +11,8 @@ HEADERS = [os.path.join(ROOT, 'include', 'dsnt_hip.h')]          # the product A
 # the calibration probes and the debug switch the library once carried beside the ABI: gone, and not to come back unnoticed
 RETIRED_PROBES = ['dsnt_debug_mfma_peak', 'dsnt_debug_coexec', 'dsnt_debug_bf16_peak', 'dsnt_debug_starve',
                   'dsnt_debug_grid_barrier', 'dsnt_debug_grid_barrier2', 'dsnt_debug_empty', 'dsnt_debug_force_gemm6']
+# the list-fusing entry points of the persistent low-resolution stage (measured slower, profiles/r06_stage_ab.txt): removed in 132
+RETIRED_STAGE = ['dsnt_list_fuse_bytes', 'dsnt_list_fuse', 'dsnt_list_fuse_plan', 'dsnt_list_stages', 'dsnt_list_stage_errors']
 
 
 def _declared(headers=HEADERS):
@@ -36,6 +38,16 @@ def test_library_exports_every_declared_symbol():
     assert not [n for n in _declared(HEADERS[:1]) if n.startswith('dsnt_debug')]
     for n in RETIRED_PROBES:
         assert not hasattr(lib, n), 'libdsnt_hip.so still exports ' + n
+
+
+def test_retired_stage_symbols_are_neither_exported_nor_bound():
+    from dsnt import _lib
+    lib = _lib.load()
+    assert lib.dsnt_version() >= 132
+    for n in RETIRED_STAGE:
+        assert not hasattr(lib, n), 'libdsnt_hip.so still exports ' + n
+        assert n not in _lib.SIGNATURES and n not in _lib.PLAIN, 'dsnt._lib still binds ' + n
+        assert n not in _declared(), 'include/dsnt_hip.h still declares ' + n
 
 
 def _prototypes(headers=HEADERS):

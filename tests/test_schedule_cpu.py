@@ -239,36 +239,6 @@ def test_resnet34_train_schedule(monkeypatch_module):
     assert len(fwd) <= 180 and len(bwd) <= 330, (len(fwd), len(bwd))
 
 
-def test_persistent_stage_runs_of_the_recorded_lists(tape):
-    """Round 6 (csrc/stage.h): the 8 x 8 / 4 x 4 levels of every hourglass (hourglass.py:78-90) are runs of small dependent launches
-    of one lane that dsnt_list_fuse turns into persistent stage launches.  Recording a list needs no GPU (launches are captured, not
-    enqueued); dsnt_list_fuse_plan runs the same run finder as dsnt_list_fuse."""
-    import ctypes as C
-    from dsnt import _lib
-    lib = _lib.load()
-    for lst, lo, hi in ((tape.fwd, 2 * 24, 2 * 32), (tape.bwd, 2 * 40, 2 * 56)):
-        h, marks = lst.record()
-        try:
-            size = lib.dsnt_list_size(h)
-            n = C.c_int(0)
-            s = lib.dsnt_list_fuse_plan(h, 3, 512, C.byref(n))
-            # per hourglass: the 4 x 4 chain, the two 8 x 8 runs around it and the 8 x 8 skip branch on its side lane
-            assert 2 * 3 <= s <= 2 * 5, (s, n.value)
-            assert lo <= n.value <= hi, (s, n.value)
-            assert lib.dsnt_list_fuse_bytes(h, 3, 512) == 512 * n.value + 64 * s
-            # nothing to fuse if runs had to be longer than any run is / launches narrower than any of these are
-            assert lib.dsnt_list_fuse_plan(h, 64, 512, None) == 0 and lib.dsnt_list_fuse_plan(h, 3, 1, None) == 0
-            assert lib.dsnt_list_size(h) == size        # planning changes nothing
-            # argument checks of the fusing call come before anything touches the device: more than 256 stage workgroups cannot be
-            # co-resident (the barrier would wait for ever — bounded, but wrong); the workspace is the caller's and must be big enough
-            assert lib.dsnt_list_fuse(h, None, 0, 3, 512, 300) != 0 and b'grid_cap' in lib.dsnt_last_error()
-            assert lib.dsnt_list_fuse(h, None, 0, 3, 512, 64) != 0 and b'workspace' in lib.dsnt_last_error()
-            assert lib.dsnt_list_fuse(h, C.c_void_p(64), 64, 3, 512, 64) != 0 and b'workspace' in lib.dsnt_last_error()
-            assert lib.dsnt_list_size(h) == size and lib.dsnt_list_stages(h, None) == 0
-        finally:
-            lib.dsnt_list_destroy(h)
-
-
 def test_launch_list_stands_alone(monkeypatch_module):
     """A LaunchList with no Tape and no model behind it: two launches on two lanes, a lane synchronisation and a bucket mark between
     them.  It records itself into a C list of two segments, once — a second compile hands back the same handle."""

@@ -1,14 +1,14 @@
 """Sensitivity of tests/test_bn_finalize_gpu.py: build libdsnt_hip.so from a scratch copy of csrc/ that carries ONE change to the
-BatchNorm finalise step in ew_bodies.h (a, b) or bn_pro.h (b, c), outside the tree, and print its path.  The module run against it
+BatchNorm finalise step in bn.hip (a, b) or bn_pro.h (b, c), outside the tree, and print its path.  The module run against it
 must FAIL:
 
     python3 tools/mutate_bn_finalize.py a|b|c <empty scratch directory>          # build (no GPU needed)
     DSNT_HIP_LIB=<printed path> python3 -m pytest -m gpu tests/test_bn_finalize_gpu.py
 
      what changes                                                              which tests fail (measured on an MI355X; the rest pass)
-  a  bn_finalize_body: the lane stride `t += FIN_P` -> `FIN_P + 1` (tiles         test_bn_finalize and test_bn_bwd_finalize: all ten cases of 65 tiles
+  a  bn_finalize_kernel: the lane stride `t += FIN_P` -> `FIN_P + 1` (tiles         test_bn_finalize and test_bn_bwd_finalize: all ten cases of 65 tiles
      dropped from the second trip on)                                             or more each; test_bn_bwd_finalize_bound: the three of 65 or more
-  b  the combine's accumulators are `float` (bn_finalize_body's a0 / a1 and       test_bn_finalize 14 of 15, test_bn_bwd_finalize 13 of 15, test_bn_bwd_
+  b  the combine's accumulators are `float` (bn_finalize_kernel's a0 / a1 and      test_bn_finalize 14 of 15, test_bn_bwd_finalize 13 of 15, test_bn_bwd_
      bn_pro_sums' lane sum)                                                       finalize_bound 5 of 5, test_conv_prologue_finalises_... 18 of 30,
                                                                                  test_apply_prologue_finalises_... 19 of 30: every cancelling case and
                                                                                  most producer ones of many tiles (one tile has nothing to combine)
@@ -28,8 +28,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'dsnt-pose2d_amd', 'csrc')
 MUTATIONS = {
-    'a': [('ew_bodies.h', 'for (int t = part; t < ntiles; t += FIN_P) {', 'for (int t = part; t < ntiles; t += FIN_P + 1) {')],
-    'b': [('ew_bodies.h', '    double a0[VP], a1[VP];\n', '    float a0[VP], a1[VP];\n'),
+    'a': [('bn.hip', 'for (int t = part; t < ntiles; t += FIN_P) {', 'for (int t = part; t < ntiles; t += FIN_P + 1) {')],
+    'b': [('bn.hip', '    double a0[VP], a1[VP];\n', '    float a0[VP], a1[VP];\n'),
           ('bn_pro.h', '        double a = 0.0;\n        if (lane < L) {', '        float a = 0.f;\n        if (lane < L) {')],
     'c': [('bn_pro.h', '__device__ __forceinline__ void bn_pro_forward(const BnProP& q, double* sh, bool writer) {\n',
            '__device__ __forceinline__ void bn_pro_forward(const BnProP& q, double* sh, bool writer) {\n    writer = true;\n')],

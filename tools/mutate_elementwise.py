@@ -1,5 +1,5 @@
 """Sensitivity of tests/test_elementwise_edges_gpu.py: build libdsnt_hip.so from a scratch copy of csrc/ that carries ONE
-change in resample.hip (a, c), optim.hip (e, f), bn.hip (g) or ew_bodies.h (b, d), outside the tree, and print its path.  The module run against it must FAIL:
+change in resample.hip (a, c), optim.hip (e, f), bn.hip (d, g) or ew_bodies.h (b), outside the tree, and print its path.  The module run against it must FAIL:
 
     python3 tools/mutate_elementwise.py a|b|c|d|e|f|g <empty scratch directory>          # build (no GPU needed)
     DSNT_HIP_LIB=<printed path> python3 -m pytest -m gpu tests/test_elementwise_edges_gpu.py
@@ -19,7 +19,7 @@ change in resample.hip (a, c), optim.hip (e, f), bn.hip (g) or ew_bodies.h (b, d
                                                                                    yardstick; with one row in all, the dropped partial is zero)
 
 Values and skipped work only: no mutation touches an address, a bound or a loop limit in a way that could read or write outside a
-tensor (g reads one lane partial FEWER).  A header mutation (b, d) rebuilds every source that includes ew_bodies.h.  Nothing here
+tensor (g reads one lane partial FEWER).  The header mutation (b) rebuilds every source that includes ew_bodies.h.  Nothing here
 changes the product."""
 import os
 import shutil
@@ -32,7 +32,7 @@ MUTATIONS = {
     'a': ('resample.hip', 'if (V.x > m.x || V.x != V.x) { m.x = V.x; k.x = P; }', 'if (V.x >= m.x || V.x != V.x) { m.x = V.x; k.x = P; }'),
     'b': ('ew_bodies.h', 'if (V.x > v.x || V.x != V.x) { v.x = V.x; k.x = P; }', 'if (V.x >= v.x || V.x != V.x) { v.x = V.x; k.x = P; }'),
     'c': ('resample.hip', 'if (v.x > m.x || v.x != v.x) { m.x = v.x; k.x = p; }', 'if (v.x >= m.x || v.x != v.x) { m.x = v.x; k.x = p; }'),
-    'd': ('ew_bodies.h', 'o1 = bn_apply_one(g1, x1, v, relu);', 'o1 = bn_apply_one(g1, x1, v, 0);'),
+    'd': ('bn.hip', 'o1 = bn_apply_one(g1, x1, v, relu);', 'o1 = bn_apply_one(g1, x1, v, 0);'),
     'e': ('optim.hip', '        if (wd != 0.f) gi = fmaf(wd, pi, gi);\n        const float s = alpha * sq[i]', '        const float s = alpha * sq[i]'),
     'f': ('optim.hip', 'momentum * buf[i] + gi', 'momentum * gi + buf[i]'),
     'g': ('bn.hip', 'for (int j = 0; j < rpar; ++j)', 'for (int j = 0; j < rpar - 1; ++j)'),
