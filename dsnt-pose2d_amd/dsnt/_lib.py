@@ -113,7 +113,7 @@ SIGNATURES = {
     'dsnt_conv_wgrad_f16x3': [P, P, P, I, P, P, P, P, I, P, P, GP, P],
     'dsnt_conv1x1_fwd_f16x3': [P, P, L, P, P, P, P, P, P, I, P, P, GP, TP, P],
     'dsnt_conv1x1_bwd_f16x3': [BP, P, AP, P, L, P, P, P, P, P, P, P, I, GP, P],
-    # conv3 of a Bottleneck and its projection shortcut as one forward launch (engine.py `_conv_forward_ds`)
+    # conv3 of a Bottleneck and its projection shortcut as one forward launch (convop.py `ConvOp.forward_ds`)
     'dsnt_conv1x1_fwd_ds_f16x3': [P, P, P, P, L, P, P, P, P, P, P, P, P, P, I, P, GP, GP, TP, P],
     'dsnt_conv_dgrad_f16x3_stream_apply': [P, AP, P, P, L, P, P, P, P, I, GP, BP, TP, P],
     'dsnt_wgrad_reduce_all': [P, I, I, P],

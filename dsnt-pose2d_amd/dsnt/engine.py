@@ -17,14 +17,18 @@ into a hipGraph).  Fusions decided at trace time:
 
 Gradients with respect to parameters are written straight into one flat arena (the same arena
 the fused optimiser and the RCCL all-reduce operate on).
+
+This module is the tape: buffers, lanes, gradient plumbing, BatchNorm bookkeeping and the element-wise ops.  The convolution —
+its forward choice, its backward plan and everything its backward emits — is a `ConvOp` (dsnt.convop) that `Tape.conv` and
+`Tape.conv_ds` build; the launch lists, the operand bounds and the weight-gradient queue are dsnt.launchlist, dsnt.bounds and
+dsnt.wgrad_queue.
 """
-import ctypes as C
 import os
 
 import torch
 
-from . import _lib
-from ._lib import ConvGeom, BnBwdEpilogue, BnTail, BnPrologue, BnBwdApply
+from . import _lib, convop
+from ._lib import ConvGeom, BnTail
 from .bounds import Bounds
 from .launchlist import Lanes, LaunchList
 from .wgrad_queue import WgradQueue
@@ -42,7 +46,7 @@ class Act:
         self.buf = buf
         self.N, self.H, self.W, self.C = buf.shape
         self._grad = None       # torch tensor once some backward op has written it (`grad`)
-        # a gradient this activation's CONTINUES without owning it (Tape.conv's backward, `defer_res`): the next writer writes
+        # a gradient this activation's CONTINUES without owning it (`ConvOp.residual_grads`, `defer_res`): the next writer writes
         # base + its value into a buffer of its own (`Tape.grad_target`), so that the base stays intact for a deferred reader
         self.base, self.base_amax = None, None
         self.stats = None       # (partial tensor, ntiles)
@@ -109,15 +113,13 @@ class Normed:
     __slots__ = ('x', 'bn', 'mean', 'invstd', 'scale', 'shift', 'relu', 'abound', 'pending', 'lane')
 
 
-class _Conv:
-    """One traced convolution: what `Tape.conv` decided forward and what the methods that emit its backward read."""
-    __slots__ = ('src', 'x', 'y', 'p', 'g', 'res1', 'res2', 'name', 'normed', 'sc', 'sh', 'relu', 'x_amax', 'use6', 'use16',
-                 'slot', 'slot_k', 'bucket', 'fuse1', 'fold3_ok', 'need_input_grad', 'gd')
+class PendingApply:
+    """A BatchNorm backward reduced but not applied (`Tape._norm_backward` with dz_amax): dz, the Normed it goes through, its
+    two coefficients per channel, the bound slots of the dx to be formed and of dz."""
+    __slots__ = ('dz', 'n', 'coef', 'bound', 'dz_amax')
 
-
-class _Dgrad:
-    """The operands of one data-gradient launch (`Tape._conv_dgrad_operands`)."""
-    __slots__ = ('native', 'gd', 'gsrc', 'wd', 'wq', 'wq_stride', 'wq16', 'wbd', 'g_amax', 'd6', 'd16', 'd_stream')
+    def __init__(self, dz, n, coef, bound, dz_amax):
+        self.dz, self.n, self.coef, self.bound, self.dz_amax = dz, n, coef, bound, dz_amax
 
 
 class Tape:
@@ -262,15 +264,6 @@ class Tape:
         t = torch.tensor(rows, dtype=dtype).to(self.device)
         self._keep.append(t)
         return t
-
-    def stream_ok(self, p, g, rows, res2):
-        """A 3x3 convolution the symmetric persistent kernel runs (weights in stream order): at most one residual."""
-        return (self.conv3s and p.R == 3 and p.S == 3 and res2 is None and
-                bool(self.lib.dsnt_conv_fwd_stream_ok(C.byref(g))))
-
-    def _use6(self, g):
-        return (self.use_bf16x6 and g.N * g.Ho * g.Wo >= self.bf16x6_min_rows and
-                bool(self.lib.dsnt_conv_bf16x6_ok(C.byref(g))))
 
     def act(self, N, H, W, Cc, name=''):
         a = Act(self.empty(N, H, W, Cc), name)
@@ -459,6 +452,11 @@ class Tape:
             a.stats = (part, tiles)
         return a.stats
 
+    def finalize_in_consumer(self, bn, tiles):
+        """`tiles` rows of partial sums of bn's channels are few enough for the launch that consumes them to finalise them in its
+        prologue (forward: the statistics, backward: dgamma / dbeta / coef) instead of a finalise launch of their own."""
+        return self.fuse_finalize and bn.C <= 256 and tiles * bn.C <= self.fuse_finalize_max
+
     def norm(self, x, bn, relu=True):
         """BatchNorm bookkeeping for x under `bn`: finalise kernel -> scale/shift vectors."""
         if self.no_relu:
@@ -473,7 +471,7 @@ class Tape:
             n.pending = self.ensure_stats(x)
             # few tiles (the 8x8 / 4x4 levels): the launch that CONSUMES this BatchNorm finalises it in its prologue
             # (`conv`); any other first reader materialises it with the usual launch (`materialize`), as do many tiles here
-            if not (self.fuse_finalize and bn.C <= 256 and n.pending[1] * bn.C <= self.fuse_finalize_max):
+            if not self.finalize_in_consumer(bn, n.pending[1]):
                 self.materialize(n)
         else:
             self.bounds.eval_bn(n)
@@ -508,9 +506,9 @@ class Tape:
         """The apply launch of a BatchNorm backward that was left to x's producer (`_norm_backward` with dz_amax) after all:
         x got a second gradient contribution, so its gradient has to exist in memory."""
         ap, x.pending_apply = x.pending_apply, None
-        n = ap['n']
+        n = ap.n
         buf, acc = self.grad_target(x, amax=True)
-        self.b_amax('dsnt_bn_act_bwd_apply', ap['dz'], x.buf, n.scale, n.shift, n.mean, n.invstd, ap['coef'], 0,
+        self.b_amax('dsnt_bn_act_bwd_apply', ap.dz, x.buf, n.scale, n.shift, n.mean, n.invstd, ap.coef, 0,
                     buf, acc, x.M, n.bn.C, amax=x.grad_amax)
 
     def _norm_backward(self, n, da, reduced=None, finalised=False, dz_amax=None):
@@ -538,12 +536,12 @@ class Tape:
             bound = self.bounds.amax_slot()
             self.b('dsnt_bn_bwd_finalize_bound', part, tiles, x.M, bn.C, bn.ggamma, bn.gbeta, acc_p, coef, n.scale,
                    dz_amax, bound)
-            x.pending_apply = dict(dz=da, n=n, coef=coef, bound=bound, dz_amax=dz_amax)
+            x.pending_apply = PendingApply(da, n, coef, bound, dz_amax)
             return
         # eval-mode forward: the statistics are constants — dx = scale dz, i.e. the apply with both coefficients zero
         # (DSNT_BN_FROZEN); the two sums still are dbeta / dgamma
         frozen = not self.training
-        fused = (not finalised) and self.fuse_finalize and bn.C <= 256 and tiles * bn.C <= self.fuse_finalize_max and not frozen
+        fused = (not finalised) and self.finalize_in_consumer(bn, tiles) and not frozen
         assert not (frozen and finalised)
         if not finalised:
             acc_p = 1 if bn.uses > 0 else 0
@@ -570,480 +568,39 @@ class Tape:
     # ------------------------------------------------------------------ convolution
     def conv(self, src, p, res1=None, res2=None, want_stats=False, need_input_grad=True, name=''):
         """y = conv(src) + bias [+ res1 + res2]; src is an Act (raw) or a Normed (BN+ReLU folded)."""
-        c = _Conv()
-        c.src, c.p, c.res1, c.res2, c.name, c.need_input_grad = src, p, res1, res2, name, need_input_grad
-        c.normed = isinstance(src, Normed)
-        c.x = x = src.x if c.normed else src
-        c.g = self.geom(x, p)
-        c.y = y = self.act(x.N, c.g.Ho, c.g.Wo, p.Cout, name)
-        x.uses += 1
+        c = convop.ConvOp(self, src, p, res1, res2, name, need_input_grad)
+        c.y = y = self.act(c.x.N, c.g.Ho, c.g.Wo, p.Cout, name)
+        c.x.uses += 1
         for r in (res1, res2):
             if r is not None:
                 r.uses += 1
                 y.gives_away = True             # dL/dy's buffer is handed to a residual input in backward
-        c.sc, c.sh, c.relu = (src.scale, src.shift, 1 if src.relu else 0) if c.normed else (None, None, 0)
-        self._conv_forward(c, want_stats)
+        c.forward(want_stats)
         if self.record:
-            self._conv_backward_plan(c)
-            self.on_backward(lambda: self._conv_backward(c))
+            c.plan_backward()
+            self.on_backward(c.backward)
         return y
 
-    # ------------------------------------------------------------------ conv3 + projection shortcut in one launch
     def ds_fuse_ok(self, x, p_ds, p3):
         """conv3 of a Bottleneck (p3) and its projection shortcut (p_ds, over the block input x) can run as ONE forward launch
-        (csrc/fwd1.hip DS): a train step on fp16x3 from DSNT_X_DS_FUSE_ROWS rows, equal halves, the forward's `_ok` predicate,
-        x's producer able to leave max|x|.  Asked BEFORE the block is traced: on the fused path the shortcut is not traced on its
-        own and the skip tensor never exists.  The backward stays two launches (`_conv_backward_ds`)."""
-        if not (self.ds_fuse and self.training and self.record and self.use_f16x3 and self.fwd1):
-            return False
-        if not (p_ds.R == 1 and p_ds.S == 1 and p_ds.stride == 1 and p3.R == 1 and p3.S == 1 and p3.stride == 1 and
-                (p_ds.Cin, p_ds.Cout) == (p3.Cin, p3.Cout) and (p3.Cin, p3.Cout) in ((64, 128), (128, 256)) and
-                x.M >= self.ds_fuse_rows and p_ds.post_reduce is None and p3.post_reduce is None):
-            return False
-        if any(p.wq is None or p.wq16 is None for p in (p_ds, p3)) or p_ds.wq_stride != p3.wq_stride:
-            return False
-        g = self.geom(x, p_ds)
-        if not (self._use6(g) and self.lib.dsnt_conv1x1_fwd_ok(C.byref(g))):
-            return False
-        return self.bounds.operand_amax(x) is not None      # (claims the producer's tail, as the shortcut's own launch would)
+        (csrc/fwd1.hip DS).  Asked BEFORE the block is traced: on the fused path the shortcut is not traced on its own and the
+        skip tensor never exists.  The backward stays two launches (`ConvOp.backward_ds`)."""
+        return convop.ds_fuse_ok(self, x, p_ds, p3)
 
     def conv_ds(self, src, p, x_ds, p_ds, want_stats=False, name='', name_ds='ds'):
         """y = conv(src) + bias + (conv_ds(x_ds) + bias_ds): `conv(src, p, res1=conv(x_ds, p_ds))` without the skip tensor
-        (the caller has asked `ds_fuse_ok`)."""
-        c, cd = _Conv(), _Conv()
-        c.src, c.p, c.res1, c.res2, c.name, c.need_input_grad = src, p, None, None, name, True
-        c.normed, c.x = True, src.x
-        c.g = self.geom(c.x, p)
-        cd.src, cd.p, cd.res1, cd.res2, cd.name, cd.need_input_grad = x_ds, p_ds, None, None, name_ds, True
-        cd.normed, cd.x = False, x_ds
-        cd.g = self.geom(x_ds, p_ds)
+        (the caller has asked `ds_fuse_ok`): two ops over one output."""
+        c, cd = convop.ConvOp(self, src, p, None, None, name, True), convop.ConvOp(self, x_ds, p_ds, None, None, name_ds, True)
         c.y = cd.y = y = self.act(c.x.N, c.g.Ho, c.g.Wo, p.Cout, name)
         c.x.uses += 1
         x_ds.uses += 1
-        c.sc, c.sh, c.relu = src.scale, src.shift, 1 if src.relu else 0
-        cd.sc, cd.sh, cd.relu = None, None, 0
-        self._conv_forward_ds(c, cd, want_stats)
+        c.forward_ds(cd, want_stats)
         # (the shortcut's plan first: the order in which the two-launch path asks for the data-gradient slots)
-        self._conv_backward_plan(cd)
-        self._conv_backward_plan(c)
+        cd.plan_backward()
+        c.plan_backward()
         y.fold_ok = False               # dL/dy feeds two convolutions: it has to exist in memory
-        self.on_backward(lambda: self._conv_backward_ds(c, cd))
+        self.on_backward(lambda: c.backward_ds(cd))
         return y
-
-    def _conv_forward_ds(self, c, cd, want_stats):
-        src, x, y, p, g = c.src, c.x, c.y, c.p, c.g
-        self.check_lane(src)
-        c.use6 = cd.use6 = True
-        c.use16 = cd.use16 = True
-        shr = self._share()
-        part = None
-        if want_stats:
-            tiles = self.lib.dsnt_conv1x1_fwd_stats_rows(C.byref(g), shr)
-            part = self.empty(tiles, 2, p.Cout)
-            y.stats = (part, tiles)
-        y.amax_tail = tail = BnTail()
-        ab = self.bounds.f16_bn_bound(src)
-        c.x_amax, cd.x_amax = None, self.bounds.operand_amax(cd.x)
-        self.materialize(src)
-        for q in (p, cd.p):
-            self.bounds.f16_weights(q, stream=False)
-        e = self.f('dsnt_conv1x1_fwd_ds_f16x3', x.buf, cd.x.buf, p.wq16, cd.p.wq16, p.wq_stride, p.wb, cd.p.wb, ab, cd.x_amax,
-                   p.b, cd.p.b, y.buf, c.sc, c.sh, c.relu | shr, part, g, cd.g, tail)
-        # one info per operand pair (tests/test_bounds_gpu.py)
-        self.f16_uses.append((e, dict(kind='fwd', name=c.name, x=x.buf, sc=c.sc, sh=c.sh, relu=c.relu, a_bound=ab,
-                                      w=p.w, w_bound=p.wb)))
-        self.f16_uses.append((e, dict(kind='fwd', name=cd.name, x=cd.x.buf, sc=None, sh=None, relu=0, a_bound=cd.x_amax,
-                                      w=cd.p.w, w_bound=cd.p.wb)))
-
-    def _conv_backward_ds(self, c, cd):
-        """The backward of `conv_ds`: the two convolutions' own backwards over the same dL/dy, conv3's first (what bn3 and conv2
-        wait for).  The shortcut's is then the FIRST writer of dL/dx where its stand-alone trace made it the last; the sum of the
-        two fp32 contributions is the same either way."""
-        y = c.y
-        if y.pending_apply is not None:
-            self.materialize_apply(y)
-        assert y.grad is not None, 'no gradient reached conv output ' + c.name
-        self._conv_backward(c)
-        self._conv_backward(cd)
-
-    def _share(self, persistent=True):
-        """DSNT_CONV_SHARE_CHIP (bit 1 of a launch's flag word) on the side lanes' launches of the persistent kernels (3x3: 3/2
-        workgroups per CU; 1x1: half of the CUs): they hold most of a CU's LDS for the whole launch, and the chain's kernels
-        need LDS too (-0.2 ms)."""
-        return 2 if (persistent and self.lane != 0) else 0
-
-    def _operand_bound(self, c):
-        """The bound slot of c's A operand as its producer leaves it (None if it cannot); the first call claims the producer's tail."""
-        return self.bounds.operand_amax_bn(c.src) if c.normed else self.bounds.operand_amax(c.x)
-
-    @staticmethod
-    def _bn_epilogue(x, n):
-        """The BatchNorm(+ReLU) n in front of x's consumer (None: a raw operand) as a data gradient's epilogue reads it."""
-        vectors = (n.scale, n.shift, n.mean, n.invstd) if n is not None else (None,) * 4
-        return BnBwdEpilogue(_lib.ptr(x.buf), *(_lib.ptr(v) for v in vectors), 1 if (n is not None and n.relu) else 0)
-
-    @staticmethod
-    def _bn_apply(y, ap):
-        """(BnBwdApply of y's pending BatchNorm backward, the tensors behind it for `f16_uses`)."""
-        n = ap['n']
-        return (BnBwdApply(_lib.ptr(y.buf), _lib.ptr(n.scale), _lib.ptr(n.mean), _lib.ptr(n.invstd), _lib.ptr(ap['coef'])),
-                dict(dz=ap['dz'], y=y.buf, scale=n.scale, mean=n.mean, invstd=n.invstd, coef=ap['coef']))
-
-    def _dz_buffer(self, x, private):
-        """dz of the BatchNorm in front of x's consumer: the op's scratch, or — read again by the backward of the 1x1 convolution
-        that produced x (`fold_ok`) — a buffer that outlives this op's launches."""
-        n = x.M * x.C
-        return self.empty(n) if private else self.scratch('da', n).view(-1)[:n]
-
-    def _conv_forward(self, c, want_stats):
-        """Choose c's forward kernel — fwd1 / stem4 / stream or tiled fp16x3 / bf16x6 / fp32 with the BatchNorm finalised in its
-        prologue / fp32 — and emit it."""
-        src, x, y, p, g, normed, res2 = c.src, c.x, c.y, c.p, c.g, c.normed, c.res2
-        sc, sh, relu = c.sc, c.sh, c.relu
-        if normed:
-            self.check_lane(src)
-        part, tail = None, None
-        use6 = c.use6 = self._use6(g) and p.wq is not None
-        can16 = use6 and p.wq16 is not None
-        # the large 1x1 convolutions with both operand bounds: the LDS-staged streaming kernel (csrc/fwd1.hip) — its statistics
-        # come one row per WORKGROUP, and how many that is depends on the launch's share flag, so a candidate claims its bound
-        # (and keeps it if f1 turns out false) BEFORE the statistics buffer is allocated; every other convolution after it
-        early = can16 and p.R == 1 and res2 is None and self.fwd1
-        x_amax = self._operand_bound(c) if early else None
-        f1 = bool(early and self.use_f16x3 and ((self.training and normed) or x_amax is not None) and
-                  self.lib.dsnt_conv1x1_fwd_ok(C.byref(g)))
-        f1_shr = self._share(f1)
-        # the stem's space-to-depth convolution (4x4, 16 -> 64 channels, a raw operand): the halo kernel of csrc/stem4.hip
-        s4 = bool(can16 and self.use_f16x3 and self.stem4 and not normed and c.res1 is None and res2 is None and
-                  self.lib.dsnt_stem4_fwd_ok(C.byref(g)))
-        if want_stats and self.training:
-            bm = 128 if use6 else self.lib.dsnt_conv_fwd_bm(C.byref(g))
-            tiles = (self.lib.dsnt_conv1x1_fwd_stats_rows(C.byref(g), f1_shr) if f1 else
-                     self.lib.dsnt_stem4_fwd_stats_rows(C.byref(g)) if s4 else (y.M + bm - 1) // bm)
-            part = self.empty(tiles, 2, p.Cout)
-            y.stats = (part, tiles)
-        if use6 and self.use_f16x3:
-            # the large-tile kernels can leave max|y| behind: a later consumer of the raw y claims it (operand_amax)
-            y.amax_tail = tail = BnTail()
-        r1 = c.res1.buf if c.res1 is not None else None
-        r2 = res2.buf if res2 is not None else None
-        if self.use_f16x3 and self.training and normed:
-            self.bounds.f16_bn_bound(src)       # also for the weight gradient of convs whose forward is not fp16x3
-        # fp16x3 needs a bound of the A operand: train-mode BatchNorm parameters, or the producer's max|x| for a raw x
-        if can16 and not early:
-            x_amax = self._operand_bound(c)
-        c.x_amax = x_amax
-        use16 = c.use16 = can16 and self.use_f16x3 and ((self.training and normed) or x_amax is not None)
-        if normed and (use16 or use6):
-            self.materialize(src)
-        if use16:
-            st = self.stream_ok(p, g, y.M, res2)
-            self.bounds.f16_weights(p, stream=st)
-            ab = self.bounds.f16_bn_bound(src) if (normed and self.training) else x_amax
-            if f1:
-                e = self.f('dsnt_conv1x1_fwd_f16x3', x.buf, p.wq16, p.wq_stride, p.wb, ab, p.b, y.buf, sc, sh, relu | f1_shr, r1,
-                           part, g, tail)
-            elif s4:
-                e = self.f('dsnt_stem4_fwd_f16x3', x.buf, p.wq16, p.wq_stride, p.wb, ab, p.b, y.buf, part, g, tail)
-            else:
-                e = self.f('dsnt_conv_fwd_f16x3_stream' if st else 'dsnt_conv_fwd_f16x3_ex', x.buf, p.wq16, p.wq_stride, p.wb, ab,
-                           p.b, y.buf, sc, sh, relu | self._share(st or p.R == 1), r1, r2, part, g, None, tail)
-            self.f16_uses.append((e, dict(kind='fwd', name=c.name, x=x.buf, sc=sc, sh=sh, relu=relu, a_bound=ab,
-                                          w=p.w, w_bound=p.wb)))
-        elif use6:
-            self.f('dsnt_conv_fwd_bf16x6_ex', x.buf, p.wq, p.wq_stride, p.b, y.buf, sc, sh, relu, r1, r2, part, g,
-                   None, tail)
-        elif normed and src.pending is not None and self.lib.dsnt_conv_fwd_pro_ok(C.byref(g), src.pending[1], src.bn.C):
-            # the BatchNorm of this operand has few statistics tiles: finalised in this launch's prologue
-            spart, stiles = src.pending
-            src.pending = None
-            bn = src.bn
-            pro = BnPrologue(_lib.ptr(spart), stiles, bn.C, x.M, _lib.ptr(bn.gamma), _lib.ptr(bn.beta), _lib.ptr(bn.rmean),
-                             _lib.ptr(bn.rvar), bn.momentum, bn.eps, _lib.ptr(src.mean), _lib.ptr(src.invstd),
-                             _lib.ptr(src.scale), _lib.ptr(src.shift))
-            self._keep.extend((spart, src.mean, src.invstd, src.scale, src.shift))
-            self.f('dsnt_conv_fwd_pro', x.buf, p.w, p.b, y.buf, pro, relu, r1, r2, part, g, tail)
-        else:
-            if normed:
-                self.materialize(src)
-            self.f('dsnt_conv_fwd_ex', x.buf, p.w, p.b, y.buf, sc, sh, relu, r1, r2, part, g, None, tail)
-
-    def _conv_backward_plan(self, c):
-        """Decided while the forward is traced: c's slot among the re-packed data-gradient weights, and whether its backward can take
-        over the BatchNorm backward of its consumer (`Act.fold_ok`: that BatchNorm's backward, emitted first, leaves its apply pending)."""
-        x, y, p, g = c.x, c.y, c.p, c.g
-        c.slot = c.slot_k = None
-        if c.need_input_grad and self.param_arena is not None:
-            c.slot, c.slot_k = self.bounds.dgrad_slot(p)
-        c.bucket = self.cur_bucket
-        # the whole backward of this convolution as ONE launch (csrc/bwd1.hip): 1x1 behind a train-mode BatchNorm, both
-        # operand bounds known on the device
-        one_pass = self.bwd1 and self.use_f16x3 and self.defer_reduce and c.slot is not None
-        c.fuse1 = bool(one_pass and (c.normed or c.x_amax is not None) and p.R == 1 and p.S == 1 and p.post_reduce is None and
-                       self.lib.dsnt_conv1x1_bwd_ok(C.byref(g)))
-        # ... and without residual inputs (whose gradient IS dL/dy) it can also take over the BatchNorm backward of its consumer
-        plain = c.normed and c.res1 is None and c.res2 is None
-        # the geometry of the stride-1 data gradient: decided here, read again by `_conv_dgrad_operands`
-        c.gd = None
-        if p.stride == 1:
-            c.gd = ConvGeom(x.N, g.Ho, g.Wo, p.Cout, x.H, x.W, p.Cin, p.R, p.S, 1, p.dil * (p.R - 1) - p.pad, p.dil)
-        # the same for a 3x3 convolution on the persistent fp16x3 kernel (conv2 of a Bottleneck: bn3's backward rides in the operand
-        # load of conv2's data gradient, csrc/conv3s.hip MODE 4), from DSNT_X_FOLD3_ROWS output rows — if the data gradient of
-        # THAT geometry takes the fp16x3 stream kernel: a geometry it refuses is decided HERE, while the consumer BatchNorm can
-        # still be told to apply by itself
-        c.fold3_ok = bool(self.fold3 and one_pass and plain and self.training and p.R == 3 and p.S == 3 and c.gd is not None and
-                          c.use16 and y.M >= self.fold3_rows and self._use6(c.gd) and self.stream_ok(p, c.gd, x.M, None))
-        y.fold_ok = bool(c.fuse1 and plain) or c.fold3_ok
-
-    def _conv_backward(self, c):
-        """Emit c's backward: the one-launch 1x1 form, or weight gradient and data gradient; then the residual inputs' gradients."""
-        y = c.y
-        gy, ap = y.grad, y.pending_apply
-        fused = c.fuse1 and self.bounds.dgrad_planes16 is not None
-        fold3 = bool(c.fold3_ok and ap is not None and gy is None and self.bounds.dgrad_planes16 is not None and c.need_input_grad and
-                     ap['bound'] is not None)
-        if ap is not None and (not fused or gy is not None) and not fold3:
-            self.materialize_apply(y)
-            ap, gy = None, y.grad
-        assert gy is not None or ap is not None, 'no gradient reached conv output ' + c.name
-        if fused and ap is None and y.grad_amax is None:
-            fused = False
-        wl, defer_res = self.lane, False
-        if fused:
-            self._conv_bwd_fused1(c, ap, gy)
-        elif fold3:
-            # the BatchNorm backward of the layer behind a 3x3 convolution, left pending by that layer's own backward
-            # (`fold_ok`), rides in this convolution's data gradient (csrc/conv3s.hip MODE 4): the launch forms dL/dy from
-            # (dz, y) while it stages its operand and writes it out for the weight gradient, which therefore comes SECOND
-            gy = y._grad = self.empty(y.N, y.H, y.W, y.C)
-            y.grad_amax, y.pending_apply = ap['bound'], None
-            self._conv_dgrad(c, gy, ap)
-            wl, defer_res = self._conv_wgrad(c, gy)
-        else:
-            wl, defer_res = self._conv_wgrad(c, gy)
-            self._conv_dgrad(c, gy, None)
-        self._conv_residual_grads(c, gy, wl, defer_res)
-
-    def _conv_bwd_fused1(self, c, ap, gy):
-        """The one-launch backward of a 1x1 convolution (dsnt_conv1x1_bwd_f16x3).  ap: the pending BatchNorm backward of c's
-        consumer, applied in the operand load (else dL/dy = gy is read as it is)."""
-        src, x, y, p, g, name = c.src, c.x, c.y, c.p, c.g, 'dsnt_conv1x1_bwd_f16x3'
-        nw = p.w.numel()
-        shr = self._share()
-        nsp = self.lib.dsnt_conv1x1_bwd_splits(C.byref(g), shr)
-        ws = self.wgrads.slab(p, self.lib.dsnt_conv1x1_bwd_ws_floats(C.byref(g), shr), nsp)
-        wd, wq16, wbd = self.bounds.dgrad_f16(c.slot, c.slot_k, nw)
-        total = self.bounds.dgrad_total
-        if ap is not None:
-            aps, applied = self._bn_apply(y, ap)
-            dy, gb = ap['dz'], ap['bound']
-            y.pending_apply = None
-            grad = dict(g_apply=applied, g_bound=gb)
-        else:
-            aps, dy, gb = None, gy, y.grad_amax
-            grad = dict(g=dy, g_bound=gb)
-        if c.normed:
-            ab = self.bounds.f16_bn_bound_bwd(src)
-            # (the BatchNorm in front of THIS convolution may in turn be left to the 1x1 convolution before it)
-            fold = self.fold_ok(src)
-            dz = self._dz_buffer(x, fold)
-            dz_amax = self.bounds.amax_slot() if fold else None
-            part = self.scratch('bnpart', nsp * 2 * x.C).view(-1)
-            e = self.b(name, self._bn_epilogue(x, src), dy, aps, wq16, total, wbd, ab, gb, dz, part, ws, dz_amax, shr, g)
-        else:
-            # no BatchNorm in front of it (projection shortcuts, the `fc` convolutions): dL/dx itself is written, or
-            # added to what x's gradient holds already
-            ab = c.x_amax
-            buf, acc = self.grad_target(x, amax=True)
-            e = self.b(name, self._bn_epilogue(x, None), dy, None, wq16, total, wbd, ab, gb, buf, None, ws,
-                       x.grad_amax, shr | acc, g)
-        # (the tensors the launch names inside a struct: `emit` counts the plain arguments)
-        self.bwd.count(name, 4 * (x.buf.numel() + (y.buf.numel() if ap is not None else 0)))
-        u = dict(kind='bwd1', name=c.name, x=x.buf, sc=c.sc, sh=c.sh, relu=c.relu, a_bound=ab, w=wd, w_bound=wbd)
-        u.update(grad)
-        self.f16_uses.append((e, u))
-        if c.normed:
-            self._norm_backward(src, dz, reduced=(part, nsp), finalised=False, dz_amax=dz_amax)
-
-    def _conv_wgrad(self, c, gy):
-        """Parameter gradients of c (flat arena, overwritten every step).  Returns (the lane they run on, whether dL/dy stays
-        intact for them as the `base` of the residual inputs' gradients)."""
-        p, g = c.p, c.g
-        cur = self.lane
-        w6 = self.use_bf16x6 and bool(self.lib.dsnt_conv_wgrad_bf16x6_ok(C.byref(g)))
-        defer_res = False
-        with self.wgrads.placed(c, gy) as (wl, share):
-            if self.defer_reduce:
-                defer_res = self._conv_wgrad_slab(c, gy, share, w6, wl == cur)
-            else:
-                ws = self.scratch('wgrad', self.lib.dsnt_conv_wgrad_ws_floats(C.byref(g)))
-                self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', c.x.buf, c.sc, c.sh, c.relu, gy, ws, p.gw, p.gb, 0, g)
-                if p.post_reduce is not None:      # the stem's space-to-depth gradient -> the parameter's 7x7 layout
-                    self.b(p.post_reduce[0], *p.post_reduce[1])
-        return wl, defer_res
-
-    def _conv_wgrad_slab(self, c, gy, share, w6, on_chain):
-        """c's weight gradient into a slab of its own that the bucket's one reduction launch sums (`WgradQueue.flush`): a launch here,
-        or — low-resolution convolutions — a descriptor for the bucket's grouped launch.  Returns `defer_res`."""
-        x, y, p, g, normed, sc, sh, relu = c.x, c.y, c.p, c.g, c.normed, c.sc, c.sh, c.relu
-        # deferred to the bucket's grouped launch: x, gy and the BN vectors are written once per
-        # step and gy is not donated onwards (no residual inputs), so they are intact at the flush
-        # (... nor shared with an activation whose gradient is accumulated into later: `share_grads`)
-        # (a RAW operand — conv1 of a torchvision BasicBlock, resnet.py — rides with the identity prologue: scale 1, shift 0)
-        groupable = (w6 and (normed or self.share_grads) and on_chain and not y.grad_shared and
-                     0 < g.N * g.Ho * g.Wo <= self.group_rows)
-        # ... or, WITH residual inputs (conv3 of the low-resolution Bottlenecks): dL/dy is not donated to them but
-        # handed over as the `base` their own gradient continues out of place, and so stays intact as well
-        residuals = [r for r in (c.res1, c.res2) if r is not None]
-        defer_res = bool(groupable and residuals and self.share_grads and self.defer_res and all(r.untouched for r in residuals))
-        grouped = groupable and (not residuals or defer_res)
-        # fp16x3: both operand bounds exist (A: train-mode BN parameters, dY: one bn-backward apply wrote it)
-        w16 = w6 and self.use_f16x3 and (normed or c.x_amax is not None) and y.grad_amax is not None
-        ab = (self.bounds.f16_bn_bound_bwd(c.src) if normed else c.x_amax) if w16 else None
-        if w16 and not grouped:
-            # dsnt_conv_wgrad_f16x3 cuts the pixels of a 3x3 convolution into its own slabs (halo kernel)
-            nws = self.lib.dsnt_conv_wgrad_f16x3_ws_floats(C.byref(g), share)
-            splits = self.lib.dsnt_conv_wgrad_f16x3_splits(C.byref(g), share)
-        else:
-            nws, splits = self.lib.dsnt_conv_wgrad_ws_floats(C.byref(g)), self.lib.dsnt_conv_wgrad_splits(C.byref(g))
-        ws = self.wgrads.slab(p, nws, splits)
-        use = dict(kind='wgrad', name=c.name, x=x.buf, sc=sc, sh=sh, relu=relu, a_bound=ab, g=gy, g_bound=y.grad_amax)
-        if grouped:
-            desc = C.create_string_buffer(self.lib.dsnt_conv_wgrad_desc_bytes())
-            gsc, gsh = (sc, sh) if normed else self.identity_bn(x.C)
-            if w16:
-                nblk = self.lib.dsnt_conv_wgrad_desc_f16x3(_lib.ptr(x.buf), _lib.ptr(gsc), _lib.ptr(gsh), relu, _lib.ptr(gy),
-                                                           _lib.ptr(ws), _lib.ptr(ab), _lib.ptr(y.grad_amax), C.byref(g), desc)
-            else:
-                nblk = self.lib.dsnt_conv_wgrad_desc(_lib.ptr(x.buf), _lib.ptr(gsc), _lib.ptr(gsh), relu, _lib.ptr(gy),
-                                                     _lib.ptr(ws), C.byref(g), desc)
-            if nblk <= 0:
-                raise RuntimeError('dsnt_conv_wgrad_desc failed: %s' % self.lib.dsnt_last_error().decode())
-            self.wgrads.group(desc.raw, nblk, use if w16 else None)
-        elif w16:
-            e = self.b('dsnt_conv_wgrad_f16x3', x.buf, sc, sh, relu, gy, ws, None, None, share, ab, y.grad_amax, g)
-            self.f16_uses.append((e, use))
-        else:
-            self.b('dsnt_conv_wgrad_bf16x6' if w6 else 'dsnt_conv_wgrad', x.buf, sc, sh, relu, gy, ws, None, None,
-                   share if w6 else 0, g)
-        return defer_res
-
-    def _conv_dgrad_operands(self, c, gy):
-        """What c's data gradient launches on: the geometry (`c.gd`, or — a strided convolution the phase kernel of csrc/dgrad_up.hip
-        refuses — the stride-1 one over a zero-stuffed dL/dy) and the re-packed weights in the precision the launch takes."""
-        x, p, g, bd = c.x, c.p, c.g, self.bounds
-        d = _Dgrad()
-        nw = p.w.numel()
-        pad_d = p.dil * (p.R - 1) - p.pad
-        assert pad_d >= 0, 'data gradient needs pad <= dil * (R - 1)'
-        # strided convolution (ResNet stage transitions): dsnt_conv_dgrad_strided computes the pixels of dX phase by phase
-        # straight from dY
-        d.native = p.stride != 1 and c.slot is not None and self.lib.dsnt_conv_dgrad_strided_ok(C.byref(g))
-        d.gd, d.gsrc = c.gd, gy
-        if p.stride != 1 and not d.native:
-            # ... or, for the shapes that kernel refuses: the stride-1 data gradient of dY with zeros stuffed between the pixels
-            Hs, Ws = x.H + 2 * p.pad - p.dil * (p.R - 1), x.W + 2 * p.pad - p.dil * (p.S - 1)
-            d.gsrc = self.scratch('stuffed', x.N * Hs * Ws * p.Cout).view(-1)[:x.N * Hs * Ws * p.Cout]
-            self.b('dsnt_zero_insert', gy, d.gsrc, x.N, g.Ho, g.Wo, p.Cout, Hs, Ws, p.stride)
-            d.gd = ConvGeom(x.N, Hs, Ws, p.Cout, x.H, x.W, p.Cin, p.R, p.S, 1, pad_d, p.dil)
-        d.wq = d.wq_stride = d.wq16 = d.wbd = d.d_stream = None
-        if c.slot is not None:
-            d.wd = bd.dgrad_f32[c.slot:c.slot + nw]
-            d.wq, d.wq_stride = bd.dgrad_planes[c.slot:c.slot + nw], bd.dgrad_total
-            d.d6 = d.gd is not None and self._use6(d.gd)
-        else:       # stand-alone use without a parameter arena
-            d.wd = self.scratch('wdgrad', nw)
-            self.b('dsnt_conv_pack_dgrad', p.w, d.wd, p.Cout, p.R, p.S, p.Cin)
-            d.d6 = self._use6(d.gd) and nw % 8 == 0
-            if d.d6:
-                d.wq, d.wq_stride = self.scratch('wdgrad6', 3 * nw, torch.bfloat16, 8), nw
-                self.b('dsnt_split_bf16x3', d.wd, d.wq, nw)
-        d.g_amax = c.y.grad_amax if (self.use_f16x3 and p.stride == 1) else None
-        d.d16 = d.d6 and d.g_amax is not None and c.slot is not None and self.bounds.dgrad_planes16 is not None
-        if d.d16:
-            # (the data gradient's filter is [Cin][3][3][Cout]: its "Cout" is this convolution's Cin)
-            d.d_stream = self.stream_ok(p, d.gd, x.M, None)
-            _, d.wq16, d.wbd = bd.dgrad_f16(c.slot, c.slot_k, nw, (p.Cin, p.Cout) if d.d_stream else (0, 0))
-        return d
-
-    def _conv_dgrad_launch(self, c, d, out, res, part=None, bnb=None, tail=None):
-        """out = data gradient of c [+ res], with the BatchNorm-backward epilogue bnb (partial sums into part) and the bound tail."""
-        if d.native:
-            self.b('dsnt_conv_dgrad_strided', d.gsrc, d.wd, out, res, part, c.g, bnb, tail)
-        elif d.d16:
-            e = self.b('dsnt_conv_fwd_f16x3_stream' if d.d_stream else 'dsnt_conv_fwd_f16x3_ex', d.gsrc, d.wq16, self.bounds.dgrad_total,
-                       d.wbd, d.g_amax, None, out, None, None, self._share(d.d_stream or c.p.R == 1), res, None, part, d.gd, bnb, tail)
-            self.f16_uses.append((e, dict(kind='dgrad', name=c.name, g=d.gsrc, g_bound=d.g_amax, w=d.wd, w_bound=d.wbd)))
-        elif d.d6:
-            self.b('dsnt_conv_fwd_bf16x6_ex', d.gsrc, d.wq, d.wq_stride, None, out, None, None, 0, res, None, part, d.gd, bnb, tail)
-        else:
-            self.b('dsnt_conv_fwd_ex', d.gsrc, d.wd, None, out, None, None, 0, res, None, part, d.gd, bnb, tail)
-
-    def _conv_dgrad(self, c, gy, ap):
-        """The data gradient of c.  ap: the pending BatchNorm backward of c's consumer, applied in the operand load of the
-        launch, which also writes the dL/dy it forms to gy (`fold3`; None: gy is read)."""
-        if not c.need_input_grad:
-            return
-        src, x, y = c.src, c.x, c.y
-        d = self._conv_dgrad_operands(c, gy)
-        if not c.normed:
-            # (d6: the large-tile kernels; their epilogue can leave max|written gradient| as the next bound)
-            buf, acc, base = self.grad_target_base(x, amax=bool(d.d6 or d.native))      # (base: the residual operand)
-            tl = None
-            if x.grad_amax is not None:
-                tl = BnTail()
-                tl.amax = x.grad_amax.data_ptr()
-            self._conv_dgrad_launch(c, d, buf, base if base is not None else (buf if acc else None), tail=tl)
-            return
-        # the ReLU mask and the two per-channel sums of the BatchNorm backward ride in the
-        # data-gradient epilogue; only finalise + apply remain as separate launches
-        # (fold: the 1x1 convolution that produced x forms this BatchNorm's dx in its own backward — dz then has
-        # to outlive this op's launches, and its maximum is what the bound of dx is made from)
-        fold = not d.native and self.fold_ok(src)
-        dz = self._dz_buffer(x, fold)
-        if d.native:
-            tiles = self.lib.dsnt_conv_dgrad_strided_tiles(C.byref(c.g))
-        else:
-            bm = 128 if d.d6 else self.lib.dsnt_conv_fwd_bm(C.byref(d.gd))
-            tiles = (x.M + bm - 1) // bm
-        part = self.scratch('bnpart', tiles * 2 * x.C).view(-1)
-        bnb = self._bn_epilogue(x, src)
-        tl, dz_amax = None, None
-        if fold:
-            tl, dz_amax = BnTail(), self.bounds.amax_slot()
-            tl.amax = dz_amax.data_ptr()
-        if ap is not None:
-            assert d.d16 and d.d_stream and not d.native
-            name = 'dsnt_conv_dgrad_f16x3_stream_apply'
-            aps, applied = self._bn_apply(y, ap)
-            e = self.b(name, ap['dz'], aps, gy, d.wq16, self.bounds.dgrad_total, d.wbd, ap['bound'], dz, part, self._share(), d.gd, bnb, tl)
-            self.bwd.count(name, 4 * y.buf.numel())
-            self.f16_uses.append((e, dict(kind='dgrad', name=c.name, w=d.wd, w_bound=d.wbd, g_bound=ap['bound'], g_apply=applied)))
-        else:
-            self._conv_dgrad_launch(c, d, dz, None, part, bnb, tl)
-        self._norm_backward(src, dz, reduced=(part, tiles), dz_amax=dz_amax)
-
-    def _conv_residual_grads(self, c, gy, wl, defer_res):
-        """The gradients of c's residual inputs, last: gy is dead after c's own launches (the weight-gradient lane must have read
-        it before anyone accumulates into the donated buffer)."""
-        y = c.y
-        if c.res1 is not None or c.res2 is not None:
-            self.sync_bwd(wl, self.lane)
-        donated = False
-        for r in (c.res1, c.res2):
-            if r is None:
-                continue
-            if defer_res:
-                r.base, r.base_amax = gy, y.grad_amax
-            elif (donated and self.share_grads and r.grad is None and r.pending_apply is None and r.uses == 1 and
-                    not r.gives_away and not r.is_branch):
-                # the buffer went to the first residual input; this one has a single consumer, so its gradient is dL/dy
-                # and nothing else, and its producer only READS it (it gives no buffer away): shared, not copied.  Every
-                # later writer of the buffer comes after that reader in lane order, or waits for the lane that reads
-                # (`WgradQueue.before_write` goes by the buffer)
-                r.grad, r.grad_amax, r.grad_shared = gy, y.grad_amax, True
-            else:
-                donated = self.grad_identity(r, gy, donate=not donated, g_amax=y.grad_amax) or donated
 
     def _f_with_stats(self, name, y, tensors, dims):
         """Emit the element-wise forward launch `name` that writes y — as `name`_stats where the same pass also leaves what y's

@@ -20,7 +20,7 @@ class WgradQueue:
     # ------------------------------------------------------------------ placement
     @contextlib.contextmanager
     def placed(self, c, gy):
-        """Inside the block the tape emits c's weight gradient where it belongs: (lane, DSNT_WGRAD_* share flags)."""
+        """Inside the block c (a `ConvOp`: `ConvOp.wgrad`) emits its weight gradient where it belongs: (lane, DSNT_WGRAD_* share flags)."""
         t, g = self.tape, c.g
         cur = wl = t.lane
         # the weight gradient feeds nothing downstream in backward: run it on its own lane so the data-gradient chain never waits

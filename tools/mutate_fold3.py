@@ -1,9 +1,10 @@
 """Sensitivity of the in-model tests of the folded 3x3 data gradient (tests/test_fused_inmodel_gpu.py, variant `prod`): the same run with
-the folded BatchNorm's vectors mis-wired must FAIL.  python3 tools/mutate_fold3.py none|swap|scale under the variant's environment."""
+the folded BatchNorm's vectors mis-wired must FAIL.  python3 tools/mutate_fold3.py none|swap|scale under the variant's environment.
+It patches `BnBwdApply` in dsnt.convop, the module whose `bn_apply` builds that struct."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'dsnt-pose2d_amd'), os.path.join(ROOT, 'oracle')]
-import dsnt.engine as E
+import dsnt.convop as E
 real = E.BnBwdApply
 which = sys.argv[1]
 class Mutated(real):
