@@ -277,7 +277,7 @@ def conv3_stream_kernel(case, mode):
     (y0, st0, am0), (y1, st1, am1) = outs
     assert not bool(torch.isnan(y1).any()) and not bool(torch.isnan(st1).any())
     scale = y0.abs().max().item()
-    # Cout 128 on 32-pixel-wide patches runs on v_mfma_f32_16x16x32_f16 (csrc/conv3s.hip MF16): an MFMA sums BOTH K-steps of a
+    # Cout 128 on 32-pixel-wide patches runs on v_mfma_f32_16x16x32_f16 (csrc/conv3s_mf.hip): an MFMA sums BOTH K-steps of a
     # pair, so the same products are added in another association — fp32 rounding of the 1152..3456-term sums, not bit identity
     mf16 = Cout == 128 and W % 32 == 0 and H % 4 == 0 and M // 128 > 128
     d01 = (y0 - y1).abs().max().item()

@@ -641,19 +641,6 @@ def test_conv3_stream_kernel_with_the_weight_ring_filled_by_lds_dma_is_reproduci
     assert err16 <= max(4 * err32, 2e-6 * y64.abs().max().item()), (err16, err32)
 
 
-def test_conv3_stream_kernel_16x16x32_form_in_every_mode():
-    """The 16x16x32 MFMA form of csrc/conv3s.hip is the default for the forward launches only; DSNT_X_C3_MF16=7 puts the
-    data-gradient modes (BatchNorm-backward epilogue, folded BatchNorm backward) on it too.  The switch is read once per
-    process, so the stream tests run again in a child with it set."""
-    import subprocess
-    import sys
-    env = dict(os.environ, DSNT_X_C3_MF16='7')
-    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-q', '-x', '-p', 'no:cacheprovider',
-                        '-k', 'test_conv3_stream_kernel[ or folded_in'], env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
-    assert ' passed' in r.stdout and 'failed' not in r.stdout, r.stdout[-500:]
-
-
 @pytest.mark.parametrize('case', [c for c in STREAM_CASES if c[3] in (64, 128)])
 @pytest.mark.parametrize('relu,big_mean', [(1, False), (0, False), (1, True)])
 def test_conv3_stream_data_gradient_with_the_batchnorm_backward_folded_in(case, relu, big_mean):

@@ -41,9 +41,6 @@ VARIANTS = {
     # ... and production's MODE 3 (a separate apply in front of it), no column split
     'prod3': (dict(DSNT_X_C3_SPLIT_TILES='0', DSNT_X_GROUP_ROWS='0', DSNT_X_WGRAD_LANE_ROWS='1', DSNT_OFF='fold3'),
               [('f', 0, MF), ('b', 3, PLAIN), ('b', 3, P16)]),
-    # every mode on the 16x16x32 form
-    'mf': (dict(DSNT_X_FOLD3_ROWS='0', DSNT_X_C3_SPLIT_TILES='0', DSNT_X_C3_MF16='7'), [('f', 0, MF), ('b', 4, MF)]),
-    'mf3': (dict(DSNT_X_C3_SPLIT_TILES='0', DSNT_X_C3_MF16='7', DSNT_OFF='fold3'), [('f', 0, MF), ('b', 3, MF)]),
     # the folded data gradient beside the column split of the other launches
     'fold': (dict(DSNT_X_FOLD3_ROWS='0'), [('f', 0, SP), ('b', 4, PLAIN)]),
 }
@@ -120,9 +117,6 @@ def _check_c3(rep, variant, stacks):
         assert n3 >= 5 * stacks and n4 == 0, cells
     if env.get('DSNT_X_C3_SPLIT_TILES') == '0':
         assert not any(form & SP for (which, mode, form) in cells), cells
-    if env.get('DSNT_X_C3_MF16') == '7':
-        # everything 32 pixels wide is on the 16x16x32 form
-        assert not any(form == PLAIN for (which, mode, form) in cells), cells
 
 
 GOLDENS = {'hg2_128': (2, 2 * 32 * 32), 'hg2_256': (2, 2 * 64 * 64), 'hg8_128': (8, 2 * 32 * 32)}
@@ -130,8 +124,7 @@ GOLDENS = {'hg2_128': (2, 2 * 32 * 32), 'hg2_256': (2, 2 * 64 * 64), 'hg8_128': 
 
 @pytest.mark.parametrize('tag,variant', [('hg2_128', 'onepass'), ('hg2_256', 'onepass'), ('hg8_128', 'onepass'),
                                          ('hg2_128', 'prod'), ('hg2_256', 'prod'), ('hg8_128', 'prod'),
-                                         ('hg2_256', 'prod3'), ('hg2_256', 'mf'), ('hg8_128', 'mf'), ('hg2_256', 'mf3'),
-                                         ('hg2_256', 'fold')])
+                                         ('hg2_256', 'prod3'), ('hg2_256', 'fold')])
 def test_goldens_with_the_production_kernels_forced_onto_the_small_models(tmp_path, tag, variant):
     """The reference's golden vectors (coords of every stack 1e-4, loss, heat-maps, running statistics, gradient norms) with every
     1x1 convolution on the one-pass kernels and the 3x3 convolutions on the forms `variant` names."""
@@ -142,7 +135,7 @@ def test_goldens_with_the_production_kernels_forced_onto_the_small_models(tmp_pa
 
 
 @pytest.mark.parametrize('kind,variant', [('smooth', 'onepass'), ('relu', 'onepass'), ('smooth', 'prod'), ('relu', 'prod'),
-                                          ('smooth', 'prod3'), ('smooth', 'mf'), ('smooth', 'mf3')])
+                                          ('smooth', 'prod3')])
 def test_hg2_every_gradient_vs_oracle_on_the_production_kernels(tmp_path, kind, variant):
     """All 396 gradients of hg2 (batch 4, 128 px) against the oracle — smooth network: 1e-3 per parameter, cosine 1 - 1e-7.
     A wrong coefficient vector, a stale dL/dy handed to the weight gradient or a mis-wired BatchNorm in a folded launch moves
@@ -152,7 +145,7 @@ def test_hg2_every_gradient_vs_oracle_on_the_production_kernels(tmp_path, kind, 
     _check_c3(rep, variant, 2)
 
 
-@pytest.mark.parametrize('variant', ['prod'])        # ('mf' passes too; 25 s of GPU time per variant)
+@pytest.mark.parametrize('variant', ['prod'])        # (25 s of GPU time per variant)
 def test_hg8_every_gradient_vs_oracle_on_the_production_kernels(tmp_path, variant):
     """hg8's 1464 gradients (batch 2, 128 px, smooth network) inside the oracle's own fp32-vs-fp64 envelope
     (tests/test_model_gpu.py::test_hg8_every_gradient_vs_oracle_on_the_smooth_network) with the production forms forced."""

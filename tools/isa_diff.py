@@ -1,5 +1,5 @@
 """Compare the device code of two builds of the library, function by function: python tools/isa_diff.py OLD.so NEW.so
-Every gfx950 code object of each library is unbundled and disassembled; functions are keyed by symbol name across all code
+[--rename OLD_SYMBOL=NEW_SYMBOL ...] (a kernel whose mangled name changed is compared under its new name).  Every gfx950 code object of each library is unbundled and disassembled; functions are keyed by symbol name across all code
 objects (a kernel may move between translation units; a symbol that several objects hold is compared copy by copy).  A
 function is identical when its instruction text (addresses and encodings dropped, cut at the symbol's size so that the padding
 behind a function, zero fill included, does not count) and, for a kernel, its resource metadata agree.  Prints the identical,
@@ -63,7 +63,15 @@ def first_difference(a, b):
 
 
 if __name__ == '__main__':
-    old, new = functions(sys.argv[1]), functions(sys.argv[2])
+    args = sys.argv[1:]
+    renames = {}                                        # --rename OLD=NEW (mangled names): compare OLD's function with NEW's
+    while '--rename' in args:
+        i = args.index('--rename')
+        o, n = args[i + 1].split('=')
+        renames[o] = n
+        del args[i:i + 2]
+    old, new = functions(args[0]), functions(args[1])
+    old = {renames.get(k, k): v for k, v in old.items()}
     both = sorted(set(old) & set(new))
     same = [n for n in both if old[n] == new[n]]
     changed = [n for n in both if old[n] != new[n]]

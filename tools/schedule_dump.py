@@ -36,8 +36,7 @@ MATRIX = ([('%s_b%d' % (b, n), [b, 'train', '%d,3,256,256' % n], {}) for b, n in
            ('hg2_input_grad', ['hg2', 'train', '32,3,256,256', '--input-grad'], {}), ('standalone', ['standalone', 'train', '2,8,16,16'], {})] +
           [('%s_%s' % (b, tag), [b, 'train', '%d,3,256,256' % n], env) for tag, env in SWITCHES for b, n in (('hg2', 32), ('resnet34', 8))] +
           [('hg2_fused_' + tag, ['hg2', 'train', '4,3,128,128'], dict(FUSED, **env)) for tag, env in
-           (('prod', dict(_LANE, DSNT_X_FOLD3_ROWS='0')), ('prod3', dict(_LANE, DSNT_OFF='fold3')),
-            ('mf', dict(DSNT_X_FOLD3_ROWS='0', DSNT_X_C3_SPLIT_TILES='0', DSNT_X_C3_MF16='7')), ('fold', dict(DSNT_X_FOLD3_ROWS='0')))])
+           (('prod', dict(_LANE, DSNT_X_FOLD3_ROWS='0')), ('prod3', dict(_LANE, DSNT_OFF='fold3')), ('fold', dict(DSNT_X_FOLD3_ROWS='0')))])
 
 
 def cpu_ptr(t):
