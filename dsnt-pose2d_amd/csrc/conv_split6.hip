@@ -4,8 +4,7 @@
 #include "conv_epilogue.h"
 #include "gemm1.h"
 #include "conv3s.h"
-#include "wgrad3.h"
-#include "stem4.h"
+#include "wgrad.h"
 #include <string.h>
 #include <stdlib.h>
 
@@ -618,13 +617,7 @@ extern "C" int dsnt_conv_dgrad_f16x3_stream_apply(const float* dz, const dsnt_bn
 // (wgrad1.hip), 0 the generic one.  Negative: the geometry is not supported.
 extern "C" int dsnt_conv_f16x3_route(const dsnt_conv_geom* g, int wgrad) {
     if (!g || conv_check_geom(g, "dsnt_conv_f16x3_route") != 0) return -1;
-    if (wgrad) {
-        if (!dsnt_conv_wgrad_bf16x6_ok(g)) return -1;
-        if (dsnt_stem4_wgrad_slabs(g)) return 1;
-        if (dsnt_wg3_plan(g, 0).ok) return 2;
-        if (dsnt_wg1_plan(g, false).ok) return 3;
-        return 0;
-    }
+    if (wgrad) return dsnt_wgrad_route_kind(g);       // the route of conv_wgrad.hip itself
     if (!dsnt_conv_bf16x6_ok(g)) return -1;
     static const float one = 1.f;
     ConvP p;

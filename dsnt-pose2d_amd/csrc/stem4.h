@@ -1,4 +1,4 @@
-// Internal interface of the stem's weight-gradient kernel (stem4.hip), used by the dispatch in conv_wgrad.hip.
+// Internal interface of the stem's weight-gradient kernel (stem4.hip), used by the dispatch in conv_wgrad.hip (the other kernel units: wgrad.h).
 #pragma once
 #include "common.h"
 

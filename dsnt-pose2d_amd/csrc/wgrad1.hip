@@ -2,7 +2,7 @@
 // convolutions) on the fp16 matrix cores, fp16x3 split:   dW[n][c] = sum over pixels  A[pixel][c] * dY[pixel][n].
 //
 // HBM-bound by a wide margin (128 -> 256 @64x64, batch 32: 201 MB per launch against 8.6 GFLOP), yet the implicit-GEMM
-// kernel (conv_wgrad.hip) runs these launches on the SIMD's issue port: 12 VALU instructions per MFMA, because the MFMA
+// kernel (wgrad_gemm.hip) runs these launches on the SIMD's issue port: 12 VALU instructions per MFMA, because the MFMA
 // contracts over PIXELS while both tensors are channel-major — every element is transformed, split and transposed by
 // VALU work, and a 128 x 128 output tile re-stages its operands for every other tile of the same rows.  Here, with the
 // machinery of the 3x3 halo kernel (wgrad3.hip):
@@ -14,7 +14,7 @@
 //     pipe (three 16-pixel stages of loads in flight per thread) and leaves 40 % of every CU's registers and most of its
 //     LDS to the dependency chain's kernels on the other streams — these launches run beside it (DSNT_WGRAD_SHARE_CHIP).
 // Slabs ws[split][Cout][K] (+ [split][Cout] bias partials) as every other weight-gradient kernel writes them.
-#include "wgrad3.h"
+#include "wgrad.h"
 #include "conv_split.h"
 #include <stdlib.h>
 

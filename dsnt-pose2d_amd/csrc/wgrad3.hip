@@ -3,7 +3,7 @@
 //
 //   dW[n][tap][c] = sum over pixels  A[pixel + tap][c] * dY[pixel][n],   A = relu(bn(x)) (zero outside the image)
 //
-// The implicit-GEMM weight gradient (conv_wgrad.hip) gives each (tap, 128-channel) k-tile its own workgroup: every input
+// The implicit-GEMM weight gradient (wgrad_gemm.hip) gives each (tap, 128-channel) k-tile its own workgroup: every input
 // element is BatchNorm-transformed, split and TRANSPOSED nine times, every dY element nine times too — 12 VALU
 // instructions per MFMA on a kernel whose bound is the SIMD's issue port.  Here a workgroup owns 64 input channels x
 // ALL nine taps x 128 (or 64) output channels for a strip of pixels:
@@ -19,7 +19,7 @@
 //     one is consumed.
 // Eight waves: wave = (channel half kc, 32-column tile nt[, tap group]), 9 (or 5 / 4) accumulator tiles each.
 // Slabs ws[slab][Cout][K] exactly as the other weight-gradient kernels write them (reduced by wgrad_reduce_*).
-#include "wgrad3.h"
+#include "wgrad.h"
 #include "conv_split.h"
 #include <stdlib.h>
 
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(CFG == 2 ? 256 : 512, 2) void wgrad3_kernel(Wg3P p)
     }
 }
 
-static int enabled = -1, min_steps = 0, small_wg = 1;
+static int enabled = -1;
 
 Wg3Plan dsnt_wg3_plan(const dsnt_conv_geom* g, int share) {
     Wg3Plan pl;
@@ -309,12 +309,9 @@ Wg3Plan dsnt_wg3_plan(const dsnt_conv_geom* g, int share) {
     // tuning constants (measured on MI355X, hg2 batch 32): 256 workgroups = one per CU; at least 32 16-pixel steps per
     // workgroup (every workgroup pays a three-row prologue and writes a whole slab); four-wave workgroups for launches
     // that share the chip
-    const long target = 256;
-    if (enabled < 0) {
-        enabled = dsnt_kernel_off("wgrad3") ? 0 : 1;
-        min_steps = 32;
-        small_wg = 1;
-    }
+    constexpr long target = 256;
+    constexpr int min_steps = 32;
+    if (enabled < 0) enabled = dsnt_kernel_off("wgrad3") ? 0 : 1;
     if (!enabled || !g) return pl;
     if (!(g->R == 3 && g->S == 3 && g->stride == 1 && g->pad == 1 && g->dil == 1 && g->Ho == g->H && g->Wo == g->W))
         return pl;
@@ -339,7 +336,7 @@ Wg3Plan dsnt_wg3_plan(const dsnt_conv_geom* g, int share) {
     // the CUs takes less from the dependency chain's kernels beside it (same box, hg2 batch 32: 12.53 -> 12.27 ms/step,
     // 12.09 -> 11.93 on a second one; and half the slab bytes); NOT at the end of backward, where nothing runs beside the
     // stem's weight gradients and their duration is the step's (hg8 batch 16 with every launch narrow: +0.4 ms)
-    long want = (share && small_wg && pl.cfg == 0) ? target / 2 : target;
+    long want = (share && pl.cfg == 0) ? target / 2 : target;
     if (share == 2) want /= 2;
     while (per * (g->H / rps) < want && rps % 2 == 0 && (rps / 2) * (WS / 16) >= min_steps) rps /= 2;
     pl.rps = rps;
@@ -372,7 +369,7 @@ void dsnt_wg3_launch(const Wg3Plan& pl, const float* x, const float* in_scale, c
     p.N = g->N; p.H = g->H; p.W = g->W; p.Cin = g->Cin; p.Cout = g->Cout; p.K = 9 * g->Cin;
     p.strips = pl.strips; p.rps = pl.rps; p.hsplits = pl.hsplits; p.kchunks = pl.kchunks; p.nchunks = pl.nchunks;
     p.nslabs = pl.nslabs;
-    const bool small = share && small_wg && pl.cfg == 0;
+    const bool small = share && pl.cfg == 0;
     if (small) p.kchunks = 2 * pl.kchunks;
 #define WG3_PICK(CFG)                                                   \
     do {                                                                \

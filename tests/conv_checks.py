@@ -207,6 +207,65 @@ def wgrad_1x1_f16x3(case, pro, relu):
                 splits=splits, splits_share=splits_s)
 
 
+def wgrad_reduction_in_the_call(fields, pro):
+    """dsnt_conv_wgrad_f16x3 on a route the two functions above do not reach (fields: the twelve of dsnt_conv_geom; the stem kernel
+    of csrc/stem4.hip, the implicit GEMM of csrc/wgrad_gemm.hip): dw and dbias of the call equal, bit for bit, the table-driven
+    reduction of a slabs-only call, and accumulate bit 0 adds.  Bars: those of the route's own accuracy test (stem 4e-6 / 8e-6 of
+    the gradient's scale, stem_weight_gradient_on_its_own_kernel; otherwise 3e-5 / 6e-5, wgrad_halo_f16x3)."""
+    from dsnt import _lib
+    from dsnt._lib import ptr, call, ConvGeom
+    N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil = fields
+    dev = torch.device('cuda:0')
+    g = ConvGeom(*fields)
+    route = _lib.fn('dsnt_conv_f16x3_route')(C.byref(g), 1)
+    assert route in (0, 1) and (route == 0 or not pro)
+    bar = 4e-6 if route == 1 else 3e-5
+    tag = 'wr' + '_'.join(map(str, fields))
+    x = synthetic.tensor(tag + 'x', (N, Cin, H, W), seed=1)
+    sc = synthetic.tensor(tag + 's', (Cin,), seed=1, kind='uniform').abs() + 0.5
+    sh = synthetic.tensor(tag + 'h', (Cin,), seed=1, scale=0.3)
+    act = F.relu(x * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)) if pro else x
+    gy = synthetic.tensor(tag + 'g', (N, Cout, Ho, Wo), seed=2) * 1e-2
+    ref = torch.nn.grad.conv2d_weight(act.double(), (Cout, Cin, R, S), gy.double(), stride=stride, padding=pad,
+                                      dilation=dil).permute(0, 2, 3, 1)
+    bref = gy.double().sum((0, 2, 3))
+    scale, bscale = ref.abs().max().item(), bref.abs().max().item()
+    if route == 1:
+        bscale = max(bscale, gy.abs().sum().item() * 1e-3)
+    xd, gyd, scd, shd = nhwc(x).to(dev), nhwc(gy).to(dev), sc.to(dev), sh.to(dev)
+    ab, gb = torch.zeros(64, device=dev), torch.zeros(64, device=dev)
+    ab.fill_(act.abs().max().item())
+    call('dsnt_amax', ptr(gyd), gyd.numel(), ptr(gb))
+    K = R * S * Cin
+    nws = _lib.fn('dsnt_conv_wgrad_f16x3_ws_floats')(C.byref(g), 0)
+    splits = _lib.fn('dsnt_conv_wgrad_f16x3_splits')(C.byref(g), 0)
+    assert splits > 0 and nws == splits * Cout * (K + 1)
+    ws, ws2 = torch.full((nws,), float('nan'), device=dev), torch.full((nws,), float('nan'), device=dev)
+    dw, db = torch.empty(Cout, R, S, Cin, device=dev), torch.empty(Cout, device=dev)
+    dw2, db2 = torch.zeros_like(dw), torch.zeros_like(db)
+    args = (ptr(xd), ptr(scd) if pro else None, ptr(shd) if pro else None, 1, ptr(gyd))
+    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws), ptr(dw), ptr(db), 0, ptr(ab), ptr(gb), C.byref(g))
+    assert bool(torch.isfinite(ws).all()), 'a slab element was never written'
+    e = (dw.cpu().double() - ref).abs().max().item()
+    eb = (db.cpu().double() - bref).abs().max().item()
+    print('wgrad_reduction_in_the_call', fields, 'pro=%d' % pro, 'route', route, 'splits', splits, 'err', e, 'scale', scale,
+          'bias err', eb, 'bias scale', bscale)
+    assert e <= bar * scale and eb <= bar * bscale
+    # slabs only + the table-driven reduction: the same bits
+    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws2), None, None, 0, ptr(ab), ptr(gb), C.byref(g))
+    assert torch.equal(ws, ws2)
+    table = torch.tensor([[ws2.data_ptr(), dw2.data_ptr(), db2.data_ptr(), splits, Cout * K, Cout, 0]], dtype=torch.int64).to(dev)
+    call('dsnt_wgrad_reduce_all', ptr(table), 1, (Cout * K // 4 + (Cout + 3) // 4 + 63) // 64)
+    assert torch.equal(dw2, dw) and torch.equal(db2, db)
+    # accumulate (bit 0) adds
+    call('dsnt_conv_wgrad_f16x3', *args, ptr(ws), ptr(dw), ptr(db), 1, ptr(ab), ptr(gb), C.byref(g))
+    e2 = (dw.cpu().double() - 2 * ref).abs().max().item()
+    print('wgrad_reduction_in_the_call', fields, 'accumulate err', e2)
+    assert e2 <= 2 * bar * scale
+    assert (db.cpu().double() - 2 * bref).abs().max().item() <= 2 * bar * bscale
+    return dict(err=e, err_accumulate=e2, scale=scale, bias_err=eb, splits=splits, route=route)
+
+
 def conv3_stream_kernel(case, mode):
     """dsnt_conv_fwd_f16x3_stream (csrc/conv3s.hip) against dsnt_conv_fwd_f16x3_ex on the same operands and against torch fp64;
     mode: plain, pro, pro_res, res, bnb, pro_norelu, bnb_norelu."""

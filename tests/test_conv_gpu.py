@@ -525,6 +525,18 @@ def test_wgrad_1x1_f16x3(case, pro, relu):
     K.wgrad_1x1_f16x3(case, pro, relu)
 
 
+@pytest.mark.parametrize('fields,pro', [
+    ((1, 5, 33, 16, 4, 32, 64, 4, 4, 1, 1, 1), False),      # the stem kernel (csrc/stem4.hip): one tile, one slab
+    ((1, 8, 8, 8, 8, 8, 8, 3, 3, 1, 1, 1), True),           # the implicit GEMM (csrc/wgrad_gemm.hip), one masked tile
+    ((1, 8, 8, 8, 8, 8, 8, 3, 3, 1, 1, 1), False),
+])
+def test_wgrad_f16x3_reduction_in_the_call_on_the_other_routes(fields, pro):
+    """The two routes of dsnt_conv_wgrad_f16x3 that the halo and 1x1 tests above do not reach, held to the same property: dw and
+    dbias of the call are, bit for bit, the table-driven reduction (dsnt_wgrad_reduce_all) of a slabs-only call, and accumulate
+    bit 0 gives twice the gradient."""
+    K.wgrad_reduction_in_the_call(fields, pro)
+
+
 def test_f16x3_preparation_launches():
     """The per-step table-driven launches of the fp16x3 path: weight planes + bounds of several tensors at once equal
     the single-tensor entry points; the BatchNorm bound is max_c(|gamma_c| sqrt(M) + |beta_c|) in all 64 slots; the

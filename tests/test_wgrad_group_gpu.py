@@ -2,7 +2,7 @@
 reduction (dsnt_wgrad_reduce_all) and the table-driven eval-mode BatchNorm vectors (dsnt_bn_eval_prep), through the C ABI.
 
 Every weight gradient of the 16x16 ... 4x4 hourglass levels runs through ONE dsnt_conv_wgrad_group launch over a table of
-dsnt_conv_wgrad_desc_f16x3 descriptors (convop.py ConvOp.wgrad_slab): wgrad6_body<true, true> of csrc/conv_wgrad.hip, picked per
+dsnt_conv_wgrad_desc_f16x3 descriptors (convop.py ConvOp.wgrad_slab): wgrad6_body<true, true> of csrc/wgrad_gemm.hip, picked per
 workgroup from the descriptor's a_bound.  Here that launch is held to an fp64 reference case by case (tests/wgrad_group_ref.py:
 single, odd and short steps, maps smaller than a step, image boundaries that move inside the step, masked tiles), its slabs are
 checked for bounds, for independence of the grid's padding and of the table order, and against the per-convolution launches of

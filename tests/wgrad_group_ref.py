@@ -1,6 +1,6 @@
 """Cases, the restated slab plan and the CPU references of tests/test_wgrad_group_gpu.py (the grouped weight-gradient launch).
 
-Nothing here touches the device: the plan is csrc/conv_wgrad.hip `wgrad_plan` as read, the references are
+Nothing here touches the device: the plan is csrc/wgrad_gemm.hip `dsnt_wgg_plan` as read, the references are
 torch.nn.grad.conv2d_weight on the CPU in float64 and float32 over the BatchNorm+ReLU'd operand."""
 import numpy as np
 import torch
@@ -53,7 +53,7 @@ def out_hw(case):
 
 
 def plan(case):
-    """csrc/conv_wgrad.hip wgrad_plan: (ktiles, ntiles, splits, rows_per_split)."""
+    """csrc/wgrad_gemm.hip dsnt_wgg_plan: (ktiles, ntiles, splits, rows_per_split)."""
     N, H, W, Cin, Cout, k, stride, pad, dil = case
     Ho, Wo = out_hw(case)
     M, K = N * Ho * Wo, k * k * Cin
