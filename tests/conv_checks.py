@@ -1,7 +1,8 @@
 """The checking code of the kernel-level convolution tests (tests/test_conv_gpu.py, tests/test_bwd1_gpu.py), shared with
 tests/test_plan_edges_gpu.py: one function per kernel family, each the whole comparison of that family against fp64 through the
 C ABI — operands, launches, every assertion — for one case.  A function returns the figures it measured (maximum errors next to
-the scales its bars are relative to), so that a caller can report them; the bars themselves live here and nowhere else."""
+the scales its bars are relative to), so that a caller can report them; the bars themselves live here and nowhere else.
+At the end: conv_f32_edge, the comparison of tests/test_conv_f32_edges_gpu.py for the fp32 family of csrc/conv_f32.hip."""
 import ctypes as C
 
 import torch
@@ -750,3 +751,275 @@ def stem_weight_gradient_on_its_own_kernel(N, Ho, Wo):
     sc, sh = torch.ones(16, device=dev), torch.zeros(16, device=dev)
     assert wg(ptr(x), ptr(sc), ptr(sh), 0, ptr(gy), ptr(ws), None, None, 0, ptr(ab), ptr(gb), C.byref(g), st) != 0
     return dict(err=e, scale=ref.abs().max().item(), splits=splits)
+
+
+# ---------------------------------------------------------------- the fp32 family at its plan edges (csrc/conv_f32.hip, conv_epilogue.h)
+
+SENT = -777.0               # what output buffers hold before a launch: no output of these cases comes near it
+FRONT = 64                  # sentinel floats in front of a buffer (256 bytes: the buffer keeps its 16-byte alignment)
+F32_BAR = 2e-5              # outputs, of max |reference|: the project's fp32 bar (tests/test_conv_gpu.py)
+SUM_BAR = 1e-5              # per-tile column sums, of the column's sum of absolute values (test_native_strided_data_gradient)
+ULP = 2.0 ** -23            # amax_bn: one fmaf on the stored value, rounded once (2^-24 of the result), against fp64
+CONV_F32_MODES = ('fwd', 'pro_relu', 'pro_norelu', 'inplace', 'bnb_relu', 'bnb_norelu')
+
+
+class Guarded:
+    """rows x cols floats on the device, a block of sentinels in front and `guard_rows` rows of them behind; the payload starts
+    as sentinels too (or as `init`).  The kernels address y and the statistics with a pitch of exactly Cout, so a column past
+    Cout of row m IS column 0.. of row m + 1: an overrun shows as a wrong value there, and in the rows behind for the last row."""
+
+    def __init__(self, rows, cols, dev, init=None, guard_rows=128):
+        self.n = rows * cols
+        self.buf = torch.full((FRONT + self.n + guard_rows * cols,), SENT, device=dev)
+        self.t = self.buf[FRONT:FRONT + self.n].view(rows, cols)
+        if init is not None:
+            self.t.copy_(init)
+
+    def intact(self):
+        return bool((self.buf[:FRONT] == SENT).all()) and bool((self.buf[FRONT + self.n:] == SENT).all())
+
+
+def _f32_same(a, b):
+    """Two launches' outputs (Guarded buffers, guards included, and bound slots) hold the same bits."""
+    return all(torch.equal(p.buf if isinstance(p, Guarded) else p, q.buf if isinstance(q, Guarded) else q) for p, q in zip(a, b))
+
+
+_f32_cache = {}
+
+
+def _f32_operands(case):
+    """Host operands of one case and its fp64 convolutions (computed once per case, shared by its modes, never written to)."""
+    if case not in _f32_cache:
+        _f32_cache.clear()              # the cases come in order: one at a time is enough
+        N, H, W, Cin, Cout, k, stride, pad, dil = case
+        tag = 'f32e' + '_'.join(map(str, case))
+        g = geom(N, H, W, Cin, Cout, k, k, stride, pad, dil)
+        M = N * g.Ho * g.Wo
+        o = dict(g=g, M=M)
+        o['x'] = synthetic.tensor(tag + 'x', (N, Cin, H, W), seed=1)
+        o['w'] = synthetic.tensor(tag + 'w', (Cout, Cin, k, k), seed=1, scale=(2.0 / (Cin * k * k)) ** 0.5)
+        o['b'] = synthetic.tensor(tag + 'b', (Cout,), seed=1, scale=0.1)
+        o['sc'] = synthetic.tensor(tag + 's', (Cin,), seed=1, kind='uniform').abs() + 0.5
+        o['sh'] = synthetic.tensor(tag + 'h', (Cin,), seed=1, scale=0.3)
+        o['r1'] = synthetic.tensor(tag + 'r1', (M, Cout), seed=2)
+        o['r2'] = synthetic.tensor(tag + 'r2', (M, Cout), seed=3)
+        o['asc'] = synthetic.tensor(tag + 'as', (Cout,), seed=4, kind='uniform') + 0.25        # both signs
+        o['ash'] = synthetic.tensor(tag + 'ah', (Cout,), seed=4, scale=0.5)
+        o['conv'] = {}
+        _f32_cache[case] = o
+    return _f32_cache[case]
+
+
+def _f32_conv64(o, case, sc=None, sh=None, relu=0):
+    """fp64 F.conv2d on relu?(x * sc + sh) or on x, as [M][Cout]; the three forms on the case's own vectors are kept."""
+    N, H, W, Cin, Cout, k, stride, pad, dil = case
+    key = None if sc is None else relu if sc is o['sc'] else -1
+    if key in o['conv']:
+        return o['conv'][key]
+    a = o['x'].double()
+    if sc is not None:
+        a = a * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1)
+        a = F.relu(a) if relu else a
+    y = F.conv2d(a, o['w'].double(), None, stride=stride, padding=pad, dilation=dil).permute(0, 2, 3, 1).reshape(o['M'], Cout)
+    if key != -1:
+        o['conv'][key] = y
+    return y
+
+
+def _f32_tile_sums(got, weight, bm, tiles):
+    """fp64 per-tile column sums of got * weight and of |got * weight| over tiles of bm rows (the last one short)."""
+    M, Cc = got.shape
+    v = torch.zeros(tiles * bm, Cc, dtype=torch.float64)
+    v[:M] = got * weight
+    v = v.view(tiles, bm, Cc)
+    return v.sum(1), v.abs().sum(1)
+
+
+def _f32_check_stats(st, got, second, bm, tiles, what):
+    """The statistics rows [tiles][2][Cout] of a launch against fp64 sums over the launch's OWN output `got`: row 0 the column
+    sums, row 1 the sums of got * second; every element overwritten, nothing behind them touched."""
+    assert st.intact(), '%s: statistics written outside [tiles][2][Cout]' % what
+    s = st.t.cpu().double().view(tiles, 2, -1)
+    assert bool((s != SENT).all()), '%s: %d statistics elements never written' % (what, int((s == SENT).sum()))
+    worst = 0.0
+    for row, wgt in ((0, torch.ones_like(got)), (1, second)):
+        want, mag = _f32_tile_sums(got, wgt, bm, tiles)
+        err = (s[:, row] - want).abs()
+        bad = ~(err <= SUM_BAR * mag)
+        assert not bool(bad.any()), '%s: statistics row %d: %d elements off, worst %.3e of the column\'s sum of absolute values' % (
+            what, row, int(bad.sum()), float((err / mag.clamp_min(1e-300))[bad].max()))
+        worst = max(worst, float((err / mag.clamp_min(1e-300)).max()))
+    return worst
+
+
+def conv_f32_edge(case, mode):
+    """One case of tests/plan_edge_cases.py CONV_F32 in one mode, against torch fp64 on the CPU, through the C ABI.  Every launch
+    writes into sentinel-filled buffers with guards and runs twice into fresh ones (the same bits).  Modes:
+      fwd / pro_relu / pro_norelu   bias, res1, res2 and statistics; without / with in_scale, in_shift (in_relu 1 / 0).  Through
+                    dsnt_conv_fwd (where the case is small enough: the K-split kernel) and through dsnt_conv_fwd_ex with a
+                    dsnt_out_bounds (always a tile kernel), amax_relu 1 and 0: y against the reference; amax == max |y| as floats;
+                    amax_bn against relu?(y s + h) of the device's y; statistics against fp64 sums of the device's y.  With a
+                    prologue, where dsnt_conv_fwd_pro_ok accepts the case: dsnt_conv_fwd_pro on dsnt_bn_stats partials leaves the
+                    vectors and running statistics of dsnt_bn_finalize and the bits of the launch on those vectors.
+      inplace       res1 == y (the accumulating data gradient): no bias, no second residual.
+      bnb_relu / bnb_norelu   the case as a data-gradient launch with the BatchNorm-backward epilogue (dsnt_conv_fwd_ex, without
+                    and with amax): dz against the reference, zero exactly where the fp64 pre-activation is <= 0, the two sums
+                    against fp64 sums over the device's dz."""
+    from dsnt import _lib
+    from dsnt._lib import ptr, call, BnTail, BnPrologue, BnBwdEpilogue
+    assert mode in CONV_F32_MODES
+    N, H, W, Cin, Cout, k, stride, pad, dil = case
+    dev = torch.device('cuda:0')
+    o = _f32_operands(case)
+    g, M = o['g'], o['M']
+    bm = _lib.fn('dsnt_conv_fwd_bm')(C.byref(g))
+    tiles = (M + bm - 1) // bm
+    xd = nhwc(o['x']).to(dev)
+    wd = o['w'].permute(0, 2, 3, 1).contiguous().to(dev)          # OHWI
+    figs = {}
+
+    def bounds(relu, am, amb, ascd, ashd):
+        t = BnTail()
+        t.amax = am.data_ptr()
+        if amb is not None:
+            t.amax_bn, t.amax_scale, t.amax_shift, t.amax_relu = amb.data_ptr(), ascd.data_ptr(), ashd.data_ptr(), relu
+        return t
+
+    if mode.startswith('bnb'):
+        relu = 1 if mode == 'bnb_relu' else 0
+        tag = 'f32e' + '_'.join(map(str, case))
+        xin = synthetic.tensor(tag + 'xin', (M, Cout), seed=5)
+        bsc = synthetic.tensor(tag + 'bs', (Cout,), seed=6, kind='uniform')
+        bsc = torch.sign(bsc) * (bsc.abs() + 0.5)                              # both signs, away from zero
+        bsh = synthetic.tensor(tag + 'bh', (Cout,), seed=7, scale=0.3)
+        bmu = synthetic.tensor(tag + 'bm', (Cout,), seed=8, scale=0.2)
+        bis = synthetic.tensor(tag + 'bi', (Cout,), seed=9, kind='uniform').abs() + 0.5
+        z = xin.double() * bsc.double() + bsh.double()
+        near = z.abs() < 1e-3           # two fp32 evaluations may disagree about a pre-activation at the kink: move those away
+        xin = (xin.double() + torch.where(near, torch.sign(z) * torch.sign(bsc.double()) * 4e-3 / bsc.double().abs(),
+                                          torch.zeros_like(z))).float()
+        z = xin.double() * bsc.double() + bsh.double()
+        assert float(z.abs().min()) >= 1e-3
+        conv = _f32_conv64(o, case)
+        ref = torch.where(z > 0, conv, torch.zeros_like(conv)) if relu else conv
+        scale = float(ref.abs().max())
+        xhat = (xin.double() - bmu.double()) * bis.double()
+        xind, vecs = xin.to(dev), [t.to(dev) for t in (bsc, bsh, bmu, bis)]
+        bnb = BnBwdEpilogue(ptr(xind), *[ptr(v) for v in vecs], relu)
+        for with_amax in (False, True):
+            what = '%s %s amax=%d' % (case, mode, with_amax)
+            outs = []
+            for _ in range(2):
+                dz, st, am = Guarded(M, Cout, dev), Guarded(tiles * 2, Cout, dev, guard_rows=4), torch.zeros(64, device=dev)
+                t = bounds(0, am, None, None, None)
+                call('dsnt_conv_fwd_ex', ptr(xd), ptr(wd), None, ptr(dz.t), None, None, 0, None, None, ptr(st.t), C.byref(g),
+                     C.byref(bnb), C.byref(t) if with_amax else None)
+                torch.cuda.synchronize()
+                outs.append((dz, st, am))
+            dz, st, am = outs[0]
+            assert dz.intact(), what + ': dz written outside M x Cout'
+            got = dz.t.cpu().double()
+            err = float((got - ref).abs().max())
+            figs['err amax=%d' % with_amax] = err
+            assert err <= F32_BAR * scale, (what, err, scale)
+            zeros = got == 0
+            if relu:
+                assert torch.equal(zeros, z <= 0), what + ': the mask differs from the fp64 pre-activation\'s in %d places' % int((zeros != (z <= 0)).sum())
+                assert float(zeros.double().mean()) > 0.2          # the mask really is on
+            else:
+                assert int(zeros.sum()) == 0, what + ': relu = 0 and %d zeros' % int(zeros.sum())
+            figs['sums amax=%d' % with_amax] = _f32_check_stats(st, got, xhat, bm, tiles, what)
+            if with_amax:
+                assert float(am.max()) == float(dz.t.abs().max()), what
+            assert _f32_same(outs[0], outs[1]), what + ': two launches differ'
+        figs['scale'] = scale
+        return figs
+
+    inplace = mode == 'inplace'
+    pro = mode.startswith('pro')
+    in_relu = 1 if mode == 'pro_relu' else 0
+    bd = None if inplace else o['b'].to(dev)
+    r1d = o['r1'].to(dev)
+    r2d = None if inplace else o['r2'].to(dev)
+    ascd, ashd = o['asc'].to(dev), o['ash'].to(dev)
+    extra = o['r1'].double() if inplace else o['b'].double() + o['r1'].double() + o['r2'].double()
+
+    def launch(vec, tail_relu, prologue=None):
+        """tail_relu None: no dsnt_out_bounds (dsnt_conv_fwd); 0 / 1: amax and amax_bn with that amax_relu (dsnt_conv_fwd_ex);
+        prologue: a function (y, st, tail) -> the launch itself, for dsnt_conv_fwd_pro."""
+        y = Guarded(M, Cout, dev, init=r1d if inplace else None)
+        st = Guarded(tiles * 2, Cout, dev, guard_rows=4)
+        am, amb = torch.zeros(64, device=dev), torch.zeros(64, device=dev)
+        t = None if tail_relu is None else bounds(tail_relu, am, amb, ascd, ashd)
+        res1 = y.t if inplace else r1d
+        if prologue is not None:
+            prologue(y, st, res1, None if t is None else C.byref(t))
+        elif t is None:
+            call('dsnt_conv_fwd', ptr(xd), ptr(wd), ptr(bd), ptr(y.t), ptr(vec[0]) if vec else None, ptr(vec[1]) if vec else None,
+                 in_relu, ptr(res1), ptr(r2d), ptr(st.t), C.byref(g))
+        else:
+            call('dsnt_conv_fwd_ex', ptr(xd), ptr(wd), ptr(bd), ptr(y.t), ptr(vec[0]) if vec else None, ptr(vec[1]) if vec else None,
+                 in_relu, ptr(res1), ptr(r2d), ptr(st.t), C.byref(g), None, C.byref(t))
+        torch.cuda.synchronize()
+        return y, st, am, amb
+
+    def check(out, ref, tail_relu, what):
+        y, st, am, amb = out
+        assert y.intact(), what + ': y written outside M x Cout'
+        got = y.t.cpu().double()
+        scale = float(ref.abs().max())
+        err = float((got - ref).abs().max())
+        assert err <= F32_BAR * scale, (what, err, scale)
+        s = _f32_check_stats(st, got, got, bm, tiles, what)
+        if tail_relu is not None:
+            assert float(am.max()) == float(y.t.abs().max()), (what, float(am.max()), float(y.t.abs().max()))
+            v = got * o['asc'].double() + o['ash'].double()
+            want = float((v.clamp_min(0.0) if tail_relu else v).abs().max())
+            assert want > 0 and abs(float(amb.max()) - want) <= ULP * want, (what, float(amb.max()), want)
+        return dict(err=err, scale=scale, sums=s)
+
+    vec = (o['sc'].to(dev), o['sh'].to(dev)) if pro else None
+    ref = _f32_conv64(o, case, o['sc'] if pro else None, o['sh'] if pro else None, in_relu) + extra
+    for tail_relu in (None, 1, 0):
+        what = '%s %s bounds=%s' % (case, mode, tail_relu)
+        a, b = launch(vec, tail_relu), launch(vec, tail_relu)
+        r = check(a, ref, tail_relu, what)
+        figs['err bounds=%s' % tail_relu], figs['sums bounds=%s' % tail_relu], figs['scale'] = r['err'], r['sums'], r['scale']
+        assert _f32_same(a, b), what + ': two launches differ'
+
+    # the BatchNorm of the A operand finalised in the launch's own prologue
+    rows = N * H * W
+    tiles_in = (rows + 127) // 128
+    if pro and _lib.fn('dsnt_conv_fwd_pro_ok')(C.byref(g), tiles_in, Cin) == 1:
+        tag = 'f32e' + '_'.join(map(str, case))
+        part = torch.empty(tiles_in, 2, Cin, device=dev)
+        call('dsnt_bn_stats', ptr(xd), ptr(part), rows, Cin)
+        gamma = (synthetic.tensor(tag + 'ga', (Cin,), seed=10, kind='uniform') + 1.5).to(dev)
+        beta = synthetic.tensor(tag + 'be', (Cin,), seed=11, scale=0.2).to(dev)
+        rm0 = synthetic.tensor(tag + 'rm', (Cin,), seed=12, scale=0.3).to(dev)
+        rv0 = (synthetic.tensor(tag + 'rv', (Cin,), seed=13, kind='uniform').abs() + 0.5).to(dev)
+        v_ref, rm_ref, rv_ref = [torch.full((Cin,), float('nan'), device=dev) for _ in range(4)], rm0.clone(), rv0.clone()
+        call('dsnt_bn_finalize', ptr(part), tiles_in, rows, Cin, ptr(gamma), ptr(beta), ptr(rm_ref), ptr(rv_ref), 0.1, 1e-5, 1,
+             *[ptr(t_) for t_ in v_ref])
+        torch.cuda.synchronize()
+        ref_bn = _f32_conv64(o, case, v_ref[2].cpu(), v_ref[3].cpu(), in_relu) + extra
+        for tail_relu in (None, 1):
+            what = '%s %s prologue bounds=%s' % (case, mode, tail_relu)
+            sep = launch((v_ref[2], v_ref[3]), tail_relu)
+            figs['err separate bounds=%s' % tail_relu] = check(sep, ref_bn, tail_relu, what + ' (separately finalised)')['err']
+            fused = []
+            for _ in range(2):
+                v, rm, rv = [torch.full((Cin,), float('nan'), device=dev) for _ in range(4)], rm0.clone(), rv0.clone()
+                bp = BnPrologue(ptr(part), tiles_in, Cin, rows, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), 0.1, 1e-5, *[ptr(t_) for t_ in v])
+
+                def prologue(y, st, res1, t):
+                    call('dsnt_conv_fwd_pro', ptr(xd), ptr(wd), ptr(bd), ptr(y.t), C.byref(bp), in_relu, ptr(res1), ptr(r2d), ptr(st.t),
+                         C.byref(g), t)
+                out = launch(None, tail_relu, prologue)
+                for name, a_, b_ in zip(('mean', 'invstd', 'scale', 'shift', 'running_mean', 'running_var'), v + [rm, rv],
+                                        v_ref + [rm_ref, rv_ref]):
+                    assert torch.equal(a_, b_), '%s: %s differs from dsnt_bn_finalize\'s by %.3e' % (what, name, float((a_ - b_).abs().max()))
+                fused.append(out)
+            assert _f32_same(fused[0], sep), what + ': not the bits of the launch on separately finalised vectors'
+            assert _f32_same(fused[0], fused[1]), what + ': two launches differ'
+    return figs

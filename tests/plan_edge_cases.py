@@ -1,6 +1,7 @@
 """The cases of tests/test_plan_edges_gpu.py, (N, H, W, Cin, Cout) unless said otherwise: geometries the plans of the fp16x3
 streaming kernels accept and the hourglass's own shapes never produce.  What each is for — on 256 CUs — is asserted by
-tests/test_plan_edges_cpu.py."""
+tests/test_plan_edges_cpu.py.  CONV_F32, at the end: the cases of tests/test_conv_f32_edges_gpu.py, the fp32 family of
+csrc/conv_f32.hip across its tile shapes, loaders and K-split chunk counts (no CU count enters its dispatch)."""
 
 WGRAD1 = [
     (1, 25, 656, 128, 128),     # 114 slabs x 144 rows = 9 stages (0 mod 3), last slab 128 rows
@@ -41,3 +42,30 @@ CONV3S_CIN96 = [(2, 8, 32, 96, 64), (1, 8, 16, 96, 128), (3, 16, 32, 96, 128)]  
 CONV3S_ONE_ROW = (3, 4, 32, 64, 64)                 # one patch row: the halo rows above and below are all padding
 
 STEM4 = [(1, 4, 32), (2, 12, 96), (1, 36, 32), (3, 8, 64)]     # (N, Ho, Wo), Ho != Wo; a single tile
+
+# (N, H, W, Cin, Cout, k, stride, pad, dil): the fp32 family (csrc/conv_f32.hip).  Where each lands without a dsnt_out_bounds; with
+# one (amax / amax_bn) the K-split cases run on the 32 x 128 tiling.  M = output rows, K = k * k * Cin, a K-step = 32 of K.
+CONV_F32 = [
+    # ---- the K-split kernel (at most 2048 rows, Cout >= 128, Cin % 8 == 0): eight waves share the chunks of K
+    (1, 6, 6, 24, 128, 3, 1, 1, 1),         # chunk width 8 (Cin % 16 != 0), 27 chunks: 3 or 4 per wave; M = 36
+    (2, 5, 5, 8, 144, 1, 1, 0, 1),          # width 8, ONE chunk: seven idle waves; Cout % 32 != 0 (out-of-range weight rows); M = 50
+    (1, 8, 8, 48, 176, 3, 2, 1, 1),         # width 16, 27 chunks: 3 or 4 per wave; stride 2; ragged Cout; M = 16
+    (1, 9, 9, 32, 128, 3, 1, 2, 2),         # width 16, 18 chunks: 2 or 3 per wave; dilation 2; M = 81
+    (1, 4, 4, 384, 128, 1, 1, 0, 1),        # width 16, 24 chunks: exactly 3 per wave (the rotation once round); M = 16, half a tile
+    (1, 4, 8, 4096, 128, 1, 1, 0, 1),       # 32 chunks per wave; with a prologue the two BatchNorm vectors fill 8192 of the 8448 LDS floats
+    (1, 4, 8, 4104, 128, 1, 1, 0, 1),       # width 8, 64 or 65 chunks per wave; with a prologue past the Cin limit: 32 x 128, general loader
+    (2, 32, 32, 32, 128, 1, 1, 0, 1),       # M = 2048: the last K-split row count; two chunks, six idle waves
+    (1, 2049, 1, 32, 128, 1, 1, 0, 1),      # M = 2049: 32 x 128, FAST, ONE K-step (the loader waves' loop never runs), ragged M
+    # ---- the tiled kernels
+    (2, 9, 9, 32, 96, 3, 1, 1, 1),          # 128 x 128 FAST, 9 K-steps (odd), ragged M (162) and N (96)
+    (1, 10, 10, 12, 72, 5, 1, 2, 1),        # 128 x 128 general, 10 K-steps with a tail (K = 300), ragged M (100) and N (72)
+    (1, 128, 128, 32, 160, 1, 1, 0, 1),     # 128 x 128 FAST, one K-step, two N tiles (the second masked past column 160), 256 workgroups
+    (2, 17, 15, 32, 64, 3, 2, 1, 1),        # 128 x 64 FAST with stride 2, 9 K-steps, odd image sizes, M = 144
+    (2, 7, 9, 16, 48, 1, 1, 0, 1),          # 128 x 64 general, one K-step with a tail (K = 16), ragged N (48), M = 126
+    (1, 12, 12, 32, 64, 5, 1, 2, 1),        # 128 x 64 general although Cin % 32 == 0: 25 taps x 4 row passes > 64 mask bits; 25 K-steps
+    (1, 11, 13, 20, 16, 3, 1, 1, 1),        # 128 x 32 general, 6 K-steps with a tail (K = 180), ragged N (16), M = 143
+    (1, 7, 5, 96, 32, 1, 1, 0, 1),          # 128 x 32 FAST, 3 K-steps, a full 32-column tile, M = 35
+    (1, 64, 64, 16, 256, 1, 1, 0, 1),       # 32 x 128 general: the score_ launch (16 -> 256 at 64 x 64), one K-step with a tail
+    (1, 6, 7, 12, 128, 3, 1, 1, 1),         # 32 x 128 general from Cin % 8 != 0 at few rows (42), 4 K-steps with a tail (K = 108)
+    (3, 30, 30, 32, 144, 3, 1, 1, 1),       # 32 x 128 FAST, 9 K-steps, ragged M (2700) and N (144), 170 workgroups (not a multiple of 8)
+]

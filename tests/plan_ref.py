@@ -1,6 +1,6 @@
 """The host-side plans of the fp16x3 streaming convolution kernels, restated in plain Python with the CU count as a parameter:
 what csrc/{wgrad1,wgrad3,fwd1,bwd1,gemm1,conv3s,stem4}.hip launch their kernels with (slabs, stages per workgroup, iterations,
-column chunks, rows per slab).  tests/test_plan_edges_cpu.py asks it which edges a case hits; tests/test_plan_edges_gpu.py first
+column chunks, rows per slab); and, at the end, the dispatch of the fp32 family of csrc/conv_f32.hip (conv_f32: no CU count enters it).  tests/test_plan_edges_cpu.py asks it which edges a case hits; tests/test_plan_edges_gpu.py first
 holds it to what the C ABI reports on the real device.  A geometry the plan refuses gives None.
 
 Cases are (N, H, W, Cin, Cout); `share` is the DSNT_CONV_SHARE_CHIP / DSNT_WGRAD_SHARE_CHIP form of the launch.  wgrad1 and wgrad3
@@ -166,3 +166,37 @@ def route(case, k, wgrad, stem=False):
         return 1
     N, H, W, Cin, Cout = case
     return 2 if k == 3 and H % 8 == 0 and W % 16 == 0 and Cin % 32 == 0 else 0
+
+
+KSPLIT_ROWS = 2048          # csrc/conv_f32.hip ksplit_rows(): output rows up to which the K-split kernel replaces the 32 x 128 tiling
+KSPLIT_PRO_CIN = 4096       # ... with a BatchNorm prologue: both vectors live in the kernel's 8448 floats of LDS
+
+
+def conv_f32(case, pro=False, amax=False):
+    """The fp32 family of csrc/conv_f32.hip (pick_cfg, the K-split conditions of conv_fwd_impl, `fast` of launch_fwd) for
+    case = (N, H, W, Cin, Cout, k, stride, pad, dil).  pro: the launch has in_scale / in_shift; amax: its dsnt_out_bounds asks for
+    amax or amax_bn (the K-split epilogue has neither).  `bm` is what dsnt_conv_fwd_bm reports: the rows per statistics tile.
+    kernel: ksplit16 / ksplit8 (chunk width; `chunks` = the set of chunks per wave) or t128x128 / t128x64 / t128x32 / t32x128
+    (`fast`: the wave-uniform-tap loader; `nsteps` K-steps of 32, `ktail`: the last one is partial)."""
+    N, H, W, Cin, Cout, k, stride, pad, dil = case
+    Ho = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+    if min(N, H, W, Cin, Cout, k, stride, dil, Ho, Wo) <= 0 or pad < 0 or Cin % 4 or Cout % 4:
+        return None
+    M, K = N * Ho * Wo, k * k * Cin
+    if N * H * W * Cin >= LIMIT or M * Cout >= LIMIT:
+        return None
+    BM, BN = 128, 32 if Cout <= 32 else 64 if Cout <= 64 else 128
+    if -(-M // BM) * -(-Cout // BN) < 256 and Cout >= 128:      # few rows: more workgroups for less register blocking
+        BM, BN = 32, 128
+    fits = N * H * W * Cin * 4 < LIMIT and Cout * K * 4 < LIMIT       # 32-bit byte offsets of the buffer loads
+    out = dict(bm=BM, M=M, K=K, ragged_m=M % BM != 0)
+    if BM == 32 and M <= KSPLIT_ROWS and Cin % 8 == 0 and fits and not amax and (not pro or Cin <= KSPLIT_PRO_CIN):
+        cw = 16 if Cin % 16 == 0 else 8
+        nch = K // cw
+        out.update(kernel='ksplit%d' % cw, chunks={(w + 1) * nch // 8 - w * nch // 8 for w in range(8)},
+                   mtiles=-(-M // 32), ntiles=-(-Cout // 32), ragged_n=Cout % 32 != 0)
+        return out
+    out.update(kernel='t%dx%d' % (BM, BN), fast=Cin % 32 == 0 and k * k * (BM // 32) <= 64 and fits, nsteps=-(-K // 32),
+               ktail=K % 32 != 0, mtiles=-(-M // BM), ntiles=-(-Cout // BN), ragged_n=Cout % BN != 0)
+    return out

@@ -1,6 +1,8 @@
 """HIP implicit-GEMM convolution / BN / pool kernels vs torch CPU ops (the oracle's building
 blocks), called through the C ABI.  fp32 MFMA is an exact-f32 fmaf chain, so forward values are
-held to 2e-5 relative to the output scale (accumulation-order differences only)."""
+held to 2e-5 relative to the output scale (accumulation-order differences only).  The edges of the fp32 family's host plan
+(every tile shape on both loaders, one / odd / tail-ended K-steps, the K-split chunk counts and limits) are
+tests/test_conv_f32_edges_gpu.py's."""
 import ctypes as C
 import os
 
@@ -731,7 +733,7 @@ def test_conv3_stream_refusals():
 
 # (N, H, W, Cin [BN'd input channels], Cout [channels of the conv whose data gradient is taken], k)
 BNB_CASES = [
-    (4, 64, 64, 128, 128, 3),     # 3x3 halo-tile kernel (split paths) / 128x128 implicit GEMM (fp32 path)
+    (4, 64, 64, 128, 128, 3),     # 3x3 halo-tile kernel (split paths) / 32x128 implicit GEMM (fp32 path: 128 tiles of 128x128 are too few)
     (4, 64, 64, 256, 128, 1),     # reducing 1x1 of a Bottleneck: data gradient 128 -> 256
     (4, 64, 64, 128, 256, 1),     # expanding 1x1: data gradient 256 -> 128
     (2, 8, 8, 128, 128, 3),       # 128 rows: the K-split kernel on the fp32 path

@@ -1,7 +1,11 @@
 """The cases of tests/test_plan_edges_gpu.py hold what they claim: on 256 CUs each one hits the plan edge it is listed for
 (tests/plan_ref.py restates the host plans of the fp16x3 streaming kernels), and the case lists of tests/test_conv_gpu.py never
 reached those edges — every 1x1 weight-gradient slab there is eight equal stages, every streaming 1x1 workgroup runs one
-iteration.  No GPU: tests/test_plan_edges_gpu.py holds plan_ref itself to the C ABI on the device."""
+iteration.  No GPU: tests/test_plan_edges_gpu.py holds plan_ref itself to the C ABI on the device.
+
+The same for the fp32 family of csrc/conv_f32.hip (plan_ref.conv_f32, plan_edge_cases.CONV_F32, run by
+tests/test_conv_f32_edges_gpu.py): which tile shape, loader, K-step count and K-split chunk counts each case lands on, and
+that the fp32 launches of tests/test_conv_gpu.py reach none of them."""
 import ast
 import os
 
@@ -160,6 +164,146 @@ def test_conv3s_and_stem_cases_hit_their_edges():
     assert P.stem4((1, 4, 32), CUS)['tiles'] == 1
     assert {c[1] > c[2] for c in E.STEM4} == {True, False}                                               # a tall image and wide ones
     assert {(P.stem4(c)['tile_rows'] > P.stem4(c)['tile_cols']) for c in E.STEM4} == {True, False}      # ... in tiles too
+
+
+def _parametrized(path, func, argnames):
+    """The literal list of the `pytest.mark.parametrize(argnames, [...])` decorator of a test function, read like _literal."""
+    tree = ast.parse(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), path)).read())
+    for node in tree.body:
+        if isinstance(node, ast.FunctionDef) and node.name == func:
+            for dec in node.decorator_list:
+                if isinstance(dec, ast.Call) and dec.args and ast.literal_eval(dec.args[0]) == argnames:
+                    return ast.literal_eval(dec.args[1])
+    raise KeyError((func, argnames))
+
+
+def _existing_f32_launches():
+    """Every dsnt_conv_fwd / _ex / _pro launch on the fp32 path that tests/test_conv_gpu.py holds to a reference of its own, as
+    (what, case, pro, amax) with case = (N, H, W, Cin, Cout, k, stride, pad, dil) of the LAUNCH: test_conv_fwd_wgrad_dgrad (CASES,
+    both `pro`, and the data gradient of the stride-1 ones), test_bn_backward_epilogue_with_relu_vs_autograd on path f32 (BNB_CASES
+    as data gradients, without and with amax), test_epilogue_leaves_the_bound_of_its_output (its shapes are written in its body:
+    restated here, the parameters read) and test_batchnorm_finalised_in_the_consumers_prologue."""
+    out = []
+    for c in _literal('test_conv_gpu.py', 'CASES'):
+        N, H, W, Cin, Cout, k, stride, pad, dil = c
+        out += [('fwd', c, False, False), ('fwd', c, True, False)]
+        if stride == 1:
+            Ho, Wo = H + 2 * pad - dil * (k - 1), W + 2 * pad - dil * (k - 1)
+            out.append(('dgrad', (N, Ho, Wo, Cout, Cin, k, 1, dil * (k - 1) - pad, dil), False, False))
+    for N, H, W, Cin, Cout, k in _literal('test_conv_gpu.py', 'BNB_CASES'):
+        out += [('bnb', (N, H, W, Cout, Cin, k, 1, k // 2, 1), False, amax) for amax in (False, True)]
+    for k, _, N in _parametrized('test_conv_gpu.py', 'test_epilogue_leaves_the_bound_of_its_output', 'k,with_res,N'):
+        out += [('bound', (N, 32, 32, 64, 128, k, 1, k // 2, 1), False, True), ('bound', (1, 8, 8, 64, 128, k, 1, k // 2, 1), False, True)]
+    for N, H, W, Cin, Cout, k in _parametrized('test_conv_gpu.py', 'test_batchnorm_finalised_in_the_consumers_prologue', 'shape'):
+        out.append(('pro', (N, H, W, Cin, Cout, k, 1, k // 2, 1), True, False))
+    return out
+
+
+def test_the_existing_fp32_launches_never_reached_the_edges_of_the_family():
+    """What tests/test_conv_f32_edges_gpu.py is for, as assertions on the lists it complements.  (tests/test_bn_finalize_gpu.py also
+    launches 1x1 convolutions of one K-step on the general loaders, but holds them to the same kernel with separately finalised
+    vectors, not to a reference of the convolution.)"""
+    launches = _existing_f32_launches()
+    assert len(launches) == 11 * 2 + 9 + 7 * 2 + 3 * 2 + 4
+    plans = [(what, case, pro, P.conv_f32(case, pro, amax)) for what, case, pro, amax in launches]
+    assert all(pl is not None for _, _, _, pl in plans)
+    ks = [(w, c, pro, pl) for w, c, pro, pl in plans if pl['kernel'].startswith('ksplit')]
+    tiled = [(w, c, pro, pl) for w, c, pro, pl in plans if pl['kernel'].startswith('t')]
+    # ---- the K-split kernel: chunk width 16 only, whole 32-column tiles, no dilation, and of the chunk counts per wave only these
+    assert ks and all(pl['kernel'] == 'ksplit16' and not pl['ragged_n'] and c[8] == 1 for _, c, _, pl in ks)
+    assert sorted(set(tuple(sorted(pl['chunks'])) for _, _, _, pl in ks)) == [(0, 1), (1,), (2,), (4, 5), (9,)]
+    assert max(pl['M'] for _, _, _, pl in ks) == 1024                                      # the row limit (2048): never approached
+    past = [pl['M'] for (_, case, pro, pl), (_, _, _, amax) in zip(plans, launches) if pl['kernel'] == 't32x128' and not amax]
+    assert past and min(past) == 16384                                                     # ... from either side
+    assert max(c[3] for _, c, pro, _ in plans if pro) == 256                               # ... nor the prologue's Cin <= 4096
+    # ---- 128 x 128: 1x1, FAST, whole tiles, never a prologue, bias, residual or plain statistics (bnb / bound launches only)
+    t128 = [(w, c, pro, pl) for w, c, pro, pl in tiled if pl['kernel'] == 't128x128']
+    assert t128 and all(w in ('bnb', 'bound') and c[5] == 1 and pl['fast'] and not pro and not pl['ragged_m'] and not pl['ragged_n']
+                        for w, c, pro, pl in t128)
+    # ---- the general loader: only the stem (128 x 64, Cin = 4); never on 32 x 128, 128 x 32 or 128 x 128, never with Cin % 32 == 0
+    general = [(c, pl) for _, c, _, pl in tiled if not pl['fast']]
+    assert general and all(pl['kernel'] == 't128x64' and c[3] == 4 and pl['nsteps'] == 7 for c, pl in general)
+    # ---- K-steps: never one, never an odd count on a FAST loader; a FAST loader never with stride > 1
+    assert sorted(set(pl['nsteps'] for _, _, _, pl in tiled)) == [2, 4, 7, 8, 18, 36]
+    assert all(pl['nsteps'] % 2 == 0 and c[6] == 1 for _, c, _, pl in tiled if pl['fast'])
+    # ---- a second N tile never exists with its last columns masked
+    assert all(not (pl['ntiles'] > 1 and pl['ragged_n']) for _, _, _, pl in plans)
+    # (res2 is None, bnb.relu is 1 and amax_relu is 1 in every launch of that file: written in the test bodies, not in the lists)
+
+
+# case -> (without a dsnt_out_bounds, without / with a prologue; the plan with one, where it differs)
+CONV_F32_WANT = {
+    (1, 6, 6, 24, 128, 3, 1, 1, 1): dict(kernel='ksplit8', chunks={3, 4}, ragged_m=True, ragged_n=False, mtiles=2, ntiles=4),
+    (2, 5, 5, 8, 144, 1, 1, 0, 1): dict(kernel='ksplit8', chunks={0, 1}, ragged_m=True, ragged_n=True, mtiles=2, ntiles=5),
+    (1, 8, 8, 48, 176, 3, 2, 1, 1): dict(kernel='ksplit16', chunks={3, 4}, ragged_m=True, ragged_n=True, mtiles=1, ntiles=6),
+    (1, 9, 9, 32, 128, 3, 1, 2, 2): dict(kernel='ksplit16', chunks={2, 3}, ragged_m=True, ragged_n=False, mtiles=3, ntiles=4),
+    (1, 4, 4, 384, 128, 1, 1, 0, 1): dict(kernel='ksplit16', chunks={3}, ragged_m=True, ragged_n=False, M=16, mtiles=1, ntiles=4),
+    (1, 4, 8, 4096, 128, 1, 1, 0, 1): dict(kernel='ksplit16', chunks={32}, ragged_m=False, ragged_n=False, mtiles=1, ntiles=4),
+    (1, 4, 8, 4104, 128, 1, 1, 0, 1): dict(kernel='ksplit8', chunks={64, 65}, ragged_m=False, ragged_n=False, mtiles=1, ntiles=4),
+    (2, 32, 32, 32, 128, 1, 1, 0, 1): dict(kernel='ksplit16', chunks={0, 1}, M=2048, ragged_m=False, ragged_n=False, mtiles=64, ntiles=4),
+    (1, 2049, 1, 32, 128, 1, 1, 0, 1): dict(kernel='t32x128', fast=True, nsteps=1, ktail=False, M=2049, ragged_m=True, ragged_n=False,
+                                            mtiles=65, ntiles=1),
+    (2, 9, 9, 32, 96, 3, 1, 1, 1): dict(kernel='t128x128', fast=True, nsteps=9, ktail=False, ragged_m=True, ragged_n=True, mtiles=2, ntiles=1),
+    (1, 10, 10, 12, 72, 5, 1, 2, 1): dict(kernel='t128x128', fast=False, nsteps=10, ktail=True, ragged_m=True, ragged_n=True, mtiles=1,
+                                          ntiles=1),
+    (1, 128, 128, 32, 160, 1, 1, 0, 1): dict(kernel='t128x128', fast=True, nsteps=1, ktail=False, ragged_m=False, ragged_n=True, mtiles=128,
+                                             ntiles=2),
+    (2, 17, 15, 32, 64, 3, 2, 1, 1): dict(kernel='t128x64', fast=True, nsteps=9, ktail=False, ragged_m=True, ragged_n=False, mtiles=2, ntiles=1),
+    (2, 7, 9, 16, 48, 1, 1, 0, 1): dict(kernel='t128x64', fast=False, nsteps=1, ktail=True, ragged_m=True, ragged_n=True, mtiles=1, ntiles=1),
+    (1, 12, 12, 32, 64, 5, 1, 2, 1): dict(kernel='t128x64', fast=False, nsteps=25, ktail=False, ragged_m=True, ragged_n=False, mtiles=2,
+                                          ntiles=1),
+    (1, 11, 13, 20, 16, 3, 1, 1, 1): dict(kernel='t128x32', fast=False, nsteps=6, ktail=True, ragged_m=True, ragged_n=True, mtiles=2, ntiles=1),
+    (1, 7, 5, 96, 32, 1, 1, 0, 1): dict(kernel='t128x32', fast=True, nsteps=3, ktail=False, ragged_m=True, ragged_n=False, mtiles=1, ntiles=1),
+    (1, 64, 64, 16, 256, 1, 1, 0, 1): dict(kernel='t32x128', fast=False, nsteps=1, ktail=True, ragged_m=False, ragged_n=False, mtiles=128,
+                                           ntiles=2),
+    (1, 6, 7, 12, 128, 3, 1, 1, 1): dict(kernel='t32x128', fast=False, nsteps=4, ktail=True, ragged_m=True, ragged_n=False, mtiles=2, ntiles=1),
+    (3, 30, 30, 32, 144, 3, 1, 1, 1): dict(kernel='t32x128', fast=True, nsteps=9, ktail=False, ragged_m=True, ragged_n=True, mtiles=85,
+                                           ntiles=2),
+}
+# the K-split cases under a dsnt_out_bounds (amax / amax_bn): the 32 x 128 tiling, (fast, K-steps, K tail, N tiles)
+CONV_F32_WANT_AMAX = {
+    (1, 6, 6, 24, 128, 3, 1, 1, 1): (False, 7, True, 1), (2, 5, 5, 8, 144, 1, 1, 0, 1): (False, 1, True, 2),
+    (1, 8, 8, 48, 176, 3, 2, 1, 1): (False, 14, True, 2), (1, 9, 9, 32, 128, 3, 1, 2, 2): (True, 9, False, 1),
+    (1, 4, 4, 384, 128, 1, 1, 0, 1): (True, 12, False, 1), (1, 4, 8, 4096, 128, 1, 1, 0, 1): (True, 128, False, 1),
+    (1, 4, 8, 4104, 128, 1, 1, 0, 1): (False, 129, True, 1), (2, 32, 32, 32, 128, 1, 1, 0, 1): (True, 1, False, 1),
+}
+
+
+def test_conv_f32_cases_hit_their_edges():
+    assert sorted(CONV_F32_WANT) == sorted(E.CONV_F32) and len(set(E.CONV_F32)) == 20
+    for case in E.CONV_F32:
+        pl = P.conv_f32(case)
+        assert pl and all(pl[k] == v for k, v in CONV_F32_WANT[case].items()), (case, pl)
+        # a prologue moves one case only: Cin = 4104 is past the K-split's limit of 4096 input channels
+        pro = P.conv_f32(case, pro=True)
+        if case[3] == 4104:
+            assert (pro['kernel'], pro['fast'], pro['nsteps'], pro['ktail']) == ('t32x128', False, 129, True), pro
+        else:
+            assert pro == pl, (case, pro)
+        am = P.conv_f32(case, amax=True)
+        if pl['kernel'].startswith('ksplit'):
+            assert (am['kernel'], am['bm']) == ('t32x128', 32), (case, am)
+            assert (am['fast'], am['nsteps'], am['ktail'], am['ntiles']) == CONV_F32_WANT_AMAX[case], (case, am)
+            assert am['mtiles'] == pl['mtiles'] and P.conv_f32(case, pro=True, amax=True) == am
+        else:
+            assert am == pl, (case, am)
+    assert sorted(CONV_F32_WANT_AMAX) == sorted(c for c in E.CONV_F32 if P.conv_f32(c)['kernel'].startswith('ksplit'))
+    plans = {c: P.conv_f32(c) for c in E.CONV_F32}
+    # every kernel form: four tile shapes x both loaders, both K-split widths
+    forms = {(pl['kernel'], pl.get('fast')) for pl in plans.values()}
+    assert forms == {('ksplit16', None), ('ksplit8', None)} | {(t, f) for t in ('t128x128', 't128x64', 't128x32', 't32x128') for f in (True, False)}
+    # the K-split rotation: three register sets, so the chunk counts mod 3 and the short ones all occur; the limits from both sides
+    counts = set().union(*[pl['chunks'] for pl in plans.values() if 'chunks' in pl])
+    assert {0, 1, 2, 3, 4, 32, 64, 65} <= counts and {c % 3 for c in counts if c} == {0, 1, 2}
+    assert plans[(1, 4, 8, 4096, 128, 1, 1, 0, 1)] == P.conv_f32((1, 4, 8, 4096, 128, 1, 1, 0, 1), pro=True) and 2 * 4096 <= 8 * 32 * 33
+    assert {plans[c]['M'] for c in plans} >= {2048, 2049}
+    # tiled: one K-step on every tile shape but 128 x 32 (FAST and general), odd counts on FAST loaders, stride 2 on a FAST loader
+    one = {(pl['kernel'], pl['fast']) for pl in plans.values() if pl.get('nsteps') == 1}
+    assert one == {('t32x128', True), ('t32x128', False), ('t128x128', True), ('t128x64', False)}
+    assert {pl['kernel'] for pl in plans.values() if pl.get('fast') and pl['nsteps'] % 2 == 1 and pl['nsteps'] > 1} == \
+        {'t128x128', 't128x64', 't128x32', 't32x128'}
+    assert plans[(2, 17, 15, 32, 64, 3, 2, 1, 1)]['fast'] and plans[(1, 12, 12, 32, 64, 5, 1, 2, 1)]['fast'] is False
+    assert (85 * 2) % 8 != 0 and 128 * 2 == 256
 
 
 def test_plan_ref_refuses_what_the_plans_refuse():
