@@ -2,7 +2,9 @@
 tests/test_plan_edges_gpu.py: one function per kernel family, each the whole comparison of that family against fp64 through the
 C ABI — operands, launches, every assertion — for one case.  A function returns the figures it measured (maximum errors next to
 the scales its bars are relative to), so that a caller can report them; the bars themselves live here and nowhere else.
-At the end: conv_f32_edge, the comparison of tests/test_conv_f32_edges_gpu.py for the fp32 family of csrc/conv_f32.hip."""
+At the end: conv_f32_edge, the comparison of tests/test_conv_f32_edges_gpu.py for the fp32 family of csrc/conv_f32.hip, and
+conv_split_edge, that of tests/test_conv_split_edges_gpu.py for the tiled bf16x6 / fp16x3 kernels of csrc/conv_split6.hip, on
+the same operands, guards and bars."""
 import ctypes as C
 
 import torch
@@ -787,17 +789,22 @@ def _f32_same(a, b):
 _f32_cache = {}
 
 
+def _fields(case):
+    """(N, H, W, Cin, Cout, R, S, stride, pad, dil) of a CONV_F32 case (nine fields, a k x k filter) or a CONV_SPLIT case (ten)."""
+    return tuple(case) if len(case) == 10 else tuple(case[:5]) + (case[5],) + tuple(case[5:])
+
+
 def _f32_operands(case):
     """Host operands of one case and its fp64 convolutions (computed once per case, shared by its modes, never written to)."""
     if case not in _f32_cache:
         _f32_cache.clear()              # the cases come in order: one at a time is enough
-        N, H, W, Cin, Cout, k, stride, pad, dil = case
-        tag = 'f32e' + '_'.join(map(str, case))
-        g = geom(N, H, W, Cin, Cout, k, k, stride, pad, dil)
+        N, H, W, Cin, Cout, R, S, stride, pad, dil = _fields(case)
+        tag = ('f32e' if len(case) == 9 else 'spl') + '_'.join(map(str, case))
+        g = geom(N, H, W, Cin, Cout, R, S, stride, pad, dil)
         M = N * g.Ho * g.Wo
-        o = dict(g=g, M=M)
+        o = dict(g=g, M=M, tag=tag)
         o['x'] = synthetic.tensor(tag + 'x', (N, Cin, H, W), seed=1)
-        o['w'] = synthetic.tensor(tag + 'w', (Cout, Cin, k, k), seed=1, scale=(2.0 / (Cin * k * k)) ** 0.5)
+        o['w'] = synthetic.tensor(tag + 'w', (Cout, Cin, R, S), seed=1, scale=(2.0 / (Cin * R * S)) ** 0.5)
         o['b'] = synthetic.tensor(tag + 'b', (Cout,), seed=1, scale=0.1)
         o['sc'] = synthetic.tensor(tag + 's', (Cin,), seed=1, kind='uniform').abs() + 0.5
         o['sh'] = synthetic.tensor(tag + 'h', (Cin,), seed=1, scale=0.3)
@@ -810,46 +817,79 @@ def _f32_operands(case):
     return _f32_cache[case]
 
 
-def _f32_conv64(o, case, sc=None, sh=None, relu=0):
-    """fp64 F.conv2d on relu?(x * sc + sh) or on x, as [M][Cout]; the three forms on the case's own vectors are kept."""
-    N, H, W, Cin, Cout, k, stride, pad, dil = case
+def _f32_conv64(o, case, sc=None, sh=None, relu=0, dtype=torch.float64):
+    """F.conv2d in fp64 (or wholly in `dtype`) on relu?(x * sc + sh) or on x, as [M][Cout]; the three forms on the case's own
+    vectors are kept."""
+    N, H, W, Cin, Cout, R, S, stride, pad, dil = _fields(case)
     key = None if sc is None else relu if sc is o['sc'] else -1
+    if key != -1:
+        key = (key, dtype)
     if key in o['conv']:
         return o['conv'][key]
-    a = o['x'].double()
+    a = o['x'].to(dtype)
     if sc is not None:
-        a = a * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1)
+        a = a * sc.to(dtype).view(1, -1, 1, 1) + sh.to(dtype).view(1, -1, 1, 1)
         a = F.relu(a) if relu else a
-    y = F.conv2d(a, o['w'].double(), None, stride=stride, padding=pad, dilation=dil).permute(0, 2, 3, 1).reshape(o['M'], Cout)
+    y = F.conv2d(a, o['w'].to(dtype), None, stride=stride, padding=pad, dilation=dil).permute(0, 2, 3, 1).reshape(o['M'], Cout)
     if key != -1:
         o['conv'][key] = y
     return y
 
 
-def _f32_tile_sums(got, weight, bm, tiles):
-    """fp64 per-tile column sums of got * weight and of |got * weight| over tiles of bm rows (the last one short)."""
+def _f32_tile_sums(got, weight, bm, tiles, tile_of=None):
+    """fp64 per-tile column sums of got * weight and of |got * weight|; tile_of: the tile index of every row (int64), without it
+    tiles of bm consecutive rows (the last one short)."""
     M, Cc = got.shape
-    v = torch.zeros(tiles * bm, Cc, dtype=torch.float64)
-    v[:M] = got * weight
-    v = v.view(tiles, bm, Cc)
-    return v.sum(1), v.abs().sum(1)
+    if tile_of is None:
+        tile_of = torch.arange(M) // bm
+    v = got * weight
+    return (torch.zeros(tiles, Cc, dtype=torch.float64).index_add_(0, tile_of, v),
+            torch.zeros(tiles, Cc, dtype=torch.float64).index_add_(0, tile_of, v.abs()))
 
 
-def _f32_check_stats(st, got, second, bm, tiles, what):
+def _f32_check_stats(st, got, second, bm, tiles, what, tile_of=None):
     """The statistics rows [tiles][2][Cout] of a launch against fp64 sums over the launch's OWN output `got`: row 0 the column
-    sums, row 1 the sums of got * second; every element overwritten, nothing behind them touched."""
+    sums, row 1 the sums of got * second; every element overwritten, nothing behind them touched.  tile_of: see _f32_tile_sums."""
     assert st.intact(), '%s: statistics written outside [tiles][2][Cout]' % what
     s = st.t.cpu().double().view(tiles, 2, -1)
     assert bool((s != SENT).all()), '%s: %d statistics elements never written' % (what, int((s == SENT).sum()))
     worst = 0.0
     for row, wgt in ((0, torch.ones_like(got)), (1, second)):
-        want, mag = _f32_tile_sums(got, wgt, bm, tiles)
+        want, mag = _f32_tile_sums(got, wgt, bm, tiles, tile_of)
         err = (s[:, row] - want).abs()
         bad = ~(err <= SUM_BAR * mag)
         assert not bool(bad.any()), '%s: statistics row %d: %d elements off, worst %.3e of the column\'s sum of absolute values' % (
             what, row, int(bad.sum()), float((err / mag.clamp_min(1e-300))[bad].max()))
         worst = max(worst, float((err / mag.clamp_min(1e-300)).max()))
     return worst
+
+
+def _out_bounds(relu, am, amb, ascd, ashd):
+    """A dsnt_out_bounds asking for amax and, with amb, for amax_bn under amax_relu = relu."""
+    from dsnt._lib import BnTail
+    t = BnTail()
+    t.amax = am.data_ptr()
+    if amb is not None:
+        t.amax_bn, t.amax_scale, t.amax_shift, t.amax_relu = amb.data_ptr(), ascd.data_ptr(), ashd.data_ptr(), relu
+    return t
+
+
+def _bnb_operands(tag, M, Cout):
+    """Host operands of a BatchNorm-backward epilogue over [M][Cout]: the BatchNorm's input, scale (both signs, away from zero),
+    shift, mean, invstd, and the fp64 pre-activation z = x * scale + shift — none of it within 1e-3 of the kink."""
+    xin = synthetic.tensor(tag + 'xin', (M, Cout), seed=5)
+    bsc = synthetic.tensor(tag + 'bs', (Cout,), seed=6, kind='uniform')
+    bsc = torch.sign(bsc) * (bsc.abs() + 0.5)                              # both signs, away from zero
+    bsh = synthetic.tensor(tag + 'bh', (Cout,), seed=7, scale=0.3)
+    bmu = synthetic.tensor(tag + 'bm', (Cout,), seed=8, scale=0.2)
+    bis = synthetic.tensor(tag + 'bi', (Cout,), seed=9, kind='uniform').abs() + 0.5
+    z = xin.double() * bsc.double() + bsh.double()
+    near = z.abs() < 1e-3           # two fp32 evaluations may disagree about a pre-activation at the kink: move those away
+    xin = (xin.double() + torch.where(near, torch.sign(z) * torch.sign(bsc.double()) * 4e-3 / bsc.double().abs(),
+                                      torch.zeros_like(z))).float()
+    z = xin.double() * bsc.double() + bsh.double()
+    assert float(z.abs().min()) >= 1e-3
+    return xin, bsc, bsh, bmu, bis, z
 
 
 def conv_f32_edge(case, mode):
@@ -878,28 +918,11 @@ def conv_f32_edge(case, mode):
     wd = o['w'].permute(0, 2, 3, 1).contiguous().to(dev)          # OHWI
     figs = {}
 
-    def bounds(relu, am, amb, ascd, ashd):
-        t = BnTail()
-        t.amax = am.data_ptr()
-        if amb is not None:
-            t.amax_bn, t.amax_scale, t.amax_shift, t.amax_relu = amb.data_ptr(), ascd.data_ptr(), ashd.data_ptr(), relu
-        return t
+    bounds = _out_bounds
 
     if mode.startswith('bnb'):
         relu = 1 if mode == 'bnb_relu' else 0
-        tag = 'f32e' + '_'.join(map(str, case))
-        xin = synthetic.tensor(tag + 'xin', (M, Cout), seed=5)
-        bsc = synthetic.tensor(tag + 'bs', (Cout,), seed=6, kind='uniform')
-        bsc = torch.sign(bsc) * (bsc.abs() + 0.5)                              # both signs, away from zero
-        bsh = synthetic.tensor(tag + 'bh', (Cout,), seed=7, scale=0.3)
-        bmu = synthetic.tensor(tag + 'bm', (Cout,), seed=8, scale=0.2)
-        bis = synthetic.tensor(tag + 'bi', (Cout,), seed=9, kind='uniform').abs() + 0.5
-        z = xin.double() * bsc.double() + bsh.double()
-        near = z.abs() < 1e-3           # two fp32 evaluations may disagree about a pre-activation at the kink: move those away
-        xin = (xin.double() + torch.where(near, torch.sign(z) * torch.sign(bsc.double()) * 4e-3 / bsc.double().abs(),
-                                          torch.zeros_like(z))).float()
-        z = xin.double() * bsc.double() + bsh.double()
-        assert float(z.abs().min()) >= 1e-3
+        xin, bsc, bsh, bmu, bis, z = _bnb_operands('f32e' + '_'.join(map(str, case)), M, Cout)
         conv = _f32_conv64(o, case)
         ref = torch.where(z > 0, conv, torch.zeros_like(conv)) if relu else conv
         scale = float(ref.abs().max())
@@ -1022,4 +1045,200 @@ def conv_f32_edge(case, mode):
                 fused.append(out)
             assert _f32_same(fused[0], sep), what + ': not the bits of the launch on separately finalised vectors'
             assert _f32_same(fused[0], fused[1]), what + ': two launches differ'
+    return figs
+
+
+# ---------------------------------------------------------------- the tiled split-precision kernels at their plan edges (csrc/conv_split6.hip)
+
+CONV_SPLIT_PATHS = ('bf16x6', 'f16x3')
+PLANE_GAP = 8               # elements between the end of a weight plane and the next one, for the cases at an odd index
+A_SLOT = 7                  # the slot of the 64 that holds the A operand's bound: any may
+
+
+def split_weight_planes(wd, path, gap, dev):
+    """The OHWI weights `wd` as the planes a split-precision launch reads: (planes, plane_stride, w_bound).  bf16x6: three bf16
+    planes of dsnt_split_bf16x3, copied `numel + gap` apart; fp16x3: dsnt_amax, then dsnt_split_f16x2 with that stride.  What
+    lies between the planes is NaN."""
+    from dsnt._lib import ptr, call
+    n = wd.numel()
+    stride = n + gap
+    if path == 'bf16x6':
+        tight = torch.empty(3 * n, dtype=torch.bfloat16, device=dev)
+        call('dsnt_split_bf16x3', ptr(wd), ptr(tight), n)
+        assert torch.equal(tight.view(3, n).float().sum(0), wd.reshape(-1))            # the split is exact
+        planes = torch.full((3 * stride,), float('nan'), dtype=torch.bfloat16, device=dev)
+        planes.view(3, stride)[:, :n] = tight.view(3, n)
+        wb = None
+    else:
+        wb = torch.zeros(64, device=dev)
+        call('dsnt_amax', ptr(wd), n, ptr(wb))
+        assert wb.max().item() == wd.abs().max().item()
+        planes = torch.full((2 * stride,), float('nan'), dtype=torch.float16, device=dev)
+        call('dsnt_split_f16x2', ptr(wd), ptr(planes), n, stride, ptr(wb))
+    v = planes.view(-1, stride)
+    assert bool(torch.isfinite(v[:, :n]).all()) and bool(torch.isnan(v[:, n:]).all())
+    return planes, stride, wb
+
+
+def split_launch(path, xd, planes, stride, wb, ab, bias, y, sc, sh, in_relu, res1, res2, st, g, bnb=None, tail=None, check=True):
+    """dsnt_conv_fwd_bf16x6_ex / dsnt_conv_fwd_f16x3_ex (ab: the A operand's bound) on the current stream; the return code."""
+    from dsnt import _lib
+    from dsnt._lib import ptr
+    common = (ptr(bias), ptr(y), ptr(sc), ptr(sh), in_relu, ptr(res1), ptr(res2), ptr(st), C.byref(g),
+              None if bnb is None else C.byref(bnb), None if tail is None else C.byref(tail), _lib.stream_ptr())
+    if path == 'bf16x6':
+        rc = _lib.fn('dsnt_conv_fwd_bf16x6_ex')(ptr(xd), ptr(planes), stride, *common)
+    else:
+        rc = _lib.fn('dsnt_conv_fwd_f16x3_ex')(ptr(xd), ptr(planes), stride, ptr(wb), ptr(ab), *common)
+    assert rc == 0 or not check, (rc, _lib.fn('dsnt_last_error')())
+    return rc
+
+
+def split_tile_of(case, halo):
+    """The statistics tile of every output row: 128 consecutive rows, or — the halo kernel — the 8 x 16 patch of pixels
+    [8 th, 8 th + 8) x [16 tw, 16 tw + 16) of image img, tile (img * (H / 8) + th) * (W / 16) + tw."""
+    N, H, W = case[:3]
+    if not halo:
+        return None
+    m = torch.arange(N * H * W)
+    img, oh, ow = m // (H * W), m % (H * W) // W, m % W
+    return (img * (H // 8) + oh // 8) * (W // 16) + ow // 16
+
+
+def conv_split_edge(case, path, mode):
+    """One case of tests/plan_edge_cases.py CONV_SPLIT on one path (bf16x6: dsnt_conv_fwd_bf16x6_ex; f16x3: dsnt_conv_fwd_f16x3_ex
+    with the weight bound of dsnt_amax and the A operand's bound in slot A_SLOT) in one mode of CONV_F32_MODES, against torch fp64
+    on the CPU.  As conv_f32_edge: sentinel-filled guarded buffers, every launch twice into fresh ones (the same bits).
+      fwd / pro_relu / pro_norelu   bias, res1, res2, statistics; without a dsnt_out_bounds, then with amax + amax_bn at amax_relu 1
+                    and 0.  fp16x3: the A bound exact; in fwd and pro_relu also 64 times loose.
+      inplace       res1 == y, no bias, no second residual.
+      bnb_relu / bnb_norelu   the BatchNorm-backward epilogue without and with amax: dz is zero exactly where the fp64
+                    pre-activation is <= 0 (relu 1) and where every tap of the output pixel lies in the padding — nowhere else.
+    Outputs: F32_BAR of max |reference|, and an error of fp32 size — at most max(4 err32, 2e-6 scale), err32 the error of torch's
+    fp32 CPU convolution (masked with the fp64 mask in the bnb modes) on the same operands.  Statistics: per tile (the halo
+    kernel's are 8 x 16 patches), SUM_BAR against fp64 sums over the device's own output.  amax exact, amax_bn within ULP."""
+    from dsnt import _lib
+    from dsnt._lib import BnBwdEpilogue
+    import plan_edge_cases as E
+    assert mode in CONV_F32_MODES and path in CONV_SPLIT_PATHS
+    N, H, W, Cin, Cout, R, S, stride_, pad, dil = case
+    dev = torch.device('cuda:0')
+    o = _f32_operands(case)
+    g, M = o['g'], o['M']
+    f16 = path == 'f16x3'
+    halo = _lib.fn('dsnt_conv_f16x3_route')(C.byref(g), 0) == 2
+    tiles = (M + 127) // 128
+    tile_of = split_tile_of(case, halo)
+    xd = nhwc(o['x']).to(dev)
+    wd = o['w'].permute(0, 2, 3, 1).contiguous().to(dev)          # OHWI
+    planes, stride, wb = split_weight_planes(wd, path, PLANE_GAP if E.CONV_SPLIT.index(case) % 2 else 0, dev)
+    figs = dict(err_max=0.0, sums_max=0.0)
+
+    def a_bound(value, loose=1.0):
+        if not f16:
+            return None
+        ab = torch.zeros(64, device=dev)
+        ab[A_SLOT] = value * loose
+        return ab
+
+    def outputs(got, ref, ref32, what):
+        """y or dz against fp64, at the project's bar and at fp32 size."""
+        assert bool((got != SENT).all()), '%s: %d output elements never written' % (what, int((got == SENT).sum()))
+        scale = float(ref.abs().max())
+        err = float((got - ref).abs().max())
+        err32 = float((ref32.double() - ref).abs().max())
+        figs.update(scale=scale, err32=err32, err_max=max(figs['err_max'], err))
+        assert err <= F32_BAR * scale, (what, err, scale)
+        assert err <= max(4 * err32, 2e-6 * scale), (what, err, err32, scale)
+        return err
+
+    if mode.startswith('bnb'):
+        relu = 1 if mode == 'bnb_relu' else 0
+        xin, bsc, bsh, bmu, bis, z = _bnb_operands(o['tag'], M, Cout)
+        conv, conv32 = _f32_conv64(o, case), _f32_conv64(o, case, dtype=torch.float32)
+        ref = torch.where(z > 0, conv, torch.zeros_like(conv)) if relu else conv
+        ref32 = torch.where(z > 0, conv32, torch.zeros_like(conv32)) if relu else conv32
+        # output pixels whose every tap lies in the padding (Ho > H): this launch has no bias, their sums are exactly zero
+        taps = F.conv2d(torch.ones(N, 1, H, W, dtype=torch.float64), torch.ones(1, 1, R, S, dtype=torch.float64), None, stride=stride_,
+                        padding=pad, dilation=dil)
+        pad_only = (taps.reshape(M, 1) == 0).expand(M, Cout)
+        assert bool((conv[pad_only] == 0).all()) and int((conv == 0).sum()) == int(pad_only.sum())
+        xhat = (xin.double() - bmu.double()) * bis.double()
+        xind, vecs = xin.to(dev), [t.to(dev) for t in (bsc, bsh, bmu, bis)]
+        bnb = BnBwdEpilogue(xind.data_ptr(), *[v.data_ptr() for v in vecs], relu)
+        ab = a_bound(float(o['x'].abs().max()))
+        for with_amax in (False, True):
+            what = '%s %s %s amax=%d' % (case, path, mode, with_amax)
+            outs = []
+            for _ in range(2):
+                dz, st, am = Guarded(M, Cout, dev), Guarded(tiles * 2, Cout, dev, guard_rows=4), torch.zeros(64, device=dev)
+                t = _out_bounds(0, am, None, None, None)
+                split_launch(path, xd, planes, stride, wb, ab, None, dz.t, None, None, 0, None, None, st.t, g, bnb, t if with_amax else None)
+                torch.cuda.synchronize()
+                outs.append((dz, st, am))
+            dz, st, am = outs[0]
+            assert dz.intact(), what + ': dz written outside M x Cout'
+            got = dz.t.cpu().double()
+            figs['err amax=%d' % with_amax] = outputs(got, ref, ref32, what)
+            zeros = got == 0
+            if relu:
+                want0 = (z <= 0) | pad_only
+                assert torch.equal(zeros, want0), what + ': the mask differs from the fp64 pre-activation\'s in %d places' % int((zeros != want0).sum())
+                assert float((z <= 0).double().mean()) > 0.2          # the mask really is on
+            else:
+                assert torch.equal(zeros, pad_only), what + ': relu = 0 and %d zeros' % int((zeros != pad_only).sum())
+            figs['sums amax=%d' % with_amax] = _f32_check_stats(st, got, xhat, 128, tiles, what, tile_of)
+            figs['sums_max'] = max(figs['sums_max'], figs['sums amax=%d' % with_amax])
+            if with_amax:
+                assert float(am.max()) == float(dz.t.abs().max()), what
+            assert _f32_same(outs[0], outs[1]), what + ': two launches differ'
+        return figs
+
+    inplace = mode == 'inplace'
+    pro = mode.startswith('pro')
+    in_relu = 1 if mode == 'pro_relu' else 0
+    bd = None if inplace else o['b'].to(dev)
+    r1d = o['r1'].to(dev)
+    r2d = None if inplace else o['r2'].to(dev)
+    ascd, ashd = o['asc'].to(dev), o['ash'].to(dev)
+    scd, shd = (o['sc'].to(dev), o['sh'].to(dev)) if pro else (None, None)
+    vec = (o['sc'], o['sh']) if pro else (None, None)
+    conv, conv32 = _f32_conv64(o, case, *vec, in_relu), _f32_conv64(o, case, *vec, in_relu, dtype=torch.float32)
+    if inplace:
+        ref, ref32 = conv + o['r1'].double(), conv32 + o['r1']
+    else:
+        ref, ref32 = conv + (o['b'].double() + o['r1'].double() + o['r2'].double()), conv32 + o['b'] + o['r1'] + o['r2']
+    act = o['x'].double()
+    if pro:
+        act = act * o['sc'].double().view(1, -1, 1, 1) + o['sh'].double().view(1, -1, 1, 1)
+        act = F.relu(act) if in_relu else act
+    act_max = float(act.abs().max())
+
+    def launch(ab, tail_relu):
+        y = Guarded(M, Cout, dev, init=r1d if inplace else None)
+        st = Guarded(tiles * 2, Cout, dev, guard_rows=4)
+        am, amb = torch.zeros(64, device=dev), torch.zeros(64, device=dev)
+        t = None if tail_relu is None else _out_bounds(tail_relu, am, amb, ascd, ashd)
+        split_launch(path, xd, planes, stride, wb, ab, bd, y.t, scd, shd, in_relu, y.t if inplace else r1d, r2d, st.t, g, None, t)
+        torch.cuda.synchronize()
+        return y, st, am, amb
+
+    for loose in ((1.0, 64.0) if f16 and mode in ('fwd', 'pro_relu') else (1.0,)):
+        ab = a_bound(act_max, loose)
+        for tail_relu in (None, 1, 0):
+            what = '%s %s %s bounds=%s bound x %g' % (case, path, mode, tail_relu, loose)
+            key = 'bounds=%s%s' % (tail_relu, '' if loose == 1.0 else ' loose')
+            a, b = launch(ab, tail_relu), launch(ab, tail_relu)
+            y, st, am, amb = a
+            assert y.intact(), what + ': y written outside M x Cout'
+            got = y.t.cpu().double()
+            figs['err ' + key] = outputs(got, ref, ref32, what)
+            figs['sums ' + key] = _f32_check_stats(st, got, got, 128, tiles, what, tile_of)
+            figs['sums_max'] = max(figs['sums_max'], figs['sums ' + key])
+            if tail_relu is not None:
+                assert float(am.max()) == float(y.t.abs().max()), (what, float(am.max()), float(y.t.abs().max()))
+                v = got * o['asc'].double() + o['ash'].double()
+                want = float((v.clamp_min(0.0) if tail_relu else v).abs().max())
+                assert want > 0 and abs(float(amb.max()) - want) <= ULP * want, (what, float(amb.max()), want)
+            assert _f32_same(a, b), what + ': two launches differ'
     return figs

@@ -1,7 +1,8 @@
 """The cases of tests/test_plan_edges_gpu.py, (N, H, W, Cin, Cout) unless said otherwise: geometries the plans of the fp16x3
 streaming kernels accept and the hourglass's own shapes never produce.  What each is for — on 256 CUs — is asserted by
 tests/test_plan_edges_cpu.py.  CONV_F32, at the end: the cases of tests/test_conv_f32_edges_gpu.py, the fp32 family of
-csrc/conv_f32.hip across its tile shapes, loaders and K-split chunk counts (no CU count enters its dispatch)."""
+csrc/conv_f32.hip across its tile shapes, loaders and K-split chunk counts (no CU count enters its dispatch).  CONV_SPLIT, after
+it: the cases of tests/test_conv_split_edges_gpu.py, the tiled split-precision kernels of csrc/conv_split6.hip."""
 
 WGRAD1 = [
     (1, 25, 656, 128, 128),     # 114 slabs x 144 rows = 9 stages (0 mod 3), last slab 128 rows
@@ -68,4 +69,29 @@ CONV_F32 = [
     (1, 64, 64, 16, 256, 1, 1, 0, 1),       # 32 x 128 general: the score_ launch (16 -> 256 at 64 x 64), one K-step with a tail
     (1, 6, 7, 12, 128, 3, 1, 1, 1),         # 32 x 128 general from Cin % 8 != 0 at few rows (42), 4 K-steps with a tail (K = 108)
     (3, 30, 30, 32, 144, 3, 1, 1, 1),       # 32 x 128 FAST, 9 K-steps, ragged M (2700) and N (144), 170 workgroups (not a multiple of 8)
+]
+
+# (N, H, W, Cin, Cout, R, S, stride, pad, dil) — R and S apart: the tiled bf16x6 / fp16x3 kernels of csrc/conv_split6.hip
+# (plan_ref.conv_split).  M = output rows, a K-step = 16 of K = R * S * Cin, a chunk = 16 input channels of the halo kernel.  Cases
+# at an odd index run with their weight planes 8 elements further apart than the weights are long.
+CONV_SPLIT = [
+    # ---- the implicit GEMM (anything the halo kernel does not take)
+    (1, 3, 5, 16, 4, 1, 1, 1, 0, 1),        # ONE K-step; M = 15; Cout = 4: one float4 column of a 64-wide tile
+    (1, 8, 16, 32, 64, 1, 1, 1, 0, 1),      # two K-steps; exactly one full 128 x 64 tile
+    (1, 3, 43, 48, 68, 1, 1, 1, 0, 1),      # three K-steps (the odd tail); M = 129: a row tile of ONE row; Cout = 68 on a 128-wide tile
+    (2, 7, 9, 16, 132, 3, 3, 1, 1, 1),      # the tap changes every K-step (9); a second N tile of four columns; two images in one tile
+    (3, 5, 7, 16, 64, 3, 3, 1, 1, 1),       # three images in one ragged tile (M = 105)
+    (1, 9, 11, 32, 192, 1, 3, 1, 1, 1),     # R != S; Ho = 11 > H: the first and last output rows see padding only; three 64-wide tiles
+    (1, 12, 10, 16, 8, 4, 4, 2, 1, 1),      # 16 taps (bit 31 of the tap mask) at stride 2; M = 30
+    (1, 15, 13, 48, 128, 3, 3, 2, 1, 1),    # stride 2, odd sizes, 27 K-steps, three per tap; 128 columns as two 64-wide tiles
+    (1, 11, 14, 32, 96, 3, 2, 2, 2, 2),     # R != S with stride 2 and dilation 2; Cout = 96 on a 128-wide tile
+    (1, 4, 8, 528, 72, 1, 1, 1, 0, 1),      # 33 K-steps; the prologue's vectors copied in three trips, the last ragged; LDS above 64 KB
+    (2, 64, 64, 16, 128, 1, 1, 1, 0, 1),    # M = 8192: the last row count on 64-wide tiles
+    (1, 65, 128, 16, 128, 1, 1, 1, 0, 1),   # M = 8320: the same channels on 128-wide tiles; 65 row tiles (not a multiple of 8)
+    # ---- the LDS halo-tile kernel (3x3 / 1 / 1, H % 8 == 0, W % 16 == 0, Cin % 32 == 0): tiles are 8 x 16 patches
+    (1, 8, 16, 32, 4, 3, 3, 1, 1, 1),       # one tile, every halo edge padding; TN = 1; one float4 column; two chunks
+    (2, 8, 48, 64, 36, 3, 3, 1, 1, 1),      # TN = 1, ragged Cout; one tile row of three tiles, two images
+    (1, 24, 16, 96, 64, 3, 3, 1, 1, 1),     # TN = 1, a full tile; three tile rows in one column; six chunks
+    (1, 16, 32, 160, 132, 3, 3, 1, 1, 1),   # TN = 2; ten chunks; 2 x 2 tiles; a second N tile of four columns
+    (3, 8, 16, 32, 128, 3, 3, 1, 1, 1),     # TN = 2, full; three one-tile images
 ]

@@ -1,6 +1,7 @@
 """The host-side plans of the fp16x3 streaming convolution kernels, restated in plain Python with the CU count as a parameter:
 what csrc/{wgrad1,wgrad3,fwd1,bwd1,gemm1,conv3s,stem4}.hip launch their kernels with (slabs, stages per workgroup, iterations,
-column chunks, rows per slab); and, at the end, the dispatch of the fp32 family of csrc/conv_f32.hip (conv_f32: no CU count enters it).  tests/test_plan_edges_cpu.py asks it which edges a case hits; tests/test_plan_edges_gpu.py first
+column chunks, rows per slab); and, at the end, the dispatch of the fp32 family of csrc/conv_f32.hip (conv_f32: no CU count enters it) and of the tiled split-precision kernels of
+csrc/conv_split6.hip (conv_split).  tests/test_plan_edges_cpu.py asks it which edges a case hits; tests/test_plan_edges_gpu.py first
 holds it to what the C ABI reports on the real device.  A geometry the plan refuses gives None.
 
 Cases are (N, H, W, Cin, Cout); `share` is the DSNT_CONV_SHARE_CHIP / DSNT_WGRAD_SHARE_CHIP form of the launch.  wgrad1 and wgrad3
@@ -199,4 +200,39 @@ def conv_f32(case, pro=False, amax=False):
         return out
     out.update(kernel='t%dx%d' % (BM, BN), fast=Cin % 32 == 0 and k * k * (BM // 32) <= 64 and fits, nsteps=-(-K // 32),
                ktail=K % 32 != 0, mtiles=-(-M // BM), ntiles=-(-Cout // BN), ragged_n=Cout % BN != 0)
+    return out
+
+
+FWD6_BN64_ROWS = 8192       # csrc/conv_split6.hip FWD6_BN64_ROWS_DEFAULT: output rows up to which Cout % 64 == 0 runs on 64-wide tiles.
+                            # A PREMISE: DSNT_X_FWD6_BN64_ROWS moves it, no test sets that, and the ABI does not show the tile width
+PITCH6 = 24                 # csrc/conv_split.h: bf16 / fp16 elements per LDS row of 16
+
+
+def conv_split(case, path='bf16x6'):
+    """conv_fwd6_impl of csrc/conv_split6.hip for case = (N, H, W, Cin, Cout, R, S, stride, pad, dil) below the streaming kernels
+    (gemm1 takes 1x1 convolutions of 65536 rows and more on the fp16x3 path: refused here).  kernel: 'halo' (conv3x3_halo_ok, the
+    8 x 16 patch kernel, TN = bn / 64) or 'gemm' (the implicit GEMM on 128 x bn tiles); mtiles = the statistics rows; nsteps =
+    K / 16 K-steps ('gemm') or nchunks = Cin / 16 ('halo'); lds = the bytes of LDS the launch asks for on `path` (three bf16 or two
+    fp16 planes; the epilogue's C tile where that is larger); trips = passes of the 256 loader threads over the BatchNorm vectors
+    of a prologue ('gemm': they live behind the tiles in LDS; the halo kernel reads them from memory)."""
+    N, H, W, Cin, Cout, R, S, stride, pad, dil = case
+    Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
+    if min(N, H, W, Cin, Cout, R, S, stride, dil, Ho, Wo) <= 0 or pad < 0 or Cin % 16 or Cout % 4 or R * S > 16:
+        return None
+    M, K = N * Ho * Wo, R * S * Cin
+    if N * H * W * Cin * 4 >= LIMIT or M * Cout >= LIMIT or 3 * Cout * K * 2 >= LIMIT:
+        return None
+    if path == 'f16x3' and R == S == 1 and stride == 1 and pad == 0 and gemm1((N, H, W, Cin, Cout)):
+        return None
+    halo = (R, S, stride, pad, dil) == (3, 3, 1, 1, 1) and H % 8 == 0 and W % 16 == 0 and Cin % 32 == 0
+    bn = 64 if Cout <= 64 or (M <= FWD6_BN64_ROWS and Cout % 64 == 0 and not halo) else 128
+    npl = 2 if path == 'f16x3' else 3
+    out = dict(kernel='halo' if halo else 'gemm', bn=bn, M=M, K=K, mtiles=-(-M // 128), ntiles=-(-Cout // bn), ragged_m=M % 128 != 0,
+               ragged_n=Cout % bn != 0)
+    epi = 128 * (bn + 4) * 4
+    if halo:
+        out.update(nchunks=Cin // 16, trips=0, lds=max(((2 if npl == 2 else 1) * npl * 192 + 2 * npl * bn) * PITCH6 * 2, epi))
+    else:
+        out.update(nsteps=K // 16, trips=-(-Cin // 256), lds=max(2 * npl * (128 + bn) * PITCH6 * 2 + 2 * Cin * 4, epi))
     return out

@@ -5,7 +5,11 @@ iteration.  No GPU: tests/test_plan_edges_gpu.py holds plan_ref itself to the C 
 
 The same for the fp32 family of csrc/conv_f32.hip (plan_ref.conv_f32, plan_edge_cases.CONV_F32, run by
 tests/test_conv_f32_edges_gpu.py): which tile shape, loader, K-step count and K-split chunk counts each case lands on, and
-that the fp32 launches of tests/test_conv_gpu.py reach none of them."""
+that the fp32 launches of tests/test_conv_gpu.py reach none of them.
+
+And for the tiled split-precision kernels of csrc/conv_split6.hip (plan_ref.conv_split, plan_edge_cases.CONV_SPLIT, run by
+tests/test_conv_split_edges_gpu.py): kernel, tile width, K-steps or chunks, LDS request and prologue trips of each case, and
+which of those edges BF16X6_CASES of tests/test_conv_gpu.py did and did not reach."""
 import ast
 import os
 
@@ -314,3 +318,121 @@ def test_plan_ref_refuses_what_the_plans_refuse():
     assert P.wgrad3((1, 16, 48, 64, 64)) is None and P.wgrad3((1, 16, 160, 64, 64)) is None
     assert P.conv3s((2, 4, 16, 64, 64)) is None and P.conv3s((2, 8, 32, 160, 64)) is None
     assert P.stem4((1, 6, 32)) is None and P.stem4((1, 4, 48)) is None
+    assert P.conv_split((1, 8, 8, 24, 16, 1, 1, 1, 0, 1)) is None and P.conv_split((1, 8, 8, 16, 16, 4, 5, 1, 1, 1)) is None
+    assert P.conv_split((16, 64, 64, 128, 128, 1, 1, 1, 0, 1), 'f16x3') is None         # the streaming 1x1 kernel's
+    assert P.conv_split((16, 64, 64, 128, 128, 1, 1, 1, 0, 1))['bn'] == 128
+
+
+# ---------------------------------------------------------------- the tiled split-precision kernels (csrc/conv_split6.hip)
+
+def _existing_split_cases():
+    """BF16X6_CASES of tests/test_conv_gpu.py — the geometries its bf16x6 test and tests/test_f16x3_range_gpu.py run through
+    these kernels — as 10-tuples with R and S apart."""
+    cases = [c for c in _literal('test_conv_gpu.py', 'CASES') if c[3] % 16 == 0 and c[4] % 4 == 0] + _literal('test_conv_gpu.py', 'BF16X6_CASES')
+    return [c[:5] + (c[5],) + c[5:] for c in cases]
+
+
+def test_the_existing_split_precision_cases_never_reached_the_edges_of_the_tiled_kernels():
+    """What tests/test_conv_split_edges_gpu.py is for, as assertions on the list it complements.  One K-step IS in that list —
+    the score_ launch (3, 8, 8, 16, 256), 192 rows on four full 64-wide tiles, once with a prologue — so the assertions below are
+    about where it is not: on a 128-wide tile, on a ragged N tile, with a filter."""
+    cases = _existing_split_cases()
+    assert len(cases) == 10 + 11
+    plans = [(c, P.conv_split(c)) for c in cases]
+    assert all(pl is not None for _, pl in plans)
+    gemm = [(c, pl) for c, pl in plans if pl['kernel'] == 'gemm']
+    halo = [(c, pl) for c, pl in plans if pl['kernel'] == 'halo']
+    assert len(gemm) == 15 and len(halo) == 6
+    # ---- K-steps: one only on (3, 8, 8, 16, 256) 1x1; otherwise even
+    one = [c for c, pl in gemm if pl['nsteps'] == 1]
+    assert one == [(3, 8, 8, 16, 256, 1, 1, 1, 0, 1)] and P.conv_split(one[0])['bn'] == 64 and not P.conv_split(one[0])['ragged_n']
+    assert all(pl['nsteps'] % 2 == 0 for c, pl in gemm if c not in one)
+    # ---- the tap never changes at every K-step away from the 1x1 filter (Cin == 16 under a filter); R == S; at most 9 taps
+    assert all(c[5] == c[6] and c[5] * c[6] <= 9 for c in cases)
+    assert not [c for c in cases if c[3] == 16 and c[5] * c[6] > 1]
+    # ---- Ho <= H; one trip of the prologue's copy; the vectors never push the LDS request past the epilogue's tile
+    assert all((c[1] + 2 * c[8] - c[9] * (c[5] - 1) - 1) // c[7] + 1 <= c[1] for c in cases)
+    assert max(c[3] for c in cases) == 256 and all(pl['trips'] == 1 for _, pl in gemm)
+    # ---- N tiles: Cout is 16, 64, 128, 160 or 256 — never a multiple of 4 that is no multiple of 16, never a lone float4 column
+    assert sorted(set(c[4] for c in cases)) == [16, 64, 128, 160, 256] and all(c[4] % 16 == 0 for c in cases)
+    assert [c for c, pl in plans if pl['ragged_n'] and pl['ntiles'] > 1] == [(1, 24, 48, 32, 160, 3, 3, 1, 1, 1)]      # 32 of 128 columns: halo
+    assert all(pl['bn'] - (-c[4]) % pl['bn'] >= 16 for c, pl in plans)
+    # ---- the 64 / 128-column threshold (8192 rows): where it decides (Cout % 64 == 0, above 64), 512 rows at the most or 65536
+    rows = sorted(set(pl['M'] for c, pl in gemm if c[4] > 64 and c[4] % 64 == 0))
+    assert rows == [35, 128, 192, 512, 65536]
+    # ---- row tiles: the only ragged ones hold 35 and 32 (of 288) and 64 (of 192) rows — never one row; at most two images in a tile
+    assert sorted(set(pl['M'] % 128 for _, pl in gemm if pl['ragged_m'])) == [32, 35, 64]
+    assert all(c[0] == 1 or c[1] * c[2] >= 64 for c in cases)
+    # ---- the halo kernel: TN = 1 only on whole tiles; at most six chunks; several images only of one tile COLUMN or more
+    assert all(not (pl['bn'] == 64 and pl['ragged_n']) and pl['nchunks'] <= 8 for _, pl in halo)
+    assert not [c for c, _ in halo if c[0] > 1 and c[1] == 8 and c[2] == 16]
+    assert not [c for c, _ in halo if c[1] == 16 and c[2] == 32]
+
+
+# case -> what plan_ref.conv_split must say of it (every path), and the LDS request per path (bf16x6, f16x3)
+CONV_SPLIT_WANT = {
+    (1, 3, 5, 16, 4, 1, 1, 1, 0, 1): (dict(kernel='gemm', bn=64, M=15, nsteps=1, mtiles=1, ntiles=1, trips=1), (55424, 36992)),
+    (1, 8, 16, 32, 64, 1, 1, 1, 0, 1): (dict(kernel='gemm', bn=64, M=128, nsteps=2, mtiles=1, ntiles=1, ragged_m=False, ragged_n=False),
+                                        (55552, 37120)),
+    (1, 3, 43, 48, 68, 1, 1, 1, 0, 1): (dict(kernel='gemm', bn=128, M=129, nsteps=3, mtiles=2, ntiles=1, ragged_n=True), (74112, 67584)),
+    (2, 7, 9, 16, 132, 3, 3, 1, 1, 1): (dict(kernel='gemm', bn=128, M=126, nsteps=9, mtiles=1, ntiles=2, ragged_n=True), (73856, 67584)),
+    (3, 5, 7, 16, 64, 3, 3, 1, 1, 1): (dict(kernel='gemm', bn=64, M=105, nsteps=9, mtiles=1, ntiles=1), (55424, 36992)),
+    (1, 9, 11, 32, 192, 1, 3, 1, 1, 1): (dict(kernel='gemm', bn=64, M=121, nsteps=6, mtiles=1, ntiles=3, ragged_n=False), (55552, 37120)),
+    (1, 12, 10, 16, 8, 4, 4, 2, 1, 1): (dict(kernel='gemm', bn=64, M=30, nsteps=16, mtiles=1, ntiles=1), (55424, 36992)),
+    (1, 15, 13, 48, 128, 3, 3, 2, 1, 1): (dict(kernel='gemm', bn=64, M=56, nsteps=27, mtiles=1, ntiles=2, ragged_n=False), (55680, 37248)),
+    (1, 11, 14, 32, 96, 3, 2, 2, 2, 2): (dict(kernel='gemm', bn=128, M=48, nsteps=12, mtiles=1, ntiles=1, ragged_n=True), (73984, 67584)),
+    (1, 4, 8, 528, 72, 1, 1, 1, 0, 1): (dict(kernel='gemm', bn=128, M=32, nsteps=33, mtiles=1, ntiles=1, trips=3), (77952, 67584)),
+    (2, 64, 64, 16, 128, 1, 1, 1, 0, 1): (dict(kernel='gemm', bn=64, M=8192, nsteps=1, mtiles=64, ntiles=2), (55424, 36992)),
+    (1, 65, 128, 16, 128, 1, 1, 1, 0, 1): (dict(kernel='gemm', bn=128, M=8320, nsteps=1, mtiles=65, ntiles=1), (73856, 67584)),
+    (1, 8, 16, 32, 4, 3, 3, 1, 1, 1): (dict(kernel='halo', bn=64, nchunks=2, mtiles=1, ntiles=1, ragged_n=True), (46080, 49152)),
+    (2, 8, 48, 64, 36, 3, 3, 1, 1, 1): (dict(kernel='halo', bn=64, nchunks=4, mtiles=6, ntiles=1, ragged_n=True), (46080, 49152)),
+    (1, 24, 16, 96, 64, 3, 3, 1, 1, 1): (dict(kernel='halo', bn=64, nchunks=6, mtiles=3, ntiles=1, ragged_n=False), (46080, 49152)),
+    (1, 16, 32, 160, 132, 3, 3, 1, 1, 1): (dict(kernel='halo', bn=128, nchunks=10, mtiles=4, ntiles=2, ragged_n=True), (67584, 67584)),
+    (3, 8, 16, 32, 128, 3, 3, 1, 1, 1): (dict(kernel='halo', bn=128, nchunks=2, mtiles=3, ntiles=1, ragged_n=False), (67584, 67584)),
+}
+
+
+def test_conv_split_cases_hit_their_edges():
+    assert list(CONV_SPLIT_WANT) == E.CONV_SPLIT and len(set(E.CONV_SPLIT)) == 17
+    plans = {}
+    for case in E.CONV_SPLIT:
+        figs, lds = CONV_SPLIT_WANT[case]
+        for path, want_lds in zip(('bf16x6', 'f16x3'), lds):
+            pl = P.conv_split(case, path)
+            assert pl and all(pl[k] == v for k, v in figs.items()) and pl['lds'] == want_lds, (case, path, pl)
+        assert {k: v for k, v in P.conv_split(case, 'f16x3').items() if k != 'lds'} == {k: v for k, v in P.conv_split(case).items() if k != 'lds'}
+        plans[case] = P.conv_split(case)
+    # all four (kernel, tile width) cells
+    assert {(pl['kernel'], pl['bn']) for pl in plans.values()} == {('gemm', 64), ('gemm', 128), ('halo', 64), ('halo', 128)}
+    gemm = {c: pl for c, pl in plans.items() if pl['kernel'] == 'gemm'}
+    halo = {c: pl for c, pl in plans.items() if pl['kernel'] == 'halo'}
+    assert len(gemm) == 12 and len(halo) == 5
+    # K-steps: one on both tile widths, odd counts past one on both, even ones; the tap of a filter changing at every K-step
+    assert {pl['bn'] for pl in gemm.values() if pl['nsteps'] == 1} == {64, 128}
+    assert {pl['bn'] for pl in gemm.values() if pl['nsteps'] % 2 == 1 and pl['nsteps'] > 1} == {64, 128}
+    assert {pl['nsteps'] for pl in gemm.values()} == {1, 2, 3, 6, 9, 12, 16, 27, 33}
+    assert sum(1 for c in gemm if c[3] == 16 and c[5] * c[6] > 1) == 3
+    # R != S (both orders of magnitude: 1 x 3, 3 x 2); 16 taps at stride 2: bit 2 * 15 + 1 of the loader's tap mask
+    assert {(c[5], c[6]) for c in gemm if c[5] != c[6]} == {(1, 3), (3, 2)}
+    assert [c for c in gemm if c[5] * c[6] == 16 and c[7] == 2] == [(1, 12, 10, 16, 8, 4, 4, 2, 1, 1)] and 15 * 2 + 1 == 31
+    # output rows that see padding only: pad = 1 under a filter of ONE row
+    c = (1, 9, 11, 32, 192, 1, 3, 1, 1, 1)
+    assert c[5] == 1 and c[8] == 1 and 9 + 2 * 1 - (1 - 1) == 11 > c[1]
+    # the prologue's copy: three trips, the last of 16 channels; the bf16x6 request above 64 KB BECAUSE of the vectors behind the tiles
+    c = (1, 4, 8, 528, 72, 1, 1, 1, 0, 1)
+    assert plans[c]['trips'] == 3 and 528 - 2 * 256 == 16 and plans[c]['lds'] == 2 * 3 * 256 * 48 + 2 * 528 * 4 > 128 * 132 * 4 > 65536
+    assert all(pl['trips'] == 1 for k, pl in gemm.items() if k != c)
+    # the row threshold from both sides, the same channels
+    lo, hi = (2, 64, 64, 16, 128, 1, 1, 1, 0, 1), (1, 65, 128, 16, 128, 1, 1, 1, 0, 1)
+    assert lo[3:] == hi[3:] and plans[lo]['M'] == P.FWD6_BN64_ROWS and plans[hi]['M'] == P.FWD6_BN64_ROWS + 128
+    assert (plans[lo]['bn'], plans[hi]['bn']) == (64, 128) and plans[hi]['mtiles'] % 8 != 0
+    # ragged N: one float4 column (both kernels), a second tile of four columns (both), 60 and 32 of 128 columns masked
+    assert {pl['kernel'] for c, pl in plans.items() if c[4] == 4} == {'gemm', 'halo'}
+    assert {pl['kernel'] for c, pl in plans.items() if c[4] == 132 and pl['ntiles'] == 2} == {'gemm', 'halo'}
+    assert {c[4] for c, pl in gemm.items() if pl['bn'] == 128} == {68, 72, 96, 128, 132} and {c[4] for c, pl in halo.items() if pl['bn'] == 64} == {4, 36, 64}
+    # ragged M: one valid row in the last tile; two and three images inside one tile
+    assert plans[(1, 3, 43, 48, 68, 1, 1, 1, 0, 1)]['M'] % 128 == 1
+    assert {c[0] for c, pl in gemm.items() if pl['mtiles'] == 1 and c[0] > 1} == {2, 3}
+    # the halo kernel: chunk-pair loop once, twice, three and five times; tiles side by side, stacked, 2 x 2, one per image
+    assert sorted(pl['nchunks'] // 2 for pl in halo.values()) == [1, 1, 2, 3, 5]
+    assert {(c[0], c[1] // 8, c[2] // 16) for c in halo} == {(1, 1, 1), (2, 1, 3), (1, 3, 1), (1, 2, 2), (3, 1, 1)}
