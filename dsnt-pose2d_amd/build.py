@@ -15,7 +15,7 @@ LIB = os.path.join(CSRC, 'libdsnt_hip.so')
 # the general convolution units: built without the SLP vectoriser whatever DSNT_SLP says (see build())
 NO_SLP = ('conv_f32.hip', 'conv_split6.hip', 'conv_wgrad.hip', 'wgrad_gemm.hip', 'wgrad_reduce.hip', 'conv_prep.hip')
 # (longest compiles first: four run at a time; the short element-wise units last)
-SOURCES = ['api.cpp', 'conv3s.hip', 'conv3s_mf.hip', 'head_loss.hip', 'head_fwd.hip', 'head_ops.hip', 'gemm1.hip', 'conv_split6.hip',
+SOURCES = ['api.cpp', 'conv3s.hip', 'conv3s_mf.hip', 'head_loss.hip', 'head_fwd.hip', 'head_ops.hip', 'distill.hip', 'gemm1.hip', 'conv_split6.hip',
            'conv_f32.hip', 'wgrad3.hip', 'bwd1.hip', 'fwd1.hip', 'wgrad_gemm.hip', 'wgrad1.hip', 'augment.hip', 'conv_prep.hip', 'stem4.hip',
            'heatmap.hip', 'dgrad_up.hip', 'render.hip', 'bn.hip', 'resample.hip', 'flat.hip', 'optim.hip', 'pckh.hip', 'modes.hip', 'sampler.hip', 'occlude.hip',
            'wgrad_reduce.hip', 'conv_wgrad.hip']

@@ -33,7 +33,7 @@ int dsnt_device_cus(void) {
     return c;
 }
 
-extern "C" int dsnt_version(void) { return 132; }      // 132: dsnt_list_fuse*, dsnt_list_stages and dsnt_list_stage_errors are REMOVED (the persistent stage is retired; not additive)      // 131 (additive): dsnt_occlude      // 130 (additive): dsnt_sample_cdf, dsnt_sample_indices, dsnt_example_scores      // 129 (additive): dsnt_map_modes      // 128 (additive): dsnt_joint_confusion, dsnt_target_mass      // 127 (additive): dsnt_pckh_boot      // 126 (additive): dsnt_score_hist, dsnt_score_lookup      // 124 (additive): dsnt_conv1x1_fwd_ds_f16x3      // 123 (additive): dsnt_render_pose      // 122 (additive): dsnt_pckh_hist      // 121: dsnt_scale_by_scalar takes any n and alignment (a 1-row 7x7 head has 49 logits)      // 120 (additive): dsnt_heatmap_stats, dsnt_flip_merge_head_stats      // 119 (additive): dsnt_crop_affine      // 118 (additive): dsnt_epoch_indices, dsnt_augment_fwd_gather, dsnt_augment_fwd_pair_gather, dsnt_augment_keypoints_gather      // 117 (additive): dsnt_conv_f16x3_route      // 116 (additive): dsnt_flip_merge_head, dsnt_augment_fwd_pair      // 115 (additive): dsnt_augment_fwd, dsnt_augment_keypoints, dsnt_pool_normalize      // 114 (additive): dsnt_list_fuse*, dsnt_list_stages      // 113 (additive): dsnt_conv_fwd_stream_form      // 112 (additive): dsnt_conv_dgrad_f16x3_stream_apply      // 110: dsnt_f16_prep_weights takes its row width; dsnt_conv1x1_bwd_*; 111 (additive): dsnt_conv1x1_fwd_*, DSNT_BN_FROZEN, dsnt_maxpool2_bwd_add
+extern "C" int dsnt_version(void) { return 133; }      // 133 (additive): dsnt_distill_rows, dsnt_distill_loss_grad      // 132: dsnt_list_fuse*, dsnt_list_stages and dsnt_list_stage_errors are REMOVED (the persistent stage is retired; not additive)      // 131 (additive): dsnt_occlude      // 130 (additive): dsnt_sample_cdf, dsnt_sample_indices, dsnt_example_scores      // 129 (additive): dsnt_map_modes      // 128 (additive): dsnt_joint_confusion, dsnt_target_mass      // 127 (additive): dsnt_pckh_boot      // 126 (additive): dsnt_score_hist, dsnt_score_lookup      // 124 (additive): dsnt_conv1x1_fwd_ds_f16x3      // 123 (additive): dsnt_render_pose      // 122 (additive): dsnt_pckh_hist      // 121: dsnt_scale_by_scalar takes any n and alignment (a 1-row 7x7 head has 49 logits)      // 120 (additive): dsnt_heatmap_stats, dsnt_flip_merge_head_stats      // 119 (additive): dsnt_crop_affine      // 118 (additive): dsnt_epoch_indices, dsnt_augment_fwd_gather, dsnt_augment_fwd_pair_gather, dsnt_augment_keypoints_gather      // 117 (additive): dsnt_conv_f16x3_route      // 116 (additive): dsnt_flip_merge_head, dsnt_augment_fwd_pair      // 115 (additive): dsnt_augment_fwd, dsnt_augment_keypoints, dsnt_pool_normalize      // 114 (additive): dsnt_list_fuse*, dsnt_list_stages      // 113 (additive): dsnt_conv_fwd_stream_form      // 112 (additive): dsnt_conv_dgrad_f16x3_stream_apply      // 110: dsnt_f16_prep_weights takes its row width; dsnt_conv1x1_bwd_*; 111 (additive): dsnt_conv1x1_fwd_*, DSNT_BN_FROZEN, dsnt_maxpool2_bwd_add
 extern "C" const char* dsnt_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------ launch lists

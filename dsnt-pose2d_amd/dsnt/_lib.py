@@ -95,6 +95,8 @@ SIGNATURES = {
     'dsnt_mask_denom': [P, P, L, P],
     'dsnt_head_loss_reduce': [P, P, P, P, F, P, P, L, P],
     'dsnt_scale_by_scalar': [P, P, L, P],
+    'dsnt_distill_rows': [P, P, P, L, L, I, I, F, I, P],
+    'dsnt_distill_loss_grad': [P, P, P, P, P, P, L, L, I, I, F, I, P],
     'dsnt_conv_fwd': [P, P, P, P, P, P, I, P, P, P, GP, P],
     'dsnt_conv_fwd_ex': [P, P, P, P, P, P, I, P, P, P, GP, BP, TP, P],
     'dsnt_conv_fwd_bf16x6_ex': [P, P, L, P, P, P, P, I, P, P, P, GP, BP, TP, P],

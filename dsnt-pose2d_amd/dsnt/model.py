@@ -49,6 +49,33 @@ class HumanPoseModel(nn.Module):
     def compute_coords(self, out_var):
         raise NotImplementedError()
 
+    def forward_distill_loss(self, teacher_logits, mask_var=None, kind='kl', temperature=1.0):
+        """The distillation term of the last `forward` against a teacher's heat-map logits `[B, J, h, w]`
+        (`teacher_logits(teacher, x)`), summed over the stacks as `forward_loss` sums them, so that
+
+            loss = model.forward_loss(out, target, mask) + alpha * model.forward_distill_loss(teacher_hm)
+
+        weighs the two per stack alike.  Per stack it is `dsnt.nn.distill_loss(logits, teacher_logits, mask_var, kind,
+        temperature)`; a hourglass's slab of S stacks takes one launch, S times the average over all S B J rows (the same
+        number for a mask that keeps at least one row, or none).  It needs no labels and back-propagates on its own.  The
+        teacher is a constant.  Only for softmax heat-maps (`output_strat` 'dsnt' or 'fc' with `preact='softmax'`), and
+        only for a teacher whose maps have the student's size."""
+        if self.output_strat == 'gauss' or self.preact != 'softmax':
+            raise ValueError('forward_distill_loss needs softmax heat-maps of logits: output_strat=%r, preact=%r'
+                             % (self.output_strat, self.preact))
+        logits = getattr(self, '_distill_logits', None)
+        if logits is None:
+            raise RuntimeError('forward_distill_loss: no forward pass yet (call forward or forward_part2 first)')
+        size, t_size = tuple(logits[0].shape[-2:]), tuple(teacher_logits.shape[-2:])
+        if size != t_size:
+            raise ValueError('forward_distill_loss: the teacher\'s maps are %dx%d, the student\'s %dx%d (resample the '
+                             'teacher first)' % (t_size + size))
+        total = 0
+        for x in logits:        # a slab [S, B, J, H, W] counts S times, a stack [B, J, H, W] once
+            term = dnn.distill_loss(x, teacher_logits, mask_var, kind, temperature)
+            total = total + (x.size(0) * term if x.dim() == 5 else term)
+        return total
+
 
 class HourglassHumanPoseModel(HumanPoseModel):
     def __init__(self, hg, n_chans=16, output_strat='gauss', preact='softmax', reg='none',
@@ -86,6 +113,7 @@ class HourglassHumanPoseModel(HumanPoseModel):
         is iterated along dim 0 like the reference does for test-time flip averaging)."""
         out = []
         self._fused = {}
+        self._distill_logits = None      # what forward_distill_loss reads: the logits of this call, a slab or one per stack
         if self.output_strat == 'gauss':
             self.heatmaps_array = hg_outs
             return hg_outs
@@ -95,16 +123,19 @@ class HourglassHumanPoseModel(HumanPoseModel):
             # every stack's head in ONE launch on the slab the hourglass hands out ([S, N, J, H, W]; rows = S N J)
             S = stacked.size(0)
             x4 = stacked.reshape(-1, stacked.size(-3), stacked.size(-2), stacked.size(-1))
+            self._distill_logits = [x4.view(S, -1, *x4.shape[1:])]
             hm, coords = dnn.head_forward(x4)
             out = list(coords.view(S, -1, coords.size(-2), 2).unbind(0))
             self.heatmaps_array = list(hm.view(stacked.shape).unbind(0))
             self._fused_all = (x4, hm, coords, out)
             return out
+        if self.preact == 'softmax':
+            self._distill_logits = [x.reshape(-1, x.size(-3), x.size(-2), x.size(-1)) for x in hg_outs]
         if self.output_strat == 'dsnt':
             self.heatmaps_array = []
-            for x in hg_outs:
+            for i, x in enumerate(hg_outs):
                 if self.preact == 'softmax':
-                    x4 = x.reshape(-1, x.size(-3), x.size(-2), x.size(-1))
+                    x4 = self._distill_logits[i]
                     hm, coords = dnn.head_forward(x4)          # one fused pass
                     self._fused[id(coords)] = (x4, hm, coords)
                 else:
@@ -235,9 +266,10 @@ class ResNetHumanPoseModel(HumanPoseModel, hourglass.TapeModule):
     def forward_part2(self, x):
         """Forward from unnormalized heatmaps to output"""
         self._fused = {}
+        x4 = x.reshape(-1, x.size(-3), x.size(-2), x.size(-1))
+        self._distill_logits = [x4] if self.preact == 'softmax' and self.output_strat != 'gauss' else None
         if self.output_strat == 'dsnt':
             if self.preact == 'softmax':
-                x4 = x.reshape(-1, x.size(-3), x.size(-2), x.size(-1))
                 hm, coords = dnn.head_forward(x4)
                 self._fused[id(coords)] = (x4, hm, coords)
             else:
@@ -303,6 +335,24 @@ def _build_hg_model(base, stacks=2, blocks=1, output_strat='gauss', preact='soft
     backbone = hourglass.HourglassNet(hourglass.Bottleneck, num_stacks=n_stacks, num_blocks=blocks)
     head = dict(output_strat=output_strat, preact=preact, reg=reg, reg_coeff=reg_coeff, hm_sigma=hm_sigma)
     return HourglassHumanPoseModel(backbone, n_chans=16, **head)
+
+
+def teacher_logits(teacher, x):
+    """The heat-map logits a teacher model gives for the images `x`: the last stack's of `teacher.forward_part1(x)`, as a
+    contiguous fp32 `[B, J, h, w]` of its own, for `forward_distill_loss`.  Runs without autograd and in eval mode
+    (BatchNorm's running statistics), and leaves the `training` flag of the teacher and of each of its submodules as it
+    found it."""
+    was_training = [(mod, mod.training) for mod in teacher.modules()]
+    teacher.eval()
+    try:
+        with torch.no_grad():
+            out = teacher.forward_part1(x)
+    finally:
+        for mod, flag in was_training:
+            mod.training = flag
+    if not torch.is_tensor(out):
+        out = out[-1]
+    return out.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
 
 
 _BUILDERS = (('resnet', _build_resnet_pose_model), ('hg', _build_hg_model))

@@ -510,3 +510,67 @@ def mask_denominator(mask, rows, device):
 def head_loss(logits, hm, coords, target, mask, reg, sigma, reg_coeff, denom2=None):
     kind = REG_KINDS.get(reg, -1)
     return _HeadLoss.apply(logits, hm, coords, target, mask, kind, float(sigma), float(reg_coeff), denom2)
+
+
+# ------------------------------------------------------------------ heat-map distillation (csrc/distill.hip)
+DISTILL_KINDS = {'js': 0, 'kl': 1, 'mse': 2}      # the numbers of REG_KINDS
+
+
+class _DistillLoss(Function):
+    """masked_average of the per-row distillation loss, straight from the two logit tensors (follows `_HeadLoss`).
+
+    Gradients wanted: ONE kernel reads both maps and leaves the per-row values and d loss / d student logits for an
+    upstream gradient of 1 (`dsnt_distill_loss_grad`); backward only rescales it when the upstream gradient is not 1.
+    Otherwise: `dsnt_distill_rows`.  The teacher is a constant: its gradient is None."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, mask, kind, temperature):
+        s, t = f32(student).contiguous(), f32(teacher).contiguous()
+        h, w = s.shape[-2], s.shape[-1]
+        rows, teacher_rows = _rows(s, 2), _rows(t, 2)
+        m = None if mask is None else mask.to(torch.float32).expand(s.shape[:-2]).contiguous()
+        loss_row = torch.empty(rows, device=s.device, dtype=s.dtype)
+        ctx.g0 = None
+        if ctx.needs_input_grad[0]:
+            denom2 = None if m is None else mask_denominator(m, rows, s.device)      # no mask: the kernel's 1 / rows
+            g0 = torch.empty_like(s)
+            call('dsnt_distill_loss_grad', ptr(s), ptr(t), ptr(m), ptr(denom2), ptr(loss_row), ptr(g0), rows,
+                 teacher_rows, h, w, temperature, kind)
+            ctx.g0 = g0
+        else:
+            call('dsnt_distill_rows', ptr(s), ptr(t), ptr(loss_row), rows, teacher_rows, h, w, temperature, kind)
+        out2 = torch.empty(2, device=s.device, dtype=s.dtype)
+        call('dsnt_masked_avg_fwd', ptr(loss_row), ptr(m), ptr(out2), rows)
+        return out2[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        g_logits, ctx.g0 = ctx.g0, None
+        if g_logits is None:
+            raise RuntimeError('dsnt: distill_loss keeps its gradient for one backward pass')
+        call('dsnt_scale_by_scalar', ptr(g_logits), ptr(f32(g).contiguous().view(1)), g_logits.numel())
+        return g_logits, None, None, None, None
+
+
+def distill_loss(student_logits, teacher_logits, mask=None, kind='kl', temperature=1.0):
+    """Average distillation loss between a student's and a teacher's heat-map LOGITS (`[..., J, H, W]`, before any softmax).
+
+    Per `(…, joint)` row, with `lq = log_softmax(student / T)`, `lp = log_softmax(teacher / T)` over the `H * W` pixels,
+    `q = exp(lq)`, `p = exp(lp)` and `T = temperature > 0`:
+      * `kind='kl'`:  `T^2 sum p (lp - lq)`, KL(teacher || student), the usual distillation term.  Mind the order: it is the
+        opposite of `kl_reg_loss`, which is KL(heat-map || target);
+      * `kind='js'`:  `T^2` times the Jensen-Shannon divergence of p and q;
+      * `kind='mse'`: `T^2 sum (q - p)^2`.
+    Everything is formed in the log domain from the logits: there is no `eps`, and a pixel whose probability underflows
+    contributes 0.  `teacher_logits` has the student's shape, or the shape of its trailing dimensions, which the student's
+    leading dimensions then repeat (student `[S, B, J, H, W]` against teacher `[B, J, H, W]`: nothing is expanded in
+    memory); anything else raises `ValueError`.  `mask` broadcasts to the student's `[..., J]`; the result is
+    `masked_average(rows, mask)` over all student rows.  The teacher is treated as a constant: it gets no gradient,
+    whatever it requires.  Device tensors only."""
+    if kind not in DISTILL_KINDS:
+        raise ValueError('dsnt: distill_loss: unknown kind %r (one of %s)' % (kind, ', '.join(sorted(DISTILL_KINDS))))
+    ss, ts = tuple(student_logits.shape), tuple(teacher_logits.shape)
+    if len(ss) < 3 or len(ts) < 3 or len(ts) > len(ss) or ss[len(ss) - len(ts):] != ts:
+        raise ValueError('dsnt: distill_loss: teacher logits %s do not match student logits %s ([..., J, H, W]: the same '
+                         'shape, or that of its trailing dimensions)' % (ts, ss))
+    return _DistillLoss.apply(student_logits, teacher_logits.detach(), mask, DISTILL_KINDS[kind], float(temperature))

@@ -202,6 +202,26 @@ int dsnt_scale_by_scalar(float* x, const float* s, int64_t n, void* stream);
 int dsnt_head_bwd(const float* hm, const float* coords, const float* target, const float* dist,
                   const float* g_dist, const float* g_reg, float* g_logits, int64_t rows,
                   int h, int w, float sigma, int reg_kind, void* stream);
+/* Heat-map distillation: per student row s and teacher row t of h x w LOGITS, temperature T > 0,
+ *   lq = log_softmax(s / T), lp = log_softmax(t / T), q = exp(lq), p = exp(lp),
+ *   kind 1 (kl):  loss_row = T^2 sum p (lp - lq)                      KL(teacher || student)
+ *   kind 0 (js):  loss_row = T^2 (sum p (lp - lm) + sum q (lq - lm)) / 2,  lm = logaddexp(lp, lq) - ln 2
+ *   kind 2 (mse): loss_row = T^2 sum (q - p)^2
+ * formed in the log domain (no eps; a term whose p or q underflows contributes 0).  Student row r pairs with teacher
+ * row r % teacher_rows (rows % teacher_rows == 0): a slab [S][B][J][h][w] reads a teacher [B][J][h][w] in place.
+ * Any h * w < 2^24: rows of up to 4096 pixels are read from HBM once.  dsnt_version() >= 133. */
+int dsnt_distill_rows(const float* student, const float* teacher, float* loss_row, int64_t rows, int64_t teacher_rows,
+                      int h, int w, float temperature, int kind, void* stream);
+/* The same loss_row AND the gradient with respect to the student's logits, the teacher a constant, in one launch, by
+ * dsnt_head_loss_grad's convention (bit for bit the same loss_row when both calls take the same variant: always, unless
+ * h * w % 4 == 0, student and teacher are 16-byte aligned and g_logits is not — this call then reads one float at a time):
+ *   g_logits[row] = w_row d loss_row / d s,   w_row = mask[row] / denom2[1]   (mask NULL: 1 / rows, denom2 unused),
+ *   d loss_row / d s_j = T (q_j - p_j) (kl),  T q_j (v_j - sum_i q_i v_i) with v = (lq - lm) / 2 (js), 2 (q - p) (mse);
+ * a row of mask 0 gets a gradient of exactly 0.  denom2 = the 2 floats dsnt_mask_denom left; dsnt_scale_by_scalar
+ * applies an upstream gradient other than 1.  dsnt_version() >= 133. */
+int dsnt_distill_loss_grad(const float* student, const float* teacher, const float* mask, const float* denom2,
+                           float* loss_row, float* g_logits, int64_t rows, int64_t teacher_rows, int h, int w,
+                           float temperature, int kind, void* stream);
 
 /* --------------------------------------------------------------- convolutions
  * Implicit-GEMM on fp32 MFMA (v_mfma_f32_32x32x2_f32).  Replaces nn.Conv2d forward
